@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """clips/s of the VideoTGB video -> LLM hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--clips B] [--flow precomputed|raft]     (N > 1 without a launcher: spawns the ranks)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--clips B] [--flow precomputed|raft] [--dump-outputs DIR]     (N > 1 without a launcher: spawns the ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+--dump-outputs DIR writes what the last timed step returned (generated token ids, selected frame indices; every rank's rows in rank
+order) as DIR/<name>.npy in float64.  Inputs and weights are seeded, so two builds run with the same arguments compare output for output.
 
 Workload (config.workload): InstructBLIP-Vicuna-7B + TGB, T = 96 flow frames -> 8 of 32 candidate
 frames, bf16, greedy decode of 16 new tokens (BASELINE.json configs[2], the configuration the
@@ -40,6 +43,7 @@ import torch.distributed as dist  # noqa: E402
 PEAK_BF16_TFLOPS = 2500.0   # dense bf16 / fp16 MFMA peak, /opt/skills/guides/MI355X_MICROARCH.md "Chip-level parameters"
 PEAK_F32_MFMA_TFLOPS = 157.3   # the fp32-input MFMA (= the fp32 vector rate): what the split-operand RAFT modes emulate on the 16-bit matrix cores
 VIT_GFLOP_PER_FRAME = 520.72   # SURVEY.md 8d / BASELINE.md 2
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: all arrays together
 
 
 def pmc_traffic(family="gemm"):
@@ -102,7 +106,13 @@ def parse():
                     "(the launch path of --gpus N, testable on a 1-GPU box)")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed (nccl = RCCL) even with one rank: exercises the "
                                                               "barrier / MAX-over-ranks path of the multi-GPU launch on a 1-GPU box")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned (generated token ids, selected frame indices; the rows "
+                         "of every rank in rank order) as DIR/<name>.npy in float64, which holds both exactly")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def synth_batch(rank, step_id, B, T, flow, dev, cfg):
@@ -175,7 +185,8 @@ def run_step(m, d, B, nframe, max_new_tokens, ev=None, decoder=None):
 def run_steps_overlapped(m, batches, steps, B, nframe, max_new_tokens, decoder, side):
     """K passes with the two halves of a pass on two HIP streams: the prefix stage of batch i+1 (MFMA-bound:
     ViT-g GEMMs) runs while the LLM decode of batch i (HBM-bound weight streaming) runs on `side`.  Every one of
-    the K batches is processed start to finish inside the caller's timed region (pipeline fill and drain included)."""
+    the K batches is processed start to finish inside the caller's timed region (pipeline fill and drain included).  Returns each
+    pass's (generated ids, frame indices), as run_step does."""
     main = torch.cuda.current_stream()
     outs = []
     for i in range(steps):
@@ -184,7 +195,7 @@ def run_steps_overlapped(m, batches, steps, B, nframe, max_new_tokens, decoder, 
         ready.record(main)
         with torch.cuda.stream(side):
             side.wait_event(ready)
-            outs.append(run_llm(m, emb, max_new_tokens, decoder))
+            outs.append((run_llm(m, emb, max_new_tokens, decoder), idx))
         emb.record_stream(side)
     main.wait_stream(side)
     return outs
@@ -335,6 +346,26 @@ def timed_steps(fn, steps, barrier, dev, world, per_rank=None):
     return float(t.item())
 
 
+def dump_outputs(dirname, outs, rank):
+    """--dump-outputs: {name: tensor} of the last timed step, every rank's rows gathered in rank order (a collective: all ranks
+    call it), written by rank 0 as DIR/<name>.npy in float64 (token ids and frame indices are exact in it)."""
+    import numpy as np
+    arrs = {}
+    for name, t in outs.items():
+        t = t.contiguous()
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            parts = [torch.empty_like(t) for _ in range(dist.get_world_size())]
+            dist.all_gather(parts, t)
+            t = torch.cat(parts, 0)
+        arrs[name] = t.double().cpu().numpy()
+    if rank != 0:
+        return
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrs.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    print(f"[bench] outputs of the last timed step -> {dirname}: " + ", ".join(f"{n} {list(a.shape)}" for n, a in arrs.items()), file=sys.stderr)
+
+
 def host_resident_leg(m, rank, B, T, nframe, max_new_tokens, decoder, dev, steps, barrier, world):
     """The same step with the clip tensors starting in PINNED HOST memory (what a decoder process hands over): a copy stream
     uploads batch i+1 (frames 19.3 MB + flow frames 57.8 MB per clip at T=96) while batch i computes; the upload of the first
@@ -409,6 +440,8 @@ def main():
     # 124 clips per step: 4 RAFT batches of 31, one ViT / Q-Former pass over 992 frames, one decode batch (the decode step
     # streams the 13.5 GB of LLM weights once per token whatever the batch: 3.4 ms per clip at 32 clips, 1.6 at 124)
     B, T, nframe = (args.clips or (124 if args.flow == "raft" else 62)), args.T, args.nframe
+    if args.dump_outputs and 8 * B * world * (args.max_new_tokens + nframe) > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {B * world} clips x ({args.max_new_tokens} ids + {nframe} indices) in float64 exceed {DUMP_MAX_BYTES >> 20} MB")
     batches = [synth_batch(rank, i, B, T, args.flow, dev, cfg) for i in range(2)]
     cpu_frames = batches[0]["flow_frames"][0, :17].cpu() if args.flow == "raft" else None      # cpu_baseline: 16 pairs of the GPU leg's first clip
     torch.cuda.synchronize()
@@ -434,18 +467,22 @@ def main():
     side = torch.cuda.Stream(priority=-1) if overlap else None   # decode stream: high priority, short memory-bound kernels
     if overlap:   # one untimed overlapped pass so that both streams have their handles / graph ready
         run_steps_overlapped(m, batches, 2, B, nframe, args.max_new_tokens, decoder, side)
+    last = [None]      # what the last timed step returned: (generated ids, frame indices)
     if overlap:
-        elapsed = timed_steps(lambda i: run_steps_overlapped(m, batches, args.steps, B, nframe, args.max_new_tokens, decoder, side) if i == 0 else None,
-                              1, barrier, dev, world, rank_times)
+        def all_steps(i):      # called once: the K overlapped passes are one timed unit
+            last[0] = run_steps_overlapped(m, batches, args.steps, B, nframe, args.max_new_tokens, decoder, side)[-1]
+        elapsed = timed_steps(all_steps, 1, barrier, dev, world, rank_times)
     else:
         def one(i):
             ev = [] if args.stage_times else None
-            run_step(m, batches[i % 2], B, nframe, args.max_new_tokens, ev, decoder)
+            last[0] = run_step(m, batches[i % 2], B, nframe, args.max_new_tokens, ev, decoder)
             if ev:
                 stage_ev.append(ev)
         elapsed = timed_steps(one, args.steps, barrier, dev, world, rank_times)
     total_clips = B * args.steps * world
     value = total_clips / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"generated_ids": last[0][0], "frame_indices": last[0][1]}, rank)
 
     # ---- roofline pass (untimed): the same step with HIP events around every GEMM / convolution / attention launch
     roofline = None

@@ -1,19 +1,13 @@
-"""CPU: the drop-in registration (videotgb_amd/dropin.py).  The first test needs nothing but this repo; the second runs the
-REFERENCE's own ``eval/utils/builder_utils.load_pretrained_model`` -- unmodified, imported from /root/reference -- and
-checks that it ends up constructing and loading the HIP-backed ``LSTP`` (skipped where the reference checkout is absent,
-e.g. on the GPU box: nothing under /root/reference travels)."""
+"""CPU: the drop-in registration (videotgb_amd/dropin.py).  The first test checks what ``install()`` registers; the second loads a
+reference-layout Lightning checkpoint the way the reference's eval loader does (``eval/utils/builder_utils.load_pretrained_model``,
+twinned by videotgb_amd.builder_utils) and checks that it ends up constructing and loading the HIP-backed ``LSTP`` that the drop-in
+hands to that loader under ``eval.utils.model``."""
 import importlib
-import importlib.machinery
-import os
 import sys
-import types
 
-import pytest
 import torch
 
 from conftest import full_state_dict, write_hf_config
-
-REF = "/root/reference"
 
 
 def test_install_registers_the_reference_module_paths():
@@ -37,47 +31,24 @@ def test_install_registers_the_reference_module_paths():
         "scheduler_params", "generate_configs"]
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "eval", "utils")), reason="reference checkout not present")
-def test_reference_builder_utils_builds_the_hip_model_unchanged(tmp_path):
-    from videotgb_amd import dropin, models
+def test_loader_builds_the_dropin_hip_model_from_a_reference_checkpoint(tmp_path):
+    from videotgb_amd import builder_utils, dropin, models, synth
     from videotgb_amd.synth import tiny_cfg
-    import transformers
-    _ = (transformers.AutoProcessor, transformers.AutoTokenizer, transformers.StoppingCriteria)   # resolve before torchvision is stubbed
-    stubbed = []
-    for name in ("av", "decord", "cv2", "ffmpeg", "sentence_transformers", "peft", "torchvision", "torchvision.transforms"):
-        if name not in sys.modules:                         # heavy optional imports of eval/utils/builder_utils.py, unused here
-            m = types.ModuleType(name)
-            m.__spec__ = importlib.machinery.ModuleSpec(name, None)
-            sys.modules[name] = m
-            stubbed.append(name)
-    sys.modules["decord"].cpu = lambda *a, **k: None
-    sys.modules["decord"].bridge = types.SimpleNamespace(set_bridge=lambda *a, **k: None)
-    for n in ("Compose", "RandomCrop", "RandomResizedCrop", "Normalize"):
-        setattr(sys.modules["torchvision.transforms"], n, type(n, (), {}))
-    for n in ("PeftModel", "PeftConfig", "get_peft_model", "get_peft_model_state_dict", "LoraConfig", "TaskType"):
-        setattr(sys.modules["peft"], n, object)
-    sys.path.insert(0, REF)
     dropin.install()
     try:
-        try:
-            bu = importlib.import_module("eval.utils.builder_utils")          # the reference's file, as is
-        except Exception as e:   # an import of the reference's own environment that this image lacks
-            pytest.skip(f"reference builder_utils not importable here: {e!r}")
-        assert bu.LSTP is models.LSTP and bu.LSTP_blip2 is models.LSTP_blip2
+        from eval.utils.model import LSTP     # noqa: the class eval/utils/builder_utils.py:14 imports
         cfg = tiny_cfg("instructblip")
         cfg.vit.image = 56
         base = write_hf_config(str(tmp_path / "instructblip-tiny"), "instructblip", cfg)
         # the reference's constructor call has no way to shrink the TGB: it is BERT-base (BertConfig(fusion_layer=6,
         # encoder_width=768)), so the checkpoint carries a full-size temporal_encoder
-        from videotgb_amd import synth
         cfg.tgb = synth.TgbCfg()
         sd = full_state_dict(cfg, models.build_language_model(models.load_hf_config(base, "instructblip")))
         ckpt = str(tmp_path / "last.ckpt")
         torch.save({"state_dict": sd}, ckpt)
-        bu.AutoProcessor = types.SimpleNamespace(from_pretrained=lambda *a, **k: "processor")
-        bu.AutoTokenizer = types.SimpleNamespace(from_pretrained=lambda *a, **k: "sampler_processor")
-        model, proc, sproc = bu.load_pretrained_model(ckpt, base, "bert-base-uncased", "cpu", False)
-        assert type(model) is models.LSTP and (proc, sproc) == ("processor", "sampler_processor")
+        # the reference loader's positional call (ckpt, base, sampler path, device, lora); strict load of ckpt["state_dict"]
+        model, proc, sproc = builder_utils.load_pretrained_model(ckpt, base, "bert-base-uncased", "cpu", False, load_processors=False)
+        assert type(model) is LSTP and (proc, sproc) == (None, None)
         got = model.state_dict()
         for k in ("model.qformer.encoder.layer.0.attention.attention.query.weight", "temporal_encoder.mrc_head.weight",
                   "of_extractor.update_block.gru.convz1.weight", "model.language_model.lm_head.weight"):
@@ -85,8 +56,3 @@ def test_reference_builder_utils_builds_the_hip_model_unchanged(tmp_path):
         assert hasattr(model, "generate") and model.model.config.use_decoder_only_language_model
     finally:
         dropin.uninstall()
-        sys.path.remove(REF)
-        for name in stubbed:
-            sys.modules.pop(name, None)
-        for name in [n for n in sys.modules if n == "eval" or n.startswith("eval.") or n == "src" or n.startswith("src.")]:
-            sys.modules.pop(name, None)

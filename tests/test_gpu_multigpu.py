@@ -4,6 +4,7 @@ context) at a tiny workload and checks the driver's JSON contract:
   * --force-dist: one rank initialises torch.distributed with the nccl (= RCCL) backend: init, barrier, MAX all-reduce of the timing;
   * --gpus 1 --spawn: the `python bench.py --gpus N` path -- bench.py re-launches itself through torch.distributed.run
     (spawn_ranks), rank 0 of the child prints the line;
+  * --dump-outputs DIR: the last timed step's token ids and frame indices land in DIR as float64 .npy files;
 and the gradient exchange of config C5 through the C ABI (vtgb_comm_* / vtgb_allreduce_f32) on a one-rank communicator."""
 import json
 import os
@@ -50,6 +51,19 @@ def test_bench_one_rank_over_rccl():
 def test_bench_spawned_through_torch_distributed_run():
     d, err = _run_bench(["--gpus", "1", "--spawn"])
     _check_line(d)
+
+
+def test_bench_dumps_the_outputs_of_the_last_timed_step(tmp_path):
+    import numpy as np
+    out = tmp_path / "outputs"
+    d, err = _run_bench(["--steps", "2", "--no-prof", "--dump-outputs", str(out)])
+    assert d["steps"] == 2
+    assert sorted(os.listdir(out)) == ["frame_indices.npy", "generated_ids.npy"]
+    ids, idx = np.load(out / "generated_ids.npy"), np.load(out / "frame_indices.npy")
+    assert ids.dtype == idx.dtype == np.float64
+    assert ids.shape == (2, 16) and idx.shape == (2, 8)                 # 2 clips, 16 new tokens, 8 of 32 frames
+    assert (ids == np.round(ids)).all() and ids.min() >= 0 and ids.max() < 32000
+    assert (idx == np.round(idx)).all() and idx.min() >= 0 and idx.max() < 32
 
 
 def test_allreduce_f32_through_the_c_abi_one_rank():
