@@ -18,6 +18,9 @@
  *     the reference's nn.Linear layout [out_features, in_features] row-major; for
  *     VTGB_F32 these are the state_dict tensors themselves, for VTGB_BF16 a one-time
  *     vtgb_pack_bf16() of them.  Biases, LayerNorm parameters, embeddings: always fp32.
+ *
+ * Added at version 601 without a version bump (the existing entries are unchanged): vtgb_tgb_trunk / vtgb_tgb_resume and their
+ * vtgb_tgb_split_args, the TGB split into a per-clip trunk and a per-question resume (see the TGB block below).
  */
 #ifndef VTGB_H
 #define VTGB_H
@@ -277,6 +280,35 @@ typedef struct {
 } vtgb_tgb_args;
 size_t vtgb_tgb_workspace_bytes(const vtgb_tgb_args* a);
 int vtgb_tgb_forward(const vtgb_tgb_args* a, vtgb_stream_t stream);
+
+/* ---- the same encoder split at its first question-dependent layer (clip sessions: many questions, one clip) -----------------
+ * vtgb_tgb_trunk runs the question-independent part on ONE clip (B == 1): TemporalOFEmbedding + its LayerNorm (xropebert.py:103-129)
+ * and the layers of `mode` before the first cross-attention layer -- [0, fusion_layer) for multi_modal, none for fusion, all for
+ * text / vision (:621-634) -- and leaves the residual stream in trunk (fp32) AND trunk_act (`dtype`, what the next layer's GEMMs
+ * read).  vtgb_tgb_resume runs B question rows against one trunk: the trunk replicated into B row blocks, RopeBertEmbeddings on
+ * the question (:190-208), the self / cross masks, the remaining layers and mrc_head (:1164).  Both share vtgb_tgb_forward's
+ * launch sequences and descriptors, so trunk + resume equals vtgb_tgb_forward on the clip repeated B times BIT FOR BIT (both
+ * dtypes, every mode, padded text masks).  Same weights table as vtgb_tgb_args; the *_workspace_bytes queries need no GPU and
+ * return 0 on bad arguments (last error set: "INVALID MODE", "bad dims"). */
+typedef struct {
+    int32_t dtype, B, L, n_text, hidden, heads, ffn, layers, fusion_layer, mode, image, patch;  /* trunk: B == 1, n_text unused */
+    float eps;
+    const float* of;            /* trunk: [1, L, 2, image, image] fp32 (resume: unused)        */
+    const int64_t* of_mask;     /* [1, L+2], the clip's (both)                                 */
+    const int64_t* text_ids;    /* resume: [B, n_text]                                         */
+    const int64_t* text_mask;   /* resume: [B, n_text]                                         */
+    const void* const* weights; /* host array, as vtgb_tgb_args                                */
+    float* trunk;               /* [L+2, hidden] fp32: written by the trunk, read by resume    */
+    void* trunk_act;            /* [L+2, hidden] `dtype`: same                                 */
+    float* seq_out;             /* resume: [B, L+2, hidden] or NULL                            */
+    float* logits;              /* resume: [B, L, 2]                                           */
+    void* workspace;
+    size_t workspace_bytes;
+} vtgb_tgb_split_args;
+size_t vtgb_tgb_trunk_workspace_bytes(const vtgb_tgb_split_args* a);
+int vtgb_tgb_trunk(const vtgb_tgb_split_args* a, vtgb_stream_t stream);
+size_t vtgb_tgb_resume_workspace_bytes(const vtgb_tgb_split_args* a);
+int vtgb_tgb_resume(const vtgb_tgb_split_args* a, vtgb_stream_t stream);
 
 /* ---- building blocks, exported for the per-kernel parity tests and the roofline bench ----
  * out[M, N] = epilogue(A[M, K] . W[N, K]^T + bias).  A, W in `dtype`; K % 8 == 0.       */

@@ -27,7 +27,8 @@ EXPORTS = [
     "vtgb_version", "vtgb_last_error", "vtgb_pack_bf16", "vtgb_span_select", "vtgb_span_to_frames",
     "vtgb_gather_frames", "vtgb_vit_patch_kpad", "vtgb_vit_workspace_bytes", "vtgb_vit_forward",
     "vtgb_qformer_workspace_bytes", "vtgb_qformer_forward", "vtgb_pool_project_workspace_bytes",
-    "vtgb_pool_project", "vtgb_tgb_workspace_bytes", "vtgb_tgb_forward", "vtgb_gemm", "vtgb_attention",
+    "vtgb_pool_project", "vtgb_tgb_workspace_bytes", "vtgb_tgb_forward", "vtgb_tgb_trunk_workspace_bytes", "vtgb_tgb_trunk",
+    "vtgb_tgb_resume_workspace_bytes", "vtgb_tgb_resume", "vtgb_gemm", "vtgb_attention",
     "vtgb_layernorm", "vtgb_prof_enable", "vtgb_prof_reset", "vtgb_prof_summary", "vtgb_prof_executed_flops",
     "vtgb_llm_rmsnorm", "vtgb_llm_rope_cache", "vtgb_llm_rope_cache_prefill", "vtgb_llm_decode_attention", "vtgb_llm_silu_mul",
     "vtgb_llm_attention_rows", "vtgb_llm_gated_act", "vtgb_llm_rmsnorm_parts", "vtgb_llm_rope_cache_parts", "vtgb_gemm_skinny_splits",
@@ -121,6 +122,14 @@ class TgbArgs(C.Structure):
                 ("seq_out", vp), ("logits", vp), ("workspace", vp), ("workspace_bytes", sz)]
 
 
+class TgbSplitArgs(C.Structure):
+    """vtgb_tgb_split_args: TgbArgs plus the trunk state (trunk fp32, trunk_act in the compute dtype) of vtgb_tgb_trunk / vtgb_tgb_resume."""
+    _fields_ = [("dtype", i32), ("B", i32), ("L", i32), ("n_text", i32), ("hidden", i32), ("heads", i32), ("ffn", i32),
+                ("layers", i32), ("fusion_layer", i32), ("mode", i32), ("image", i32), ("patch", i32), ("eps", f32),
+                ("of", vp), ("of_mask", vp), ("text_ids", vp), ("text_mask", vp), ("weights", C.POINTER(vp)),
+                ("trunk", vp), ("trunk_act", vp), ("seq_out", vp), ("logits", vp), ("workspace", vp), ("workspace_bytes", sz)]
+
+
 class RaftUpdateArgs(C.Structure):
     _fields_ = [("dtype", i32), ("n_pairs", i32), ("H8", i32), ("W8", i32), ("iters", i32), ("net", vp), ("inp", vp), ("corr", vp * 4),
                 ("weights", C.POINTER(vp)), ("flow_up", vp), ("workspace", vp), ("workspace_bytes", sz), ("corr_f16", i32), ("cnet_nhwc", vp),
@@ -199,10 +208,15 @@ def lib() -> C.CDLL:
         fn = getattr(L, "vtgb_" + name)
         fn.argtypes = [C.POINTER(st), vp]
         fn.restype = C.c_int
-    for name, st in (("vit", VitArgs), ("qformer", QFormerArgs), ("pool_project", PoolProjectArgs), ("tgb", TgbArgs)):
+    for name, st in (("vit", VitArgs), ("qformer", QFormerArgs), ("pool_project", PoolProjectArgs), ("tgb", TgbArgs),
+                     ("tgb_trunk", TgbSplitArgs), ("tgb_resume", TgbSplitArgs)):
         fn = getattr(L, f"vtgb_{name}_workspace_bytes")
         fn.argtypes = [C.POINTER(st)]
         fn.restype = sz
+    for name in ("tgb_trunk", "tgb_resume"):
+        fn = getattr(L, "vtgb_" + name)
+        fn.argtypes = [C.POINTER(TgbSplitArgs), vp]
+        fn.restype = C.c_int
     L.vtgb_pair_pack.argtypes = [i32, vp, vp, i64, i32, i32, vp]
     L.vtgb_pair_pack.restype = C.c_int
     L.vtgb_pair_conv.argtypes = [C.POINTER(PairConvArgs), vp]

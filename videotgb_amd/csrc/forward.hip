@@ -406,6 +406,96 @@ extern "C" int vtgb_pool_project(const vtgb_pool_project_args* a, vtgb_stream_t 
 // =======================================================================================
 // Temporal Grounding Bridge
 // =======================================================================================
+// The stages below are shared by vtgb_tgb_forward and the split entries (vtgb_tgb_trunk / vtgb_tgb_resume): each is the same
+// launch sequence with the same descriptors whichever entry calls it, and a row's result does not depend on how many rows a launch
+// holds (DESIGN.md "determinism and batch invariance"), so a trunk on one clip followed by a resume on B rows equals the forward on the
+// clip repeated B times bit for bit.
+namespace {
+struct TgbBufs {           // activations of the layer stack (workspace or caller-owned)
+    float* H; void* Hb; float* tmp; void* Tb; void* qkv; void* ctx; float* A1; void* A1b; void* kvc; void* inter;
+    const float* self_mask; const float* cross_mask;
+};
+}  // namespace
+
+// layers the mode runs (:621-634)
+static void tgb_layer_range(int mode, int layers, int fusion_layer, int* lo, int* hi) {
+    *lo = 0; *hi = layers;
+    if (mode == VTGB_TGB_MODE_TEXT) *hi = fusion_layer;
+    if (mode == VTGB_TGB_MODE_FUSION) *lo = fusion_layer;
+}
+// first layer of the mode that reads the question (cross attention from fusion_layer on); == hi when none does
+static int tgb_split_layer(int mode, int layers, int fusion_layer) {
+    int lo, hi;
+    tgb_layer_range(mode, layers, fusion_layer, &lo, &hi);
+    const int f = fusion_layer < hi ? fusion_layer : hi;
+    return f > lo ? f : lo;
+}
+
+// TemporalOFEmbedding (xropebert.py:103-129) + its LayerNorm: of [B, L, 2, image, image] -> H fp32 / Hb `dt` [B*(L+2), D];
+// patch axis reduced first (elementwise.hip)
+static int tgb_flow_embed(int dt, const void* const* w, const float* of, const int64_t* of_mask, int B, int L, int D, int image, int P,
+                          float* red, float* conv, float* tmp, float* H, void* Hb, hipStream_t s) {
+    const int g = image / P, kf = 2 * P * P;
+    const int64_t Ms = (int64_t)B * (L + 2), Mf = (int64_t)B * L;
+    VTGB_TRY(launch_flow_reduce(of, (const float*)w[8], red, (int)Mf, image, P, s));
+    VTGB_TRY(launch_gemm(gemm(VTGB_F32, (int)Mf, D, kf, VTGB_EPI_STORE_F32, red, kf, w[6], kf, nullptr, conv, D), s));
+    VTGB_TRY(launch_flow_assemble(conv, (const float*)w[7], (const float*)w[8], (const float*)w[9], (const float*)w[4], (const float*)w[5],
+                                  (const float*)w[10], of_mask, tmp, B, L, D, g * g, s));
+    return launch_layernorm(ln(dt, (int)Ms, D, 1e-5f, tmp, (const float*)w[11], (const float*)w[12], H, Hb), s);
+}
+
+// RopeBertEmbeddings on the question (:190-208) -> Tb `dt` [Mt, D]
+static int tgb_text_embed(int dt, const void* const* w, const int64_t* text_ids, int64_t Mt, int D, float eps, float* tmp, void* Tb,
+                          hipStream_t s) {
+    VTGB_TRY(launch_tgb_text_embed(text_ids, (const float*)w[0], (const float*)w[1], tmp, Mt, D, s));
+    return launch_layernorm(ln(dt, (int)Mt, D, eps, tmp, (const float*)w[2], (const float*)w[3], nullptr, Tb), s);
+}
+
+// encoder layers [lo, hi) over B rows of S tokens (:450-533); cross attention to the question from fusion_layer on
+static int tgb_layers(int dt, const void* const* w, int lo, int hi, int fusion_layer, int B, int S, int nt, int D, int heads, int ffn,
+                      float eps, const TgbBufs& b, hipStream_t s) {
+    const int64_t Ms = (int64_t)B * S, Mt = (int64_t)B * nt;
+    const float* rope = (const float*)w[13];
+    const float* c_rope = (const float*)w[14];
+    const int hd = D / heads;
+    for (int l = lo; l < hi; l++) {
+        const void* const* lw = w + VTGB_TGB_NW_GLOBAL + VTGB_TGB_NW_LAYER * l;
+        VTGB_TRY(bert_self_attention(dt, lw, 0, Ms, D, heads, B, S, b.Hb, b.qkv, b.ctx, b.self_mask, rope, s));
+        VTGB_TRY(launch_gemm(with_resid(gemm(dt, (int)Ms, D, D, VTGB_EPI_RESID_F32, b.ctx, D, lw[6], D, (const float*)lw[7], b.tmp, D), b.H, D,
+                                        rowmap_identity()), s));
+        VTGB_TRY(launch_layernorm(ln(dt, (int)Ms, D, eps, b.tmp, (const float*)lw[8], (const float*)lw[9], b.A1, b.A1b), s));
+        if (l >= fusion_layer) {   // cross attention to the question (:466-510)
+            VTGB_REQUIRE(lw[10] && lw[12] && lw[14] && lw[16], VTGB_EINVAL, "tgb: layer %d lacks cross-attention weights", l);
+            VTGB_TRY(launch_gemm(gemm(dt, (int)Ms, D, D, VTGB_EPI_STORE, b.A1b, D, lw[10], D, (const float*)lw[11], b.qkv, D), s));
+            VTGB_TRY(launch_gemm(gemm(dt, (int)Mt, D, D, VTGB_EPI_STORE, b.Tb, D, lw[12], D, (const float*)lw[13], b.kvc, 2 * D), s));
+            VTGB_TRY(launch_gemm(gemm(dt, (int)Mt, D, D, VTGB_EPI_STORE, b.Tb, D, lw[14], D, (const float*)lw[15], off(b.kvc, D, dt), 2 * D), s));
+            AttnDesc at;
+            memset(&at, 0, sizeof(at));
+            at.dtype = dt; at.batch = B; at.heads = heads; at.head_dim = hd; at.s_q = S; at.s_kv = nt;
+            at.q = b.qkv; at.q_tok = D; at.q_batch = (int64_t)S * D;
+            at.k = b.kvc; at.v = off(b.kvc, D, dt); at.kv_tok = 2 * D; at.kv_batch = (int64_t)nt * 2 * D;
+            at.key_mask = b.cross_mask; at.rope_q = rope; at.rope_k = c_rope;
+            at.scale = (float)(1.0 / sqrt((double)hd));
+            at.out = b.ctx; at.o_tok = D; at.o_batch = (int64_t)S * D;
+            VTGB_TRY(launch_attention(at, s));
+            VTGB_TRY(launch_gemm(with_resid(gemm(dt, (int)Ms, D, D, VTGB_EPI_RESID_F32, b.ctx, D, lw[16], D, (const float*)lw[17], b.tmp, D), b.A1, D,
+                                            rowmap_identity()), s));
+            VTGB_TRY(launch_layernorm(ln(dt, (int)Ms, D, eps, b.tmp, (const float*)lw[18], (const float*)lw[19], b.A1, b.A1b), s));
+        }
+        VTGB_TRY(launch_gemm(gemm(dt, (int)Ms, ffn, D, VTGB_EPI_GELU, b.A1b, D, lw[20], D, (const float*)lw[21], b.inter, ffn), s));
+        VTGB_TRY(launch_gemm(with_resid(gemm(dt, (int)Ms, D, ffn, VTGB_EPI_RESID_F32, b.inter, ffn, lw[22], ffn, (const float*)lw[23], b.tmp, D),
+                                        b.A1, D, rowmap_identity()), s));
+        VTGB_TRY(launch_layernorm(ln(dt, (int)Ms, D, eps, b.tmp, (const float*)lw[24], (const float*)lw[25], b.H, b.Hb), s));
+    }
+    return VTGB_OK;
+}
+
+// sequence output copy + mrc_head (:1164)
+static int tgb_head(const void* const* w, const float* H, float* seq_out, float* logits, int B, int L, int D, hipStream_t s) {
+    if (seq_out) VTGB_HIP(hipMemcpyAsync(seq_out, H, (int64_t)B * (L + 2) * D * 4, hipMemcpyDeviceToDevice, s));
+    return launch_mrc_head(H, (const float*)w[15], (const float*)w[16], logits, B, L, D, s);
+}
+
 static int tgb_impl(const vtgb_tgb_args* a, Workspace& ws, hipStream_t s) {
     VTGB_REQUIRE(a, VTGB_EINVAL, "tgb: NULL args");
     VTGB_REQUIRE(a->dtype == VTGB_BF16 || a->dtype == VTGB_F32, VTGB_EINVAL, "tgb: bad dtype %d", a->dtype);
@@ -416,7 +506,7 @@ static int tgb_impl(const vtgb_tgb_args* a, Workspace& ws, hipStream_t s) {
                  VTGB_EINVAL, "tgb: bad dims");
     const int dt = a->dtype;
     const size_t es = dtype_size(dt);
-    const int B = a->B, L = a->L, S = L + 2, nt = a->n_text, D = a->hidden, P = a->patch, g = a->image / P;
+    const int B = a->B, L = a->L, S = L + 2, nt = a->n_text, D = a->hidden, P = a->patch;
     const int64_t Ms = (int64_t)B * S, Mt = (int64_t)B * nt, Mf = (int64_t)B * L;
     const int kf = 2 * P * P;
     float* red = (float*)ws.take(Mf * kf * 4);
@@ -439,54 +529,15 @@ static int tgb_impl(const vtgb_tgb_args* a, Workspace& ws, hipStream_t s) {
                  "tgb: You have to specify either input_ids or inputs_embeds or encoder_embeds");
     const void* const* w = a->weights;
     for (int i = 0; i < VTGB_TGB_NW_GLOBAL; i++) VTGB_REQUIRE(w[i], VTGB_EINVAL, "tgb: weights[%d] is NULL", i);
-    // ---- TemporalOFEmbedding (xropebert.py:103-129), patch axis reduced first (elementwise.hip)
-    VTGB_TRY(launch_flow_reduce(a->of, (const float*)w[8], red, (int)Mf, a->image, P, s));
-    VTGB_TRY(launch_gemm(gemm(VTGB_F32, (int)Mf, D, kf, VTGB_EPI_STORE_F32, red, kf, w[6], kf, nullptr, conv, D), s));
-    VTGB_TRY(launch_flow_assemble(conv, (const float*)w[7], (const float*)w[8], (const float*)w[9], (const float*)w[4], (const float*)w[5],
-                                  (const float*)w[10], a->of_mask, tmp, B, L, D, g * g, s));
-    VTGB_TRY(launch_layernorm(ln(dt, (int)Ms, D, 1e-5f, tmp, (const float*)w[11], (const float*)w[12], H, Hb), s));
-    // ---- RopeBertEmbeddings on the question (:190-208)
-    VTGB_TRY(launch_tgb_text_embed(a->text_ids, (const float*)w[0], (const float*)w[1], tmp, Mt, D, s));
-    VTGB_TRY(launch_layernorm(ln(dt, (int)Mt, D, a->eps, tmp, (const float*)w[2], (const float*)w[3], nullptr, Tb), s));
+    VTGB_TRY(tgb_flow_embed(dt, w, a->of, a->of_mask, B, L, D, a->image, P, red, conv, tmp, H, Hb, s));
+    VTGB_TRY(tgb_text_embed(dt, w, a->text_ids, Mt, D, a->eps, tmp, Tb, s));
     VTGB_TRY(launch_mask_to_additive(a->of_mask, self_mask, Ms, -10000.0f, s));                 // :1044-1045
     VTGB_TRY(launch_mask_to_additive(a->text_mask, cross_mask, Mt, -3.4028234663852886e38f, s)); // :1127 invert_attention_mask
-    const float* rope = (const float*)w[13];
-    const float* c_rope = (const float*)w[14];
-    int lo = 0, hi = a->layers;                                                                  // :621-634
-    if (a->mode == VTGB_TGB_MODE_TEXT) hi = a->fusion_layer;
-    if (a->mode == VTGB_TGB_MODE_FUSION) lo = a->fusion_layer;
-    const int hd = D / a->heads;
-    for (int l = lo; l < hi; l++) {
-        const void* const* lw = w + VTGB_TGB_NW_GLOBAL + VTGB_TGB_NW_LAYER * l;
-        VTGB_TRY(bert_self_attention(dt, lw, 0, Ms, D, a->heads, B, S, Hb, qkv, ctx, self_mask, rope, s));
-        VTGB_TRY(launch_gemm(with_resid(gemm(dt, (int)Ms, D, D, VTGB_EPI_RESID_F32, ctx, D, lw[6], D, (const float*)lw[7], tmp, D), H, D,
-                                        rowmap_identity()), s));
-        VTGB_TRY(launch_layernorm(ln(dt, (int)Ms, D, a->eps, tmp, (const float*)lw[8], (const float*)lw[9], A1, A1b), s));
-        if (l >= a->fusion_layer) {   // cross attention to the question (:466-510)
-            VTGB_REQUIRE(lw[10] && lw[12] && lw[14] && lw[16], VTGB_EINVAL, "tgb: layer %d lacks cross-attention weights", l);
-            VTGB_TRY(launch_gemm(gemm(dt, (int)Ms, D, D, VTGB_EPI_STORE, A1b, D, lw[10], D, (const float*)lw[11], qkv, D), s));
-            VTGB_TRY(launch_gemm(gemm(dt, (int)Mt, D, D, VTGB_EPI_STORE, Tb, D, lw[12], D, (const float*)lw[13], kvc, 2 * D), s));
-            VTGB_TRY(launch_gemm(gemm(dt, (int)Mt, D, D, VTGB_EPI_STORE, Tb, D, lw[14], D, (const float*)lw[15], off(kvc, D, dt), 2 * D), s));
-            AttnDesc at;
-            memset(&at, 0, sizeof(at));
-            at.dtype = dt; at.batch = B; at.heads = a->heads; at.head_dim = hd; at.s_q = S; at.s_kv = nt;
-            at.q = qkv; at.q_tok = D; at.q_batch = (int64_t)S * D;
-            at.k = kvc; at.v = off(kvc, D, dt); at.kv_tok = 2 * D; at.kv_batch = (int64_t)nt * 2 * D;
-            at.key_mask = cross_mask; at.rope_q = rope; at.rope_k = c_rope;
-            at.scale = (float)(1.0 / sqrt((double)hd));
-            at.out = ctx; at.o_tok = D; at.o_batch = (int64_t)S * D;
-            VTGB_TRY(launch_attention(at, s));
-            VTGB_TRY(launch_gemm(with_resid(gemm(dt, (int)Ms, D, D, VTGB_EPI_RESID_F32, ctx, D, lw[16], D, (const float*)lw[17], tmp, D), A1, D,
-                                            rowmap_identity()), s));
-            VTGB_TRY(launch_layernorm(ln(dt, (int)Ms, D, a->eps, tmp, (const float*)lw[18], (const float*)lw[19], A1, A1b), s));
-        }
-        VTGB_TRY(launch_gemm(gemm(dt, (int)Ms, a->ffn, D, VTGB_EPI_GELU, A1b, D, lw[20], D, (const float*)lw[21], inter, a->ffn), s));
-        VTGB_TRY(launch_gemm(with_resid(gemm(dt, (int)Ms, D, a->ffn, VTGB_EPI_RESID_F32, inter, a->ffn, lw[22], a->ffn, (const float*)lw[23], tmp, D),
-                                        A1, D, rowmap_identity()), s));
-        VTGB_TRY(launch_layernorm(ln(dt, (int)Ms, D, a->eps, tmp, (const float*)lw[24], (const float*)lw[25], H, Hb), s));
-    }
-    if (a->seq_out) VTGB_HIP(hipMemcpyAsync(a->seq_out, H, Ms * D * 4, hipMemcpyDeviceToDevice, s));
-    return launch_mrc_head(H, (const float*)w[15], (const float*)w[16], a->logits, B, L, D, s);   // :1164
+    int lo, hi;
+    tgb_layer_range(a->mode, a->layers, a->fusion_layer, &lo, &hi);
+    const TgbBufs bufs = {H, Hb, tmp, Tb, qkv, ctx, A1, A1b, kvc, inter, self_mask, cross_mask};
+    VTGB_TRY(tgb_layers(dt, w, lo, hi, a->fusion_layer, B, S, nt, D, a->heads, a->ffn, a->eps, bufs, s));
+    return tgb_head(w, H, a->seq_out, a->logits, B, L, D, s);
 }
 extern "C" size_t vtgb_tgb_workspace_bytes(const vtgb_tgb_args* a) {
     Workspace ws(nullptr, 0);
@@ -497,6 +548,130 @@ extern "C" int vtgb_tgb_forward(const vtgb_tgb_args* a, vtgb_stream_t stream) {
     VTGB_REQUIRE(a && a->workspace, VTGB_EWORKSPACE, "tgb: workspace is NULL");
     Workspace ws(a->workspace, a->workspace_bytes);
     return tgb_impl(a, ws, stream);
+}
+
+// ---- split TGB: question-independent trunk on one clip, per-question resume on B rows ------------------------------------------
+// The resume's first launch: the trunk state replicated into B row blocks (H fp32, Hb as raw 32-bit words of either dtype) and the
+// clip's self mask (1 - m) * -10000 (the same expression as mask_kernel) for every block.  grid.y = row block.
+__global__ void tgb_replicate_kernel(const float* __restrict__ H, const uint32_t* __restrict__ Hb, const int64_t* __restrict__ of_mask,
+                                     float* __restrict__ H_out, uint32_t* __restrict__ Hb_out, float* __restrict__ mask_out, int64_t n_h,
+                                     int64_t n_hb, int S) {
+    const int64_t b = blockIdx.y;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_h; i += (int64_t)gridDim.x * blockDim.x) {
+        H_out[b * n_h + i] = H[i];
+        if (i < n_hb) Hb_out[b * n_hb + i] = Hb[i];
+        if (i < S) mask_out[b * S + i] = (1.0f - (float)of_mask[i]) * -10000.0f;
+    }
+}
+
+static int tgb_split_check(const vtgb_tgb_split_args* a, bool resume) {
+    VTGB_REQUIRE(a, VTGB_EINVAL, "tgb split: NULL args");
+    VTGB_REQUIRE(a->dtype == VTGB_BF16 || a->dtype == VTGB_F32, VTGB_EINVAL, "tgb split: bad dtype %d", a->dtype);
+    VTGB_REQUIRE(a->mode == VTGB_TGB_MODE_TEXT || a->mode == VTGB_TGB_MODE_FUSION || a->mode == VTGB_TGB_MODE_MULTIMODAL, VTGB_EINVAL,
+                 "INVALID MODE: %d", a->mode);
+    VTGB_REQUIRE((resume ? (a->B > 0 && a->n_text > 0) : a->B == 1) && a->L > 0 && a->hidden > 0 && a->heads > 0 && a->hidden % a->heads == 0 &&
+                     a->ffn > 0 && a->fusion_layer >= 0 && a->fusion_layer <= a->layers && a->patch > 0 && a->image % a->patch == 0,
+                 VTGB_EINVAL, "tgb %s: bad dims", resume ? "resume" : "trunk (B must be 1: one clip)");
+    return VTGB_OK;
+}
+
+static int tgb_trunk_impl(const vtgb_tgb_split_args* a, Workspace& ws, hipStream_t s) {
+    VTGB_TRY(tgb_split_check(a, false));
+    const int dt = a->dtype;
+    const size_t es = dtype_size(dt);
+    const int L = a->L, S = L + 2, D = a->hidden, P = a->patch;
+    const int kf = 2 * P * P;
+    int lo, hi;
+    tgb_layer_range(a->mode, a->layers, a->fusion_layer, &lo, &hi);
+    const int split = tgb_split_layer(a->mode, a->layers, a->fusion_layer);
+    float* red = (float*)ws.take((int64_t)L * kf * 4);
+    float* conv = (float*)ws.take((int64_t)L * D * 4);
+    float* tmp = (float*)ws.take((int64_t)S * D * 4);
+    TgbBufs b = {a->trunk, a->trunk_act, tmp, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (split > lo) {   // self-only layers of the trunk
+        b.qkv = ws.take((int64_t)S * 3 * D * es);
+        b.ctx = ws.take((int64_t)S * D * es);
+        b.A1 = (float*)ws.take((int64_t)S * D * 4);
+        b.A1b = ws.take((int64_t)S * D * es);
+        b.inter = ws.take((int64_t)S * a->ffn * es);
+        float* self_mask = (float*)ws.take((int64_t)S * 4);
+        b.self_mask = self_mask;
+    }
+    if (ws.dry) return VTGB_OK;
+    VTGB_REQUIRE(ws.ok(), VTGB_EWORKSPACE, "tgb trunk: workspace %zu < %zu bytes", ws.size, ws.used);
+    VTGB_REQUIRE(a->of && a->of_mask && a->weights && a->trunk && a->trunk_act, VTGB_EINVAL, "tgb trunk: of, of_mask, weights, trunk and trunk_act are required");
+    const void* const* w = a->weights;
+    for (int i = 0; i < VTGB_TGB_NW_GLOBAL; i++) VTGB_REQUIRE(w[i], VTGB_EINVAL, "tgb: weights[%d] is NULL", i);
+    VTGB_TRY(tgb_flow_embed(dt, w, a->of, a->of_mask, 1, L, D, a->image, P, red, conv, tmp, a->trunk, a->trunk_act, s));
+    if (split > lo) {
+        VTGB_TRY(launch_mask_to_additive(a->of_mask, (float*)b.self_mask, S, -10000.0f, s));
+        VTGB_TRY(tgb_layers(dt, w, lo, split, a->fusion_layer, 1, S, 0, D, a->heads, a->ffn, a->eps, b, s));
+    }
+    return VTGB_OK;
+}
+
+static int tgb_resume_impl(const vtgb_tgb_split_args* a, Workspace& ws, hipStream_t s) {
+    VTGB_TRY(tgb_split_check(a, true));
+    const int dt = a->dtype;
+    const size_t es = dtype_size(dt);
+    const int B = a->B, L = a->L, S = L + 2, nt = a->n_text, D = a->hidden;
+    const int64_t Ms = (int64_t)B * S, Mt = (int64_t)B * nt;
+    int lo, hi;
+    tgb_layer_range(a->mode, a->layers, a->fusion_layer, &lo, &hi);
+    const int split = tgb_split_layer(a->mode, a->layers, a->fusion_layer);
+    // the forward's buffers less the flow embedding's (red, conv)
+    float* H = (float*)ws.take(Ms * D * 4);
+    void* Hb = ws.take(Ms * D * es);
+    float* tmp = (float*)ws.take((Ms > Mt ? Ms : Mt) * D * 4);
+    void* Tb = ws.take(Mt * D * es);
+    void* qkv = ws.take(Ms * 3 * D * es);
+    void* ctx = ws.take(Ms * D * es);
+    float* A1 = (float*)ws.take(Ms * D * 4);
+    void* A1b = ws.take(Ms * D * es);
+    void* kvc = ws.take(Mt * 2 * D * es);
+    void* inter = ws.take(Ms * a->ffn * es);
+    float* self_mask = (float*)ws.take(Ms * 4);
+    float* cross_mask = (float*)ws.take(Mt * 4);
+    if (ws.dry) return VTGB_OK;
+    VTGB_REQUIRE(ws.ok(), VTGB_EWORKSPACE, "tgb resume: workspace %zu < %zu bytes", ws.size, ws.used);
+    VTGB_REQUIRE(a->of_mask && a->text_ids && a->text_mask && a->weights && a->trunk && a->trunk_act && a->logits, VTGB_EINVAL,
+                 "tgb resume: of_mask, text_ids, text_mask, weights, trunk, trunk_act and logits are required");
+    const void* const* w = a->weights;
+    for (int i = 0; i < VTGB_TGB_NW_GLOBAL; i++) VTGB_REQUIRE(w[i], VTGB_EINVAL, "tgb: weights[%d] is NULL", i);
+    {
+        const int64_t n_h = (int64_t)S * D, n_hb = n_h * (int64_t)es / 4;
+        int64_t gx = (n_h + 255) / 256;
+        if (gx > 1024) gx = 1024;
+        hipLaunchKernelGGL(tgb_replicate_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, s, a->trunk, (const uint32_t*)a->trunk_act,
+                           a->of_mask, H, (uint32_t*)Hb, self_mask, n_h, n_hb, S);
+        VTGB_HIP(hipGetLastError());
+    }
+    VTGB_TRY(tgb_text_embed(dt, w, a->text_ids, Mt, D, a->eps, tmp, Tb, s));
+    VTGB_TRY(launch_mask_to_additive(a->text_mask, cross_mask, Mt, -3.4028234663852886e38f, s)); // :1127 invert_attention_mask
+    const TgbBufs bufs = {H, Hb, tmp, Tb, qkv, ctx, A1, A1b, kvc, inter, self_mask, cross_mask};
+    VTGB_TRY(tgb_layers(dt, w, split, hi, a->fusion_layer, B, S, nt, D, a->heads, a->ffn, a->eps, bufs, s));
+    return tgb_head(w, H, a->seq_out, a->logits, B, L, D, s);
+}
+
+extern "C" size_t vtgb_tgb_trunk_workspace_bytes(const vtgb_tgb_split_args* a) {
+    Workspace ws(nullptr, 0);
+    if (tgb_trunk_impl(a, ws, nullptr) != VTGB_OK) return 0;
+    return align_up(ws.used, 256);
+}
+extern "C" int vtgb_tgb_trunk(const vtgb_tgb_split_args* a, vtgb_stream_t stream) {
+    VTGB_REQUIRE(a && a->workspace, VTGB_EWORKSPACE, "tgb trunk: workspace is NULL");
+    Workspace ws(a->workspace, a->workspace_bytes);
+    return tgb_trunk_impl(a, ws, stream);
+}
+extern "C" size_t vtgb_tgb_resume_workspace_bytes(const vtgb_tgb_split_args* a) {
+    Workspace ws(nullptr, 0);
+    if (tgb_resume_impl(a, ws, nullptr) != VTGB_OK) return 0;
+    return align_up(ws.used, 256);
+}
+extern "C" int vtgb_tgb_resume(const vtgb_tgb_split_args* a, vtgb_stream_t stream) {
+    VTGB_REQUIRE(a && a->workspace, VTGB_EWORKSPACE, "tgb resume: workspace is NULL");
+    Workspace ws(a->workspace, a->workspace_bytes);
+    return tgb_resume_impl(a, ws, stream);
 }
 
 // =======================================================================================

@@ -531,6 +531,74 @@ def tgb_forward(w: TgbWeights, of: Tensor, of_mask: Tensor, text_ids: Tensor, te
     return seq, logits
 
 
+class TgbTrunk:
+    """One clip's question-independent TGB state (vtgb_tgb_trunk): the residual stream after the layers before the first cross-attention
+    layer, fp32 ``H`` and its compute-dtype copy ``Hb`` [L+2, hidden]; ``of_mask`` [1, L+2] the clip's flow mask; ``mode`` / ``code`` the
+    TGB mode and compute dtype it was built at (tgb_resume checks both)."""
+
+    def __init__(self, H: Tensor, Hb: Tensor, of_mask: Tensor, mode: str, code: int):
+        self.H, self.Hb, self.of_mask, self.mode, self.code = H, Hb, of_mask, mode, code
+
+    @property
+    def L(self) -> int:
+        return self.H.shape[0] - 2
+
+
+def _tgb_split_args(w: TgbWeights, B: int, Lf: int, n_text: int, mode: str) -> "L.TgbSplitArgs":
+    return L.TgbSplitArgs(w.code, B, Lf, n_text, w.hidden, w.heads, w.ffn, w.layers, w.fusion_layer, L.TGB_MODE[mode], w.image, w.patch,
+                          float(w.eps), None, None, None, None, C.cast(w.array, C.POINTER(C.c_void_p)), None, None, None, None, None, 0)
+
+
+def tgb_trunk(w: TgbWeights, of: Tensor, of_mask: Tensor, mode: str) -> TgbTrunk:
+    """of [1, L, 2, image, image] fp32 (one clip), of_mask [1, L+2] -> the clip's TgbTrunk (vtgb_tgb_trunk)."""
+    if mode not in L.TGB_MODE:
+        raise ValueError(f"INVALID MODE: {mode}")
+    _need_cuda(of, of_mask)
+    of = of.contiguous().float()
+    if of.dim() != 5 or of.shape[0] != 1:
+        raise ValueError(f"tgb_trunk: flow {tuple(of.shape)} is not one clip [1, L, 2, image, image]")
+    Lf = of.shape[1]
+    if tuple(of.shape[2:]) != (2, w.image, w.image):
+        raise ValueError(f"tgb: flow {tuple(of.shape)} does not match image size {w.image}")
+    if Lf + 2 > w.max_pos:
+        raise ValueError(f"tgb: {Lf} flow frames exceed the {w.max_pos} position table")
+    of_mask = of_mask.contiguous().to(torch.int64)
+    if tuple(of_mask.shape) != (1, Lf + 2):
+        raise ValueError(f"tgb_trunk: of_mask {tuple(of_mask.shape)} != (1, {Lf + 2})")
+    H = torch.empty(Lf + 2, w.hidden, dtype=torch.float32, device=of.device)
+    Hb = torch.empty(Lf + 2, w.hidden, dtype=act_dtype(w.code), device=of.device)
+    a = _tgb_split_args(w, 1, Lf, 0, mode)
+    a.of, a.of_mask, a.trunk, a.trunk_act = of.data_ptr(), of_mask.data_ptr(), H.data_ptr(), Hb.data_ptr()
+    need = L.lib().vtgb_tgb_trunk_workspace_bytes(C.byref(a))
+    ws = _ws.get(need, of.device)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    L.check(L.lib().vtgb_tgb_trunk(C.byref(a), _stream()))
+    return TgbTrunk(H, Hb, of_mask, mode, w.code)
+
+
+def tgb_resume(w: TgbWeights, trunk: TgbTrunk, text_ids: Tensor, text_mask: Tensor):
+    """B question rows against one clip's trunk (vtgb_tgb_resume) -> (sequence_output [B, L+2, hidden], logits [B, L, 2]) fp32, equal bit for
+    bit to tgb_forward on the clip repeated B times."""
+    if trunk.code != w.code:
+        raise ValueError(f"tgb_resume: trunk built at compute dtype {trunk.code}, weights at {w.code}")
+    _need_cuda(text_ids, text_mask)
+    text_ids = text_ids.contiguous().to(torch.int64)
+    text_mask = text_mask.contiguous().to(torch.int64)
+    if text_ids.dim() != 2 or tuple(text_mask.shape) != tuple(text_ids.shape):
+        raise ValueError(f"tgb_resume: text_ids {tuple(text_ids.shape)} / text_mask {tuple(text_mask.shape)} mismatch")
+    B, Lf = text_ids.shape[0], trunk.L
+    seq = torch.empty(B, Lf + 2, w.hidden, dtype=torch.float32, device=text_ids.device)
+    logits = torch.empty(B, Lf, 2, dtype=torch.float32, device=text_ids.device)
+    a = _tgb_split_args(w, B, Lf, text_ids.shape[1], trunk.mode)
+    a.of_mask, a.text_ids, a.text_mask = trunk.of_mask.data_ptr(), text_ids.data_ptr(), text_mask.data_ptr()
+    a.trunk, a.trunk_act, a.seq_out, a.logits = trunk.H.data_ptr(), trunk.Hb.data_ptr(), seq.data_ptr(), logits.data_ptr()
+    need = L.lib().vtgb_tgb_resume_workspace_bytes(C.byref(a))
+    ws = _ws.get(need, text_ids.device)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    L.check(L.lib().vtgb_tgb_resume(C.byref(a), _stream()))
+    return seq, logits
+
+
 # ----------------------------------------------------------------------------- RAFT (a2 / f1)
 def conv_k_order(w: Tensor) -> Tensor:
     """[co, kh, kw, ci] (ci % 64 == 0) -> [co, K] in the implicit-GEMM kernels' K order: 64-channel chunk major,
