@@ -589,6 +589,36 @@ int vtgb_llm_rmsnorm_parts(int dtype, void* x, const float* part, int32_t n_spli
                            vtgb_stream_t stream);
 int vtgb_llm_rope_cache_parts(int dtype, const float* part, int32_t n_splits, void* q_out, void* kc, void* vc, const void* cos_t, const void* sin_t,
                               const int64_t* pos, int32_t B, int32_t nq, int32_t nkv, int32_t hd, int32_t tmax, vtgb_stream_t stream);
+
+/* ---- Padded prompt batches on the graph decoders (HF generate with an attention mask; transformers'
+ * GenerationMixin._prepare_position_ids_for_generation / _update_model_kwargs_for_generation, modeling_t5's extended mask).
+ * New entries next to the unpadded ones, which are unchanged; all per-row data is DEVICE memory, so one captured graph serves
+ * every ragged batch of one shape.
+ *   vtgb_llm_rope_cache_pos / _parts_pos: vtgb_llm_rope_cache / _parts with the rotary row of batch entry b = *pos + rope_off[b]
+ *     (rope_off [B] int64; HF: position_ids[b, P-1] + step); the cache row stays *pos.  rope_off == 0: the same values bit for bit.
+ *   vtgb_llm_rope_cache_prefill_pos: vtgb_llm_rope_cache_prefill with the rotary row of (b, s) = pos_ids[b, s] (pos_ids [B, S] int64;
+ *     HF: attention_mask.cumsum(-1) - 1, pads at 0).  Rows are clamped to [0, tmax).
+ *   vtgb_llm_decode_attention_masked: vtgb_llm_decode_attention over the keys [0, *pos] with key_valid[b, key] != 0 (key_valid
+ *     [B, tmax] uint8).  Masked keys get no weight and neither their K nor their V row is read (a pad slot may hold anything,
+ *     NaN included); the valid keys are summed in the unmasked order.  No valid key: the output row is 0.
+ *   vtgb_llm_attention_rows_masked: vtgb_llm_attention_rows with key_valid[(r / rows_per_batch) * key_valid_batch_stride + key]
+ *     (uint8) -- the T5 encoder's self-attention and the decoder's cross-attention over a padded encoder input.
+ * The prefill's attention is vtgb_attention with key_mask = finfo(float32).min on pad keys and causal = 1 (finite rows also
+ * where a query has no valid key). */
+int vtgb_llm_rope_cache_pos(int dtype, const void* qkv, void* q_out, void* kc, void* vc, const void* cos_t, const void* sin_t,
+                            const int64_t* pos, const int64_t* rope_off, int32_t B, int32_t nq, int32_t nkv, int32_t hd, int32_t tmax,
+                            vtgb_stream_t stream);
+int vtgb_llm_rope_cache_parts_pos(int dtype, const float* part, int32_t n_splits, void* q_out, void* kc, void* vc, const void* cos_t,
+                                  const void* sin_t, const int64_t* pos, const int64_t* rope_off, int32_t B, int32_t nq, int32_t nkv, int32_t hd,
+                                  int32_t tmax, vtgb_stream_t stream);
+int vtgb_llm_rope_cache_prefill_pos(int dtype, void* qkv, void* kc, void* vc, const void* cos_t, const void* sin_t, const int64_t* pos_ids,
+                                    int32_t B, int32_t S, int32_t nq, int32_t nkv, int32_t hd, int32_t tmax, vtgb_stream_t stream);
+int vtgb_llm_decode_attention_masked(int dtype, const void* q, const void* kc, const void* vc, void* out, const int64_t* pos,
+                                     const uint8_t* key_valid, int32_t B, int32_t nq, int32_t nkv, int32_t hd, int32_t tmax, float scale,
+                                     vtgb_stream_t stream);
+int vtgb_llm_attention_rows_masked(const vtgb_llm_attn_rows_args* a, const uint8_t* key_valid, int64_t key_valid_batch_stride,
+                                   vtgb_stream_t stream);
+
 size_t vtgb_pack_skinny_weight_bytes(int32_t N, int32_t K);
 int vtgb_pack_skinny_weight(const void* w, int64_t ldw, int32_t N, int32_t K, void* dst, vtgb_stream_t stream);
 size_t vtgb_gemm_skinny_workspace_bytes(const vtgb_gemm_skinny_args* a);

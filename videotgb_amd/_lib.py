@@ -32,6 +32,8 @@ EXPORTS = [
     "vtgb_layernorm", "vtgb_prof_enable", "vtgb_prof_reset", "vtgb_prof_summary", "vtgb_prof_executed_flops",
     "vtgb_llm_rmsnorm", "vtgb_llm_rope_cache", "vtgb_llm_rope_cache_prefill", "vtgb_llm_decode_attention", "vtgb_llm_silu_mul",
     "vtgb_llm_attention_rows", "vtgb_llm_gated_act", "vtgb_llm_rmsnorm_parts", "vtgb_llm_rope_cache_parts", "vtgb_gemm_skinny_splits",
+    "vtgb_llm_rope_cache_pos", "vtgb_llm_rope_cache_parts_pos", "vtgb_llm_rope_cache_prefill_pos", "vtgb_llm_decode_attention_masked",
+    "vtgb_llm_attention_rows_masked",
     "vtgb_gemm_skinny_workspace_bytes", "vtgb_gemm_skinny", "vtgb_pack_skinny_weight_bytes", "vtgb_pack_skinny_weight",
     "vtgb_raft_update_workspace_bytes", "vtgb_raft_update", "vtgb_raft_encoder_workspace_bytes", "vtgb_raft_encoder",
     "vtgb_raft_corr_workspace_bytes", "vtgb_raft_corr", "vtgb_preprocess_frames", "vtgb_concat_text_io", "vtgb_shifted_ce_forward", "vtgb_shifted_ce_backward",
@@ -248,6 +250,14 @@ def lib() -> C.CDLL:
     L.vtgb_llm_rmsnorm_parts.restype = C.c_int
     L.vtgb_llm_rope_cache_parts.argtypes = [C.c_int, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     L.vtgb_llm_rope_cache_parts.restype = C.c_int
+    L.vtgb_llm_rope_cache_pos.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    L.vtgb_llm_rope_cache_parts_pos.argtypes = [C.c_int, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    L.vtgb_llm_rope_cache_prefill_pos.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    L.vtgb_llm_decode_attention_masked.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]
+    L.vtgb_llm_attention_rows_masked.argtypes = [C.POINTER(LlmAttnRowsArgs), vp, i64, vp]
+    for fn in (L.vtgb_llm_rope_cache_pos, L.vtgb_llm_rope_cache_parts_pos, L.vtgb_llm_rope_cache_prefill_pos, L.vtgb_llm_decode_attention_masked,
+               L.vtgb_llm_attention_rows_masked):
+        fn.restype = C.c_int
     L.vtgb_gemm_skinny_splits.argtypes = [C.POINTER(GemmSkinnyArgs)]
     L.vtgb_gemm_skinny_splits.restype = i32
     L.vtgb_gemm_skinny.argtypes = [C.POINTER(GemmSkinnyArgs), vp]

@@ -137,14 +137,20 @@ __global__ __launch_bounds__(256) void llm_rmsnorm_vec_kernel(T* __restrict__ x,
 }
 
 // ---- rotary on q and k at position *pos, k and v appended to the cache.  One workgroup per (batch, head).
-template <typename T>
-__global__ __launch_bounds__(128) void llm_rope_cache_kernel(const T* __restrict__ qkv, T* __restrict__ q_out, T* __restrict__ kc,
-                                                             T* __restrict__ vc, const T* __restrict__ cos_t, const T* __restrict__ sin_t,
-                                                             const int64_t* __restrict__ pos_p, int nq, int nkv, int hd, int tmax,
-                                                             const float* __restrict__ part = nullptr, int S = 0, int M = 0) {
+// ROW_OFF (padded batches): the rotary row of batch entry b is *pos + rope_off[b] (HF's per-row position ids), the cache row stays *pos.
+template <typename T, bool ROW_OFF>
+__device__ __forceinline__ void rope_cache_body(const T* __restrict__ qkv, T* __restrict__ q_out, T* __restrict__ kc, T* __restrict__ vc,
+                                                const T* __restrict__ cos_t, const T* __restrict__ sin_t, const int64_t* __restrict__ pos_p,
+                                                const int64_t* __restrict__ rope_off, int nq, int nkv, int hd, int tmax, const float* __restrict__ part,
+                                                int S, int M) {
 #pragma clang fp contract(off)      // fp32: mul, mul, add are three roundings in the reference -- no FMA
     const int b = blockIdx.y, head = blockIdx.x;   // head in [0, nq + 2 nkv)
     const int64_t pos = *pos_p;
+    int64_t rp = pos;
+    if constexpr (ROW_OFF) {
+        rp += rope_off[b];
+        rp = rp < 0 ? 0 : rp >= tmax ? tmax - 1 : rp;      // (the tables have tmax rows; the decoder's offsets keep rp in [0, pos])
+    }
     const T* src = qkv + ((int64_t)b * (nq + 2 * nkv) + head) * hd;
     const int half = hd >> 1;
     // part != NULL: qkv is still the projection's K-split fragments -- element (b, col) = the fragments' sum in split order, rounded once
@@ -159,7 +165,7 @@ __global__ __launch_bounds__(128) void llm_rope_cache_kernel(const T* __restrict
         const float v = at(d);
         float outv = v;
         if (head < nq + nkv && cos_t) {      // (cos_t == NULL: no rotary -- T5's decoder: q passed through, k / v appended)
-            const float c = (float)cos_t[pos * hd + d], sn = (float)sin_t[pos * hd + d];
+            const float c = (float)cos_t[rp * hd + d], sn = (float)sin_t[rp * hd + d];
             const float rot = d < half ? -at(d + half) : at(d - half);
             const float pa = Cvt<T>::rnd(v * c), pb = Cvt<T>::rnd(rot * sn);      // (contract(off): the reference's three roundings, no FMA)
             outv = Cvt<T>::rnd(pa + pb);
@@ -170,12 +176,31 @@ __global__ __launch_bounds__(128) void llm_rope_cache_kernel(const T* __restrict
     }
 }
 
-// ---- single-query attention over the cache rows [0, *pos].  One wave per (batch, q head), 4 per workgroup.
-constexpr int DEC_MAX_T = 2048;
 template <typename T>
-__global__ __launch_bounds__(256) void llm_decode_attn_kernel(const T* __restrict__ q, const T* __restrict__ kc, const T* __restrict__ vc,
-                                                              T* __restrict__ out, const int64_t* __restrict__ pos_p, int B, int nq, int nkv,
-                                                              int hd, int tmax, float scale) {
+__global__ __launch_bounds__(128) void llm_rope_cache_kernel(const T* __restrict__ qkv, T* __restrict__ q_out, T* __restrict__ kc,
+                                                             T* __restrict__ vc, const T* __restrict__ cos_t, const T* __restrict__ sin_t,
+                                                             const int64_t* __restrict__ pos_p, int nq, int nkv, int hd, int tmax,
+                                                             const float* __restrict__ part = nullptr, int S = 0, int M = 0) {
+    rope_cache_body<T, false>(qkv, q_out, kc, vc, cos_t, sin_t, pos_p, nullptr, nq, nkv, hd, tmax, part, S, M);
+}
+
+template <typename T>
+__global__ __launch_bounds__(128) void llm_rope_cache_pos_kernel(const T* __restrict__ qkv, T* __restrict__ q_out, T* __restrict__ kc,
+                                                                 T* __restrict__ vc, const T* __restrict__ cos_t, const T* __restrict__ sin_t,
+                                                                 const int64_t* __restrict__ pos_p, const int64_t* __restrict__ rope_off, int nq,
+                                                                 int nkv, int hd, int tmax, const float* __restrict__ part = nullptr, int S = 0,
+                                                                 int M = 0) {
+    rope_cache_body<T, true>(qkv, q_out, kc, vc, cos_t, sin_t, pos_p, rope_off, nq, nkv, hd, tmax, part, S, M);
+}
+
+// ---- single-query attention over the cache rows [0, *pos].  One wave per (batch, q head), 4 per workgroup.
+// MASKED (padded batches): key_valid[b, key] == 0 keys get no weight; neither their K nor their V rows are read, so whatever a pad slot of
+// the cache holds (NaN included) cannot reach the output.  The valid keys are summed in the same order as unmasked.
+constexpr int DEC_MAX_T = 2048;
+template <typename T, bool MASKED>
+__device__ __forceinline__ void decode_attn_body(const T* __restrict__ q, const T* __restrict__ kc, const T* __restrict__ vc, T* __restrict__ out,
+                                                 const int64_t* __restrict__ pos_p, const uint8_t* __restrict__ key_valid, int B, int nq, int nkv, int hd,
+                                                 int tmax, float scale) {
     extern __shared__ float dsm[];   // per wave: hd floats of q + (tmax) scores
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (uniform: batch / head / cache bases on the scalar unit)
     const int64_t idx = (int64_t)blockIdx.x * 4 + wave;
@@ -191,7 +216,14 @@ __global__ __launch_bounds__(256) void llm_decode_attn_kernel(const T* __restric
     for (int d = lane; d < hd; d += 64) qs[d] = (float)qr[d];
     __syncthreads();
     float mx = -INFINITY;
+    const uint8_t* kvr = MASKED ? key_valid + (int64_t)b * tmax : nullptr;
     for (int key = lane; key < n_keys; key += 64) {
+        if constexpr (MASKED) {
+            if (!kvr[key]) {
+                sc[key] = -INFINITY;
+                continue;
+            }
+        }
         const T* k = kr + (int64_t)key * hd;
         float dot = 0.f;
         if constexpr (sizeof(T) == 2) {
@@ -215,13 +247,23 @@ __global__ __launch_bounds__(256) void llm_decode_attn_kernel(const T* __restric
     for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
     float sum = 0.f;
     for (int key = lane; key < n_keys; key += 64) {
-        const float e = expf(sc[key] - mx);
+        const float e = MASKED && sc[key] == -INFINITY ? 0.f : expf(sc[key] - mx);      // (masked: exactly 0, also when every key is masked)
         sc[key] = e;
         sum += e;
     }
     for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
     __syncthreads();
-    const float inv = 1.0f / sum;
+    const float inv = MASKED && sum == 0.f ? 0.f : 1.0f / sum;
+    // MASKED: a key of zero weight (masked; or valid with an underflowed weight, which adds nothing either way) contributes an exact 0.  No
+    // branch: its load is redirected to row *pos (always in bounds, a cache hit) and the value selected away, so every load of the
+    // sixteen-key group is issued before the first wait and a pad slot's contents (NaN included) never reach a product.
+    const int last = n_keys - 1;
+    auto vrow = [&](int key) { return MASKED && sc[key] == 0.f ? last : key; };
+    auto vload2 = [&](int key, int d) {
+        typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+        const bf16x2_t v = *reinterpret_cast<const bf16x2_t*>(vr + (int64_t)vrow(key) * hd + d);
+        return MASKED && sc[key] == 0.f ? bf16x2_t{(bf16_t)0.f, (bf16_t)0.f} : v;
+    };
     if constexpr (sizeof(T) == 2) {
         if ((hd & 1) == 0) {
             // a lane owns two adjacent channels: one 4-byte load per key (a key row = one coalesced 2 hd-byte read), sixteen keys in flight
@@ -233,19 +275,19 @@ __global__ __launch_bounds__(256) void llm_decode_attn_kernel(const T* __restric
                 for (; key + 16 <= n_keys; key += 16) {
                     bf16x2_t v[16];
 #pragma unroll
-                    for (int u = 0; u < 16; u++) v[u] = *reinterpret_cast<const bf16x2_t*>(vr + (int64_t)(key + u) * hd + d);
+                    for (int u = 0; u < 16; u++) v[u] = vload2(key + u, d);
 #pragma unroll
                     for (int u = 0; u < 16; u++) { a0 = fmaf(sc[key + u], (float)v[u][0], a0); a1 = fmaf(sc[key + u], (float)v[u][1], a1); }
                 }
                 for (; key + 4 <= n_keys; key += 4) {
                     bf16x2_t v[4];
 #pragma unroll
-                    for (int u = 0; u < 4; u++) v[u] = *reinterpret_cast<const bf16x2_t*>(vr + (int64_t)(key + u) * hd + d);
+                    for (int u = 0; u < 4; u++) v[u] = vload2(key + u, d);
 #pragma unroll
                     for (int u = 0; u < 4; u++) { a0 = fmaf(sc[key + u], (float)v[u][0], a0); a1 = fmaf(sc[key + u], (float)v[u][1], a1); }
                 }
                 for (; key < n_keys; key++) {
-                    const bf16x2_t v = *reinterpret_cast<const bf16x2_t*>(vr + (int64_t)key * hd + d);
+                    const bf16x2_t v = vload2(key, d);
                     a0 = fmaf(sc[key], (float)v[0], a0); a1 = fmaf(sc[key], (float)v[1], a1);
                 }
                 if (active) *reinterpret_cast<bf16x2_t*>(out + ((int64_t)b * nq + head) * hd + d) = bf16x2_t{(bf16_t)(a0 * inv), (bf16_t)(a1 * inv)};
@@ -255,9 +297,27 @@ __global__ __launch_bounds__(256) void llm_decode_attn_kernel(const T* __restric
     }
     for (int d = lane; d < hd; d += 64) {
         float acc = 0.f;
-        for (int key = 0; key < n_keys; key++) acc = fmaf(sc[key], (float)vr[(int64_t)key * hd + d], acc);
+        for (int key = 0; key < n_keys; key++) {
+            const float v = (float)vr[(int64_t)vrow(key) * hd + d];
+            acc = fmaf(sc[key], MASKED && sc[key] == 0.f ? 0.f : v, acc);
+        }
         if (active) out[((int64_t)b * nq + head) * hd + d] = Cvt<T>::to(acc * inv);
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void llm_decode_attn_kernel(const T* __restrict__ q, const T* __restrict__ kc, const T* __restrict__ vc,
+                                                              T* __restrict__ out, const int64_t* __restrict__ pos_p, int B, int nq, int nkv,
+                                                              int hd, int tmax, float scale) {
+    decode_attn_body<T, false>(q, kc, vc, out, pos_p, nullptr, B, nq, nkv, hd, tmax, scale);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void llm_decode_attn_masked_kernel(const T* __restrict__ q, const T* __restrict__ kc, const T* __restrict__ vc,
+                                                                     T* __restrict__ out, const int64_t* __restrict__ pos_p,
+                                                                     const uint8_t* __restrict__ key_valid, int B, int nq, int nkv, int hd, int tmax,
+                                                                     float scale) {
+    decode_attn_body<T, true>(q, kc, vc, out, pos_p, key_valid, B, nq, nkv, hd, tmax, scale);
 }
 
 // ---- act[b, i] = silu(gu[b, i]) * gu[b, I + i]
@@ -337,20 +397,39 @@ extern "C" int vtgb_llm_rope_cache_parts(int dtype, const float* part, int32_t S
     return VTGB_OK;
 }
 
+extern "C" int vtgb_llm_rope_cache_parts_pos(int dtype, const float* part, int32_t S, void* q_out, void* kc, void* vc, const void* cos_t, const void* sin_t,
+                                             const int64_t* pos, const int64_t* rope_off, int32_t B, int32_t nq, int32_t nkv, int32_t hd, int32_t tmax,
+                                             vtgb_stream_t s) {
+    VTGB_REQUIRE(part && S > 1 && q_out && kc && vc && cos_t && sin_t && pos && rope_off && B > 0 && B <= 128 && nq > 0 && nkv > 0 && (hd % 2) == 0 &&
+                     tmax > 0 && dtype == VTGB_BF16,
+                 VTGB_EINVAL, "llm_rope_cache_parts_pos: bad argument");
+    hipLaunchKernelGGL(llm_rope_cache_pos_kernel<bf16_t>, dim3(nq + 2 * nkv, B), dim3(128), 0, s, (const bf16_t*)nullptr, (bf16_t*)q_out, (bf16_t*)kc, (bf16_t*)vc,
+                       (const bf16_t*)cos_t, (const bf16_t*)sin_t, pos, rope_off, nq, nkv, hd, tmax, part, S, B);
+    VTGB_HIP(hipGetLastError());
+    return VTGB_OK;
+}
+
 // ---- the prefill's counterpart: rotary on q and k of EVERY position, in place in qkv [B, S, (nq + 2 nkv) * hd] (the attention then reads q
 // and k from there), k and v copied to the cache rows 0 .. S - 1.  One workgroup per (position, batch); bf16: a thread takes 8 channels of
 // the first half of a head together with their partners in the second half (16-byte loads and stores); HF's roundings (each product, then
 // the sum: LlamaRotaryEmbedding / apply_rotary_pos_emb in the model's dtype).
-template <typename T>
-__global__ __launch_bounds__(256) void llm_rope_cache_prefill_kernel(T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc, const T* __restrict__ cos_t,
-                                                                     const T* __restrict__ sin_t, int S, int nq, int nkv, int hd, int tmax) {
+// pos_ids != NULL (padded batches): the rotary row of (b, spos) is pos_ids[b, spos] (HF: attention_mask.cumsum(-1) - 1, pads at 0).
+template <typename T, bool POS_IDS>
+__device__ __forceinline__ void rope_cache_prefill_body(T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc, const T* __restrict__ cos_t,
+                                                        const T* __restrict__ sin_t, const int64_t* __restrict__ pos_ids, int S, int nq, int nkv, int hd,
+                                                        int tmax) {
 #pragma clang fp contract(off)      // fp32: mul, mul, add are three roundings in the reference -- no FMA
     constexpr int V = 16 / (int)sizeof(T);                     // elements per 16-byte vector
     typedef T TV __attribute__((ext_vector_type(V)));
     const int spos = blockIdx.x, b = blockIdx.y, half = hd >> 1, cph = half / V;      // vectors per half head
     T* const row = qkv + ((int64_t)b * S + spos) * (nq + 2 * nkv) * hd;
-    const T* const cr = cos_t + (int64_t)spos * hd;
-    const T* const sr = sin_t + (int64_t)spos * hd;
+    int64_t rp = spos;
+    if constexpr (POS_IDS) {
+        rp = pos_ids[(int64_t)b * S + spos];
+        rp = rp < 0 ? 0 : rp >= tmax ? tmax - 1 : rp;
+    }
+    const T* const cr = cos_t + rp * hd;
+    const T* const sr = sin_t + rp * hd;
     for (int it = threadIdx.x; it < (nq + nkv) * cph; it += blockDim.x) {
         const int head = it / cph, d = (it - head * cph) * V;
         T* const hp = row + head * hd;
@@ -380,6 +459,19 @@ __global__ __launch_bounds__(256) void llm_rope_cache_prefill_kernel(T* __restri
     }
 }
 
+template <typename T>
+__global__ __launch_bounds__(256) void llm_rope_cache_prefill_kernel(T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc, const T* __restrict__ cos_t,
+                                                                     const T* __restrict__ sin_t, int S, int nq, int nkv, int hd, int tmax) {
+    rope_cache_prefill_body<T, false>(qkv, kc, vc, cos_t, sin_t, nullptr, S, nq, nkv, hd, tmax);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void llm_rope_cache_prefill_pos_kernel(T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc, const T* __restrict__ cos_t,
+                                                                         const T* __restrict__ sin_t, const int64_t* __restrict__ pos_ids, int S, int nq, int nkv,
+                                                                         int hd, int tmax) {
+    rope_cache_prefill_body<T, true>(qkv, kc, vc, cos_t, sin_t, pos_ids, S, nq, nkv, hd, tmax);
+}
+
 extern "C" int vtgb_llm_rope_cache(int dtype, const void* qkv, void* q_out, void* kc, void* vc, const void* cos_t, const void* sin_t,
                                    const int64_t* pos, int32_t B, int32_t nq, int32_t nkv, int32_t hd, int32_t tmax, vtgb_stream_t s) {
     VTGB_REQUIRE(qkv && q_out && kc && vc && ((cos_t == nullptr) == (sin_t == nullptr)) && pos && B > 0 && nq > 0 && nkv > 0 && (hd % 2) == 0, VTGB_EINVAL, "llm_rope_cache: bad argument");
@@ -390,6 +482,22 @@ extern "C" int vtgb_llm_rope_cache(int dtype, const void* qkv, void* q_out, void
     else
         hipLaunchKernelGGL(llm_rope_cache_kernel<float>, grid, dim3(128), 0, s, (const float*)qkv, (float*)q_out, (float*)kc, (float*)vc,
                            (const float*)cos_t, (const float*)sin_t, pos, nq, nkv, hd, tmax);
+    VTGB_HIP(hipGetLastError());
+    return VTGB_OK;
+}
+
+extern "C" int vtgb_llm_rope_cache_pos(int dtype, const void* qkv, void* q_out, void* kc, void* vc, const void* cos_t, const void* sin_t,
+                                       const int64_t* pos, const int64_t* rope_off, int32_t B, int32_t nq, int32_t nkv, int32_t hd, int32_t tmax,
+                                       vtgb_stream_t s) {
+    VTGB_REQUIRE(qkv && q_out && kc && vc && cos_t && sin_t && pos && rope_off && B > 0 && nq > 0 && nkv > 0 && (hd % 2) == 0 && tmax > 0, VTGB_EINVAL,
+                 "llm_rope_cache_pos: bad argument");
+    const dim3 grid(nq + 2 * nkv, B);
+    if (dtype == VTGB_BF16)
+        hipLaunchKernelGGL(llm_rope_cache_pos_kernel<bf16_t>, grid, dim3(128), 0, s, (const bf16_t*)qkv, (bf16_t*)q_out, (bf16_t*)kc, (bf16_t*)vc,
+                           (const bf16_t*)cos_t, (const bf16_t*)sin_t, pos, rope_off, nq, nkv, hd, tmax);
+    else
+        hipLaunchKernelGGL(llm_rope_cache_pos_kernel<float>, grid, dim3(128), 0, s, (const float*)qkv, (float*)q_out, (float*)kc, (float*)vc,
+                           (const float*)cos_t, (const float*)sin_t, pos, rope_off, nq, nkv, hd, tmax);
     VTGB_HIP(hipGetLastError());
     return VTGB_OK;
 }
@@ -409,6 +517,22 @@ extern "C" int vtgb_llm_rope_cache_prefill(int dtype, void* qkv, void* kc, void*
     return VTGB_OK;
 }
 
+extern "C" int vtgb_llm_rope_cache_prefill_pos(int dtype, void* qkv, void* kc, void* vc, const void* cos_t, const void* sin_t, const int64_t* pos_ids,
+                                               int32_t B, int32_t S, int32_t nq, int32_t nkv, int32_t hd, int32_t tmax, vtgb_stream_t s) {
+    VTGB_REQUIRE(qkv && kc && vc && cos_t && sin_t && pos_ids && B > 0 && S > 0 && S <= tmax && nq > 0 && nkv > 0, VTGB_EINVAL,
+                 "llm_rope_cache_prefill_pos: bad argument");
+    VTGB_REQUIRE(dtype == VTGB_BF16 ? (hd % 16) == 0 : (hd % 8) == 0, VTGB_EUNSUPPORTED, "llm_rope_cache_prefill_pos: head_dim=%d (16-byte vectors per half head)", hd);
+    const dim3 grid(S, B);
+    if (dtype == VTGB_BF16)
+        hipLaunchKernelGGL(llm_rope_cache_prefill_pos_kernel<bf16_t>, grid, dim3(256), 0, s, (bf16_t*)qkv, (bf16_t*)kc, (bf16_t*)vc, (const bf16_t*)cos_t,
+                           (const bf16_t*)sin_t, pos_ids, S, nq, nkv, hd, tmax);
+    else
+        hipLaunchKernelGGL(llm_rope_cache_prefill_pos_kernel<float>, grid, dim3(256), 0, s, (float*)qkv, (float*)kc, (float*)vc, (const float*)cos_t,
+                           (const float*)sin_t, pos_ids, S, nq, nkv, hd, tmax);
+    VTGB_HIP(hipGetLastError());
+    return VTGB_OK;
+}
+
 extern "C" int vtgb_llm_decode_attention(int dtype, const void* q, const void* kc, const void* vc, void* out, const int64_t* pos, int32_t B,
                                          int32_t nq, int32_t nkv, int32_t hd, int32_t tmax, float scale, vtgb_stream_t s) {
     VTGB_REQUIRE(q && kc && vc && out && pos && B > 0 && nq > 0 && nkv > 0 && nq % nkv == 0, VTGB_EINVAL, "llm_decode_attention: bad argument");
@@ -421,6 +545,24 @@ extern "C" int vtgb_llm_decode_attention(int dtype, const void* q, const void* k
     else
         hipLaunchKernelGGL(llm_decode_attn_kernel<float>, grid, dim3(256), lds, s, (const float*)q, (const float*)kc, (const float*)vc, (float*)out, pos,
                            B, nq, nkv, hd, tmax, scale);
+    VTGB_HIP(hipGetLastError());
+    return VTGB_OK;
+}
+
+extern "C" int vtgb_llm_decode_attention_masked(int dtype, const void* q, const void* kc, const void* vc, void* out, const int64_t* pos,
+                                                const uint8_t* key_valid, int32_t B, int32_t nq, int32_t nkv, int32_t hd, int32_t tmax, float scale,
+                                                vtgb_stream_t s) {
+    VTGB_REQUIRE(q && kc && vc && out && pos && key_valid && B > 0 && nq > 0 && nkv > 0 && nq % nkv == 0 && tmax > 0, VTGB_EINVAL,
+                 "llm_decode_attention_masked: bad argument");
+    VTGB_REQUIRE(tmax <= DEC_MAX_T && hd <= 256, VTGB_EUNSUPPORTED, "llm_decode_attention_masked: tmax=%d hd=%d too large", tmax, hd);
+    const size_t lds = 4 * (size_t)(hd + tmax) * sizeof(float);
+    const dim3 grid((unsigned)(((int64_t)B * nq + 3) / 4));
+    if (dtype == VTGB_BF16)
+        hipLaunchKernelGGL(llm_decode_attn_masked_kernel<bf16_t>, grid, dim3(256), lds, s, (const bf16_t*)q, (const bf16_t*)kc, (const bf16_t*)vc, (bf16_t*)out,
+                           pos, key_valid, B, nq, nkv, hd, tmax, scale);
+    else
+        hipLaunchKernelGGL(llm_decode_attn_masked_kernel<float>, grid, dim3(256), lds, s, (const float*)q, (const float*)kc, (const float*)vc, (float*)out,
+                           pos, key_valid, B, nq, nkv, hd, tmax, scale);
     VTGB_HIP(hipGetLastError());
     return VTGB_OK;
 }
@@ -451,8 +593,10 @@ extern "C" int vtgb_llm_silu_mul(int dtype, const void* gu, void* act, int64_t r
 // keys [0, n_keys) -- n_keys fixed, or *pos + 1 (decode step over a static cache, bias row *pos).  Covers the decoder's self-attention
 // (rows_per_batch 1, cache [B, H, N, dk], bias), its cross-attention (fixed n_keys = encoder length, no bias) and the ENCODER's
 // self-attention (rows = B x P straight out of the q|k|v projection: token-major strides, bias row = query position).
-template <typename T>
-__global__ __launch_bounds__(256) void llm_attn_rows_kernel(const vtgb_llm_attn_rows_args a) {
+// MASKED (padded encoder inputs): key_valid[b * kv_stride + key] == 0 keys get no weight and their K / V rows are not read (HF: the
+// attention mask added to the scores as finfo.min -- an exact 0 after the softmax).
+template <typename T, bool MASKED>
+__device__ __forceinline__ void attn_rows_body(const vtgb_llm_attn_rows_args& a, const uint8_t* __restrict__ key_valid, int64_t kv_stride) {
     extern __shared__ float dsm[];   // per wave: hd floats of q + t_pad scores
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int hd = a.head_dim, nq = a.heads;
@@ -473,7 +617,14 @@ __global__ __launch_bounds__(256) void llm_attn_rows_kernel(const vtgb_llm_attn_
     for (int d = lane; d < hd; d += 64) qs[d] = (float)qr[d];
     __syncthreads();
     float mx = -INFINITY;
+    const uint8_t* kvr = MASKED ? key_valid + b * kv_stride : nullptr;
     for (int key = lane; key < n_keys; key += 64) {
+        if constexpr (MASKED) {
+            if (!kvr[key]) {
+                sc[key] = -INFINITY;
+                continue;
+            }
+        }
         const T* k = kr + (int64_t)key * a.kv_tok;
         float dot = 0.f;
         for (int d = 0; d < hd; d++) dot = fmaf(qs[d], (float)k[d], dot);
@@ -485,33 +636,65 @@ __global__ __launch_bounds__(256) void llm_attn_rows_kernel(const vtgb_llm_attn_
     for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
     float sum = 0.f;
     for (int key = lane; key < n_keys; key += 64) {
-        const float e = expf(sc[key] - mx);
+        const float e = MASKED && sc[key] == -INFINITY ? 0.f : expf(sc[key] - mx);
         sc[key] = e;
         sum += e;
     }
     for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
     __syncthreads();
-    const float inv = 1.0f / sum;
+    const float inv = MASKED && sum == 0.f ? 0.f : 1.0f / sum;
     if (idx < total) {
         T* o = reinterpret_cast<T*>(a.out) + r * a.o_row + (int64_t)head * hd;
         for (int d = lane; d < hd; d += 64) {
             float acc = 0.f;
-            for (int key = 0; key < n_keys; key++) acc = fmaf(Cvt<T>::rnd(sc[key] * inv), (float)vr[(int64_t)key * a.kv_tok + d], acc);      // (weights as the model's dtype holds them)
+            for (int key = 0; key < n_keys; key++) {
+                // (MASKED, zero weight: the load goes to row n_keys - 1 and the value is selected away -- no branch, see decode_attn_body)
+                const bool skip = MASKED && sc[key] == 0.f;
+                const float v = (float)vr[(int64_t)(skip ? n_keys - 1 : key) * a.kv_tok + d];
+                acc = fmaf(Cvt<T>::rnd(sc[key] * inv), skip ? 0.f : v, acc);      // (weights as the model's dtype holds them)
+            }
             o[d] = Cvt<T>::to(acc);
         }
     }
 }
 
-extern "C" int vtgb_llm_attention_rows(const vtgb_llm_attn_rows_args* a, vtgb_stream_t s) {
+template <typename T>
+__global__ __launch_bounds__(256) void llm_attn_rows_kernel(const vtgb_llm_attn_rows_args a) {
+    attn_rows_body<T, false>(a, nullptr, 0);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void llm_attn_rows_masked_kernel(const vtgb_llm_attn_rows_args a, const uint8_t* __restrict__ key_valid, int64_t kv_stride) {
+    attn_rows_body<T, true>(a, key_valid, kv_stride);
+}
+
+static int attn_rows_check(const vtgb_llm_attn_rows_args* a) {
     VTGB_REQUIRE(a && a->q && a->k && a->v && a->out && a->rows > 0 && a->heads > 0 && a->head_dim > 0 && a->rows_per_batch > 0, VTGB_EINVAL,
                  "llm_attention_rows: bad argument");
     VTGB_REQUIRE(a->pos || a->n_keys > 0, VTGB_EINVAL, "llm_attention_rows: n_keys or pos");
     VTGB_REQUIRE(a->t_pad >= (a->pos ? 1 : a->n_keys) && a->t_pad <= DEC_MAX_T && a->head_dim <= 256, VTGB_EUNSUPPORTED,
                  "llm_attention_rows: t_pad=%d head_dim=%d outside [n_keys .. %d], <= 256", a->t_pad, a->head_dim, DEC_MAX_T);
+    return VTGB_OK;
+}
+
+extern "C" int vtgb_llm_attention_rows(const vtgb_llm_attn_rows_args* a, vtgb_stream_t s) {
+    if (const int rc = attn_rows_check(a)) return rc;
     const size_t lds = 4 * (size_t)(a->head_dim + a->t_pad) * sizeof(float);
     const dim3 grid((unsigned)(((int64_t)a->rows * a->heads + 3) / 4));
     if (a->dtype == VTGB_BF16) hipLaunchKernelGGL(llm_attn_rows_kernel<bf16_t>, grid, dim3(256), lds, s, *a);
     else hipLaunchKernelGGL(llm_attn_rows_kernel<float>, grid, dim3(256), lds, s, *a);
+    VTGB_HIP(hipGetLastError());
+    return VTGB_OK;
+}
+
+extern "C" int vtgb_llm_attention_rows_masked(const vtgb_llm_attn_rows_args* a, const uint8_t* key_valid, int64_t key_valid_batch_stride, vtgb_stream_t s) {
+    if (const int rc = attn_rows_check(a)) return rc;
+    VTGB_REQUIRE(key_valid && key_valid_batch_stride >= (a->pos ? a->t_pad : a->n_keys), VTGB_EINVAL,
+                 "llm_attention_rows_masked: key_valid and a batch stride >= the key count");
+    const size_t lds = 4 * (size_t)(a->head_dim + a->t_pad) * sizeof(float);
+    const dim3 grid((unsigned)(((int64_t)a->rows * a->heads + 3) / 4));
+    if (a->dtype == VTGB_BF16) hipLaunchKernelGGL(llm_attn_rows_masked_kernel<bf16_t>, grid, dim3(256), lds, s, *a, key_valid, key_valid_batch_stride);
+    else hipLaunchKernelGGL(llm_attn_rows_masked_kernel<float>, grid, dim3(256), lds, s, *a, key_valid, key_valid_batch_stride);
     VTGB_HIP(hipGetLastError());
     return VTGB_OK;
 }

@@ -570,15 +570,22 @@ class _LSTPBase(nn.Module):
     @staticmethod
     def _graph_plan(lm, inputs_embeds, attention_mask, do_sample, temperature, stopping_criteria, kw):
         """The keyword arguments of ``decode.*Decoder.generate`` for this request, or None when it is outside what the graph decoders reproduce
-        (then HF ``generate`` runs it): a Llama / T5 language model on the device, no padding, one beam, neutral penalties; greedy, or (Llama)
-        sampling with temperature / top_k / top_p; ``stopping_criteria`` None or KeywordsStoppingCriteria objects (eval/utils/builder_utils.py:320-346:
-        recognised by their ``keyword_ids`` / ``keywords`` / ``tokenizer`` attributes)."""
+        (then HF ``generate`` runs it): a Llama / T5 language model on the device, a 0 / 1 attention mask with a token in every row (a padded
+        mask goes into the plan as ``attention_mask``), one beam, neutral penalties; greedy, or (Llama) sampling with temperature / top_k / top_p;
+        ``stopping_criteria`` None or KeywordsStoppingCriteria objects (eval/utils/builder_utils.py:320-346: recognised by their ``keyword_ids`` /
+        ``keywords`` / ``tokenizer`` attributes)."""
+        from .decode import prompt_padding
         mt = getattr(lm.config, "model_type", "")
-        if not inputs_embeds.is_cuda or not ("llama" in mt or mt == "t5") or not bool((attention_mask != 0).all()):
+        if not inputs_embeds.is_cuda or not ("llama" in mt or mt == "t5"):
+            return None
+        padded, host_mask = prompt_padding(attention_mask)
+        if padded is None:
             return None
         gc = getattr(lm, "generation_config", None)     # HF generate's defaults come from the generation config
         plan = dict(eos_token_id=kw.pop("eos_token_id", getattr(gc, "eos_token_id", None)), pad_token_id=kw.pop("pad_token_id", getattr(gc, "pad_token_id", None)),
                     min_new_tokens=kw.pop("min_new_tokens", 0))
+        if padded:
+            plan["attention_mask"] = host_mask      # (the host copy: the decoder classifies it again without reading the device)
         if kw.pop("num_beams", 1) != 1 or kw.pop("repetition_penalty", 1.0) not in (None, 1.0) or kw.pop("length_penalty", 1.0) not in (None, 1.0):
             return None
         top_k, top_p = kw.pop("top_k", getattr(gc, "top_k", 50)), kw.pop("top_p", getattr(gc, "top_p", 1.0))

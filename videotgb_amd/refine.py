@@ -91,14 +91,13 @@ def frame_answers(lstp, frames: Tensor, batch_size: int, qformer_text: Optional[
     """Greedy answer tokens from every candidate frame on its own (LSTP_SF_module.py:150-204), all B*num_frames frames in
     one batch: ViT -> Q-Former (the clip's instruction repeated per frame) -> language_projection (a "clip" of one frame)
     -> [prefix | question] -> greedy decode.  ``max_length`` counts prefix + question + new tokens, as
-    ``generate(inputs_embeds=..., max_length=128)`` does in the pinned transformers.  Requires unpadded questions
-    (the graph decoder has no padding mask); returns ids [B*num_frames, <= n_new] (rows end at EOS and are padded, as HF
+    ``generate(inputs_embeds=..., max_length=128)`` does in the pinned transformers (a padded question counts with its pads).
+    Padded questions decode with their mask (``question_mask`` repeated per frame behind the all-ones prefix), as the reference's
+    ``generate(inputs_embeds=..., attention_mask=...)`` does; returns ids [B*num_frames, <= n_new] (rows end at EOS and are padded, as HF
     generate returns them) with the LLaMA 0 -> 2 patch applied."""
     from .decode import GreedyDecoder
     n_all = frames.shape[0]
     num_frames = n_all // batch_size
-    if not bool((question_mask != 0).all()):
-        raise NotImplementedError("frame_answers: padded questions need HF generate (attention-mask aware)")
     enc = None
     if qformer_text is not None:
         enc = {"qformer_input_ids": torch.repeat_interleave(qformer_text, num_frames, 0),
@@ -114,7 +113,11 @@ def frame_answers(lstp, frames: Tensor, batch_size: int, qformer_text: Optional[
     if getattr(lstp, "_decoder", None) is None or lstp._decoder.lm is not lm:
         lstp._decoder = GreedyDecoder(lm)
     gc = getattr(lm, "generation_config", None)     # HF generate's defaults: stop at EOS, pad afterwards
-    out = lstp._decoder.generate(emb, n_new, eos_token_id=getattr(gc, "eos_token_id", None), pad_token_id=getattr(gc, "pad_token_id", None) or 0)
+    mask, qm = None, question_mask.detach().cpu()          # (built on the host: the decoder checks it without reading the device again)
+    if not bool((qm != 0).all()):
+        mask = torch.cat([torch.ones(lm_inputs.shape[:2], dtype=torch.long), torch.repeat_interleave(qm, num_frames, 0).long()], dim=1)
+    out = lstp._decoder.generate(emb, n_new, eos_token_id=getattr(gc, "eos_token_id", None), pad_token_id=getattr(gc, "pad_token_id", None) or 0,
+                                 attention_mask=mask)
     if lstp.model.config.text_config.architectures[0] == "LLaMAForCausalLM":
         out[out == 0] = 2
     return out

@@ -117,7 +117,8 @@ class ClipSession:
                  **gen_kwargs):
         """``model.generate``'s question-side arguments, same meaning; B = rows of ``sampler_text_encoding``, every row a question about the
         session's clip; ``noise`` [2, 2B, T] as generate takes it for B rows.  Returns what ``model.generate(frames, flow_frames, ...)`` returns
-        for these questions: (ids, cand_index[, stages])."""
+        for these questions: (ids, cand_index[, stages]).  Questions of different lengths go in one call padded (``attention_mask`` 0 on the
+        pads, e.g. the tokenizer's padding="longest"): the graph decoder takes the padded batch with HF generate's padding semantics."""
         self._check_fresh()
         m = self.model
         sampler_ids = sampler_text_encoding["input_ids"]
