@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """clips/s of the VideoTGB video -> LLM hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--clips B] [--flow precomputed|raft] [--dump-outputs DIR]     (N > 1 without a launcher: spawns the ranks)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--clips B] [--flow precomputed|raft] [--dump-outputs DIR] [--full]     (N > 1 without a launcher: spawns the ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs and no more: set-up, W warm-up steps, the K timed steps, the outputs if --dump-outputs
+is given, the JSON line.  --full adds every other measurement described below, after the timed steps; the headline is timed the same way.
 
 --dump-outputs DIR writes what the last timed step returned (generated token ids, selected frame indices; every rank's rows in rank
 order) as DIR/<name>.npy in float64.  Inputs and weights are seeded, so two builds run with the same arguments compare output for output.
@@ -17,7 +20,7 @@ per GPU, inputs already resident in HBM:
 Clips shard across ranks with no data-path collective (weak scaling: B clips per GPU per step).
 Weights are random-init (seeded N(0, 0.02)), data synthetic: there is no network here.
 
-The JSON line also carries
+With --full the JSON line also carries (--no-prof, --no-secondary and --no-cpu-baseline leave parts of it out again)
   roofline     for the dominant kernel family: algorithmic FLOPs / summed launch time, both recorded per
                launch with HIP events on the launch stream (include/vtgb.h, vtgb_prof_*) in a short pass
                AFTER the timed region (the headline is timed without the event records);
@@ -77,8 +80,11 @@ def parse():
     ap.add_argument("--flow", choices=["precomputed", "raft"], default="raft",
                     help="raft: RAFT runs inline on the T frames inside the timed step, as eval/utils/model.py:76-84 does (default); "
                          "precomputed: the batch['of'] contract of the LightningModules (src/models/LSTP_SF_module.py:476)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline value does not need: the roofline and per-stage passes, the bf16 parity "
+                         "probe, the hipBLASLt GEMM baseline, the companion legs and the CPU baseline (minutes; a plain run skips them all)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the short companion legs reported next to the headline value (precomputed flow, 32-clip steps, single-clip "
+                    help="with --full: skip the short companion legs reported next to the headline value (precomputed flow, 32-clip steps, single-clip "
                          "latency, host-resident inputs over PCIe, fp32-RAFT exactness mode)")
     ap.add_argument("--max-new-tokens", type=int, default=16)
     ap.add_argument("--llm", default="vicuna-7b")
@@ -98,8 +104,8 @@ def parse():
                     help="two HIP streams: the prefix stage of batch i+1 over the LLM decode of batch i (round 3: +2 %% clips/s -- the persistent "
                          "convolution launches hold every CU, so the decode only fills their tails; off by default: the headline is K strictly "
                          "sequential steps)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-prof", action="store_true", help="skip the (untimed) roofline pass that records per-launch HIP events")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle timed on the host cores")
+    ap.add_argument("--no-prof", action="store_true", help="with --full: skip the (untimed) roofline pass that records per-launch HIP events")
     ap.add_argument("--prof-steps", type=int, default=2, help="steps of the untimed roofline pass")
     ap.add_argument("--stage-times", action="store_true", help="print a per-stage breakdown to stderr")
     ap.add_argument("--spawn", action="store_true", help="start the ranks through torch.distributed.run as a child process even for --gpus 1 "
@@ -112,6 +118,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:      # a plain run: the headline figure only
+        args.no_prof = args.no_secondary = args.no_cpu_baseline = True
     return args
 
 
@@ -443,7 +451,7 @@ def main():
     if args.dump_outputs and 8 * B * world * (args.max_new_tokens + nframe) > DUMP_MAX_BYTES:
         raise SystemExit(f"--dump-outputs: {B * world} clips x ({args.max_new_tokens} ids + {nframe} indices) in float64 exceed {DUMP_MAX_BYTES >> 20} MB")
     batches = [synth_batch(rank, i, B, T, args.flow, dev, cfg) for i in range(2)]
-    cpu_frames = batches[0]["flow_frames"][0, :17].cpu() if args.flow == "raft" else None      # cpu_baseline: 16 pairs of the GPU leg's first clip
+    cpu_frames = batches[0]["flow_frames"][0, :17].cpu() if args.flow == "raft" and not args.no_cpu_baseline else None      # cpu_baseline: 16 pairs of the GPU leg's first clip
     torch.cuda.synchronize()
     if rank == 0:
         print(f"[bench] setup {time.time() - t_setup:.1f}s, world={world}, clips/step/gpu={B}, flow={args.flow}", file=sys.stderr)

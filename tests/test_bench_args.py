@@ -18,3 +18,8 @@ def test_steps_below_one_is_rejected():
 def test_help_lists_dump_outputs():
     p = _bench("--help")
     assert p.returncode == 0 and "--dump-outputs DIR" in p.stdout, p.stdout[-2000:]
+
+
+def test_help_lists_full():
+    p = _bench("--help")
+    assert p.returncode == 0 and "--full" in p.stdout, p.stdout[-2000:]

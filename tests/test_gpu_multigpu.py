@@ -4,7 +4,9 @@ context) at a tiny workload and checks the driver's JSON contract:
   * --force-dist: one rank initialises torch.distributed with the nccl (= RCCL) backend: init, barrier, MAX all-reduce of the timing;
   * --gpus 1 --spawn: the `python bench.py --gpus N` path -- bench.py re-launches itself through torch.distributed.run
     (spawn_ranks), rank 0 of the child prints the line;
-  * --dump-outputs DIR: the last timed step's token ids and frame indices land in DIR as float64 .npy files;
+  * --dump-outputs DIR: the last timed step's token ids and frame indices land in DIR as float64 .npy files (a plain run);
+  * a plain run (no --full) prints the headline keys and runs none of the extra measurements;
+the two launch-path tests pass --full, because the roofline object they check is measured only there;
 and the gradient exchange of config C5 through the C ABI (vtgb_comm_* / vtgb_allreduce_f32) on a one-rank communicator."""
 import json
 import os
@@ -43,13 +45,13 @@ def _check_line(d):
 
 
 def test_bench_one_rank_over_rccl():
-    d, err = _run_bench(["--force-dist"])
+    d, err = _run_bench(["--full", "--force-dist"])
     _check_line(d)
     assert "world=1" in err
 
 
 def test_bench_spawned_through_torch_distributed_run():
-    d, err = _run_bench(["--gpus", "1", "--spawn"])
+    d, err = _run_bench(["--full", "--gpus", "1", "--spawn"])
     _check_line(d)
 
 
@@ -64,6 +66,17 @@ def test_bench_dumps_the_outputs_of_the_last_timed_step(tmp_path):
     assert ids.shape == (2, 16) and idx.shape == (2, 8)                 # 2 clips, 16 new tokens, 8 of 32 frames
     assert (ids == np.round(ids)).all() and ids.min() >= 0 and ids.max() < 32000
     assert (idx == np.round(idx)).all() and idx.min() >= 0 and idx.max() < 32
+
+
+def test_plain_run_carries_the_headline_and_nothing_that_full_adds():
+    d, err = _run_bench([])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert k in d, k
+    assert d["unit"] == "clips/s" and d["higher_is_better"] is True and d["dtype"] == "bf16" and d["steps"] == 1 and d["warmup"] == 1
+    assert d["value"] > 0 and abs(d["value"] - 2 * 1000.0 / d["ms_per_step"]) < 1e-2 * d["value"]        # 2 clips per step on 1 GPU
+    assert d["roofline"] is None
+    for k in ("vit_util", "stages_ms", "parity", "vit_gemm_baseline", "precomputed_flow", "companions", "raft_bf16_fast", "cpu_baseline"):
+        assert k not in d, k
 
 
 def test_allreduce_f32_through_the_c_abi_one_rank():

@@ -6,7 +6,7 @@
 cd "${GRAFT_REPO_ROOT:-.}"
 OTHER="$1"
 run() {
-  python bench.py --no-secondary --no-cpu-baseline --steps 4 --warmup 1 2>/dev/null | python -c "
+  python bench.py --full --no-secondary --no-cpu-baseline --steps 4 --warmup 1 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('$1', 'clips/s', d['value'], 'ms/step', d['ms_per_step'], '| conv', r['achieved'], 'TF/s', r['avg_launch_us'], 'us | gemm', r['other'][0]['achieved'], 'TF/s', r['other'][0]['ms_per_step'], 'ms')"

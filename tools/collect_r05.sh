@@ -2,6 +2,7 @@
 # GPU box: everything under profiles/ for round 5 (run from the repo root through gpurun; outputs in gpurun_out/, copies in profiles/).
 # usage: tools/collect_r05.sh [part ...]   parts: pmc bench trace mfma x3 single vit tests   (default: all)
 R=r05
+ROOT=$(cd "$(dirname "$0")/.." && pwd)      # the checkout this script lies in
 O=$GRAFT_REPO_ROOT/gpurun_out
 P=$GRAFT_REPO_ROOT/profiles
 mkdir -p $O $P; export TMPDIR=/tmp
@@ -22,12 +23,12 @@ if has pmc; then
   cp $O/${R}_pmc_traffic_*.json $P/
 fi
 if has bench; then
-  cd $GRAFT_REPO_ROOT; python3 bench.py > $O/${R}_bench.json 2> $O/${R}_bench.err; tail -c 400 $O/${R}_bench.json; cp $O/${R}_bench.json $P/
+  cd $ROOT; python3 bench.py --full > $O/${R}_bench.json 2> $O/${R}_bench.err; tail -c 400 $O/${R}_bench.json; cp $O/${R}_bench.json $P/
 fi
 if has trace; then
   cd /tmp; rm -rf /tmp/pb
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pb -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-secondary > /tmp/pb.log 2>&1
-  cd $GRAFT_REPO_ROOT; python3 tools/summarize_rocprof.py /tmp/pb $O/${R}_bench_kernel_stats python bench.py --no-cpu-baseline --no-secondary > /dev/null
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pb -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-secondary > /tmp/pb.log 2>&1
+  cd $ROOT; python3 tools/summarize_rocprof.py /tmp/pb $O/${R}_bench_kernel_stats python bench.py --full --no-cpu-baseline --no-secondary > /dev/null
   head -24 $O/${R}_bench_kernel_stats.md | cut -c1-160; cp $O/${R}_bench_kernel_stats.* $P/
 fi
 if has mfma; then
