@@ -73,7 +73,7 @@ def graph_leg(m, batch, out_hf, reps):
         out = m.eval_forward(batch)
         assert tuple(out.shape) == tuple(out_hf.shape), (tuple(out.shape), tuple(out_hf.shape))
         assert out[:, :2].tolist() == out_hf[:, :2].tolist()
-        assert getattr(m, "_graph_decoder", None) is not None
+        assert getattr(m, "_decoder", None) is not None
         return timed(lambda: m.eval_forward(batch), n=reps)
     finally:
         m.fast_decode = False

@@ -20,13 +20,23 @@ the returned ids end at the step where the last row finished.  ``min_new_tokens`
 for the first steps like MinNewTokensLengthLogitsProcessor.  ``eos_token_id=None`` = fixed-length
 decode (the bench's "no EOS stopping, fixed work per clip" mode).
 Greedy ids are checked token-for-token against HF generate at fp32 (tests/test_decode.py, test_gpu_e2e.py).
+
+Structure: ``_GraphDecoder`` owns everything that is not the model -- the state cache (LRU, MAX_STATES), the emission state (token / position
+feedback, finished flags, lengths, sampling and stopping data), token selection, capture, the replay loop and the truncation of the returned ids;
+``GreedyDecoder`` (Llama) and ``T5GreedyDecoder`` add weights, prefill / encoder, one decode step and their buffers.  ``plan_decode`` is the one
+place that decides "graph decoder or HF generate" (each caller's envelope is an ``Envelope`` value), ``decoder_for`` the one place a decoder is
+cached on its owner.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Tuple
+import ctypes
+from typing import Callable, Dict, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
+
+from . import _lib as L, ops
+from .ops import _ptr, _stream, dtype_code
 
 Tensor = torch.Tensor
 
@@ -49,7 +59,7 @@ def _rot_half(x: Tensor) -> Tensor:
 def weights_key(lm):
     """(in-place version, storage address) of every parameter: the decoders hold re-packed COPIES of the language model's weights
     (concatenated q|k|v, tiled decode weights, captured graphs), so an optimizer step, a load_state_dict or a `.data` swap on
-    the model must retire the decoder (round-3 ADVICE) -- models.generate compares this key before every use."""
+    the model must retire the decoder (round-3 ADVICE) -- ``decoder_for`` compares this key before every use."""
     return tuple((p._version, p.data_ptr()) for p in lm.parameters())
 
 
@@ -66,15 +76,175 @@ def _padding(attention_mask: Optional[Tensor], B: int, P: int) -> Optional[Tenso
     return host if padded else None
 
 
-class GreedyDecoder:
+class _GraphDecoder:
+    """The model-independent half of both decoders.  A subclass supplies ``_state`` (its key and buffers, through ``_cached_state``),
+    ``_decode_step(st)`` (one token for every row, ending in ``_emit``) and ``generate``: prefill, ``_reset``, then ``_replay``."""
     MAX_STATES = 4
+    FEEDBACK = ("tok", "pos", "step", "out", "fin", "len")      # what one step writes besides the model's caches
 
+    def __init__(self, lm, fused: bool):
+        self.lm, self.cfg, self.fused = lm, lm.config, fused
+        self.key = weights_key(lm)
+        self.graphs: Dict[tuple, dict] = {}
+
+    def _special(self, eos_token_id, pad_token_id, min_new_tokens):
+        """(eos, pad, min_new) as the state holds them: a one-element eos list unwrapped, HF's pad default (the eos id), ints."""
+        if isinstance(eos_token_id, (list, tuple)):
+            if len(eos_token_id) != 1:
+                raise NotImplementedError(f"{type(self).__name__}: one eos_token_id")
+            eos_token_id = eos_token_id[0]
+        return eos_token_id, int(pad_token_id if pad_token_id is not None else (eos_token_id or 0)), int(min_new_tokens or 0)
+
+    def _cached_state(self, key: tuple, B: int, N: int, n_ar: int, device, eos, pad: int, min_new: int, sample, stop, buffers: Callable[[], dict]) -> dict:
+        """The state under ``key``, most recently used last; a new one takes the least recently used state's place once MAX_STATES are kept
+        (its graph and buffers are freed first) and is the emission state below plus the model's ``buffers()``."""
+        st = self.graphs.pop(key, None)
+        if st is None:
+            while len(self.graphs) >= self.MAX_STATES:
+                self.graphs.pop(next(iter(self.graphs))).clear()
+            st = dict(tok=torch.zeros(B, dtype=torch.long, device=device), pos=torch.zeros(1, dtype=torch.long, device=device),
+                      step=torch.zeros(1, dtype=torch.long, device=device), out=torch.zeros(B, N, dtype=torch.long, device=device),
+                      fin=torch.zeros(B, dtype=torch.bool, device=device), ar=torch.arange(n_ar, device=device), graph=None,
+                      eos=eos, pad=pad, min_new=min_new, sample=sample, stop=stop,
+                      stop_t=[torch.tensor(t, dtype=torch.long, device=device) for t in (stop or ())],      # (device copies made outside any capture)
+                      # sampling: one uniform number per (step, row); the generated length of every row (N = not finished)
+                      u=torch.zeros(N, B, device=device), len=torch.full((B,), N, dtype=torch.long, device=device))
+            st.update(buffers())
+        self.graphs[key] = st
+        return st
+
+    def _pick(self, st, logits: Tensor, step) -> Tensor:
+        """Next token of every row with HF's EOS semantics (device-side, capturable): EOS masked while step < min_new_tokens, finished rows emit
+        pad, a row finishes when it emits EOS.  Greedy: argmax.  Sampling (``st["sample"] = (temperature, top_k, top_p)``): HF's warpers
+        (TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper; GenerationMixin._sample) then the inverse CDF of the warped distribution at
+        this step's uniform number -- the distribution of torch.multinomial(softmax(.)), a different random stream (HF's is not reproducible
+        across torch versions either); temperature -> 0 degenerates to the greedy token."""
+        eos = st["eos"]
+        if eos is not None and st["min_new"] > 0:
+            blocked = (step < st["min_new"]) if isinstance(step, Tensor) else torch.tensor([step < st["min_new"]], device=logits.device)
+            logits = logits.clone()
+            logits[:, eos] = torch.where(blocked, torch.full_like(logits[:, eos], float("-inf")), logits[:, eos])
+        if st["sample"] is None:
+            nxt = logits.argmax(-1)
+        else:
+            temperature, top_k, top_p = st["sample"]
+            k = min(int(top_k), logits.shape[-1]) if top_k else logits.shape[-1]
+            vals, idx = (logits.float() / temperature).topk(k, dim=-1)                  # sorted, largest first
+            p = torch.softmax(vals, -1)
+            if top_p is not None and top_p < 1.0:                                        # nucleus: the smallest prefix whose mass reaches top_p
+                keep = (p.cumsum(-1) - p) < top_p
+                p = torch.where(keep, p, torch.zeros_like(p))
+                p = p / p.sum(-1, keepdim=True)
+            u = st["u"][step] if not isinstance(step, Tensor) else st["u"].index_select(0, step)[0]
+            j = (p.cumsum(-1) < u[:, None]).sum(-1).clamp_(max=k - 1)
+            nxt = idx.gather(-1, j[:, None])[:, 0]
+        if eos is not None or st["stop"] is not None:
+            nxt = torch.where(st["fin"], torch.full_like(nxt, st["pad"]), nxt)
+        if eos is not None:
+            st["fin"].logical_or_(nxt == eos)
+        return nxt
+
+    def _after_token(self, st, step):
+        """Bookkeeping behind the token written to out[:, step]: the keyword-suffix test of KeywordsStoppingCriteria (builder_utils.py:337-339:
+        the last len(k) generated ids equal keyword k's ids) and the finished rows' lengths -- on the device, inside the captured step."""
+        stop = st["stop"]
+        if stop is not None:
+            n = max(len(t) for t in stop)
+            ar = st["ar"][:n]
+            pos = step - (n - 1) + ar                                                    # the last n positions, right-aligned
+            window = st["out"].index_select(1, pos.clamp(min=0))
+            hit = torch.zeros_like(st["fin"])
+            for t, tail in zip(stop, st["stop_t"]):
+                ok = (window[:, n - len(t):] == tail[None]).all(-1) & (pos[n - len(t)] >= 0)
+                hit = hit | ok
+            st["fin"].logical_or_(hit)
+        if st["eos"] is not None or stop is not None:
+            N = st["out"].shape[1]
+            st["len"].copy_(torch.where(st["fin"] & (st["len"] == N), (step + 1).expand_as(st["len"]), st["len"]))
+
+    def _emit(self, st, logits: Tensor):
+        nxt = self._pick(st, logits, st["step"])
+        st["tok"].copy_(nxt)
+        st["out"].index_copy_(1, st["step"], nxt[:, None])
+        self._after_token(st, st["step"])
+        st["pos"].add_(1)
+        st["step"].add_(1)
+
+    def _reset(self, st, ending: bool, pos: int):
+        """The feedback buffers before a call: nothing finished, step 0 at position ``pos`` (the caller sets ``tok``); ``out`` is pre-filled
+        with pad only when rows can end early (otherwise every column is written)."""
+        st["fin"].zero_()
+        st["len"].fill_(st["out"].shape[1])
+        if ending:
+            st["out"].fill_(st["pad"])
+        st["step"].zero_()
+        st["pos"].fill_(pos)
+
+    def _capture(self, st):
+        """One decode step into a graph: a warm-up step on a side stream first (handles, workspaces), the feedback buffers put back after both."""
+        keep = [st[k].clone() for k in self.FEEDBACK]
+
+        def restore():
+            for k, v in zip(self.FEEDBACK, keep):
+                st[k].copy_(v)
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            self._decode_step(st)
+        torch.cuda.current_stream().wait_stream(s)
+        restore()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._decode_step(st)
+        st["graph"] = g
+        restore()
+
+    def _replay(self, st, first: int, use_graph: bool, ending: bool, text_stop=None) -> Tensor:
+        """Steps ``first`` .. N-1 (``first`` tokens were emitted before the loop: Llama's comes from its prefill, T5 starts at 0), one graph replay
+        each, with one host read per 16 tokens when rows can end early (never before a step has run); returns ``out`` up to the step where the
+        last row finished, as HF does -- ``len.max()``, or the length at which the text test first held."""
+        N = st["out"].shape[1]
+        use_graph = use_graph and st["tok"].is_cuda
+        checked, cut = 0, None        # text test: lengths [1, checked] have been tested; cut = the length at which it first held
+        if N > first:
+            if use_graph and st["graph"] is None:
+                self._capture(st)
+            for i in range(N - first):
+                if ending and i % 16 == 0 and i + first > 0:
+                    if text_stop is not None:
+                        cut, checked = self._text_scan(st, text_stop, checked, i + first)
+                        if cut is not None:
+                            break
+                    if bool(st["fin"].all()):
+                        break                      # every row has finished
+                if use_graph:
+                    st["graph"].replay()
+                else:
+                    self._decode_step(st)
+        out = st["out"].clone()
+        if text_stop is not None and cut is None:
+            cut, checked = self._text_scan(st, text_stop, checked, int(st["step"].item()))
+        if ending:
+            n = int(st["len"].max().item())
+            out = out[:, : n if cut is None else min(n, cut)]
+        return out
+
+    @staticmethod
+    def _text_scan(st, text_stop, checked: int, upto: int):
+        """The criteria's TEXT test for the lengths checked + 1 .. upto (host; the first length at which it holds, or None)."""
+        ids = st["out"][:, :upto].cpu()
+        for n in range(checked + 1, upto + 1):
+            if text_stop(ids[:, :n]):
+                return n, n
+        return None, upto
+
+
+class GreedyDecoder(_GraphDecoder):
     def __init__(self, lm, fused: bool = True):
         cfg = lm.config
         if "llama" not in cfg.model_type:
             raise NotImplementedError("GreedyDecoder handles Llama-architecture models; use HF generate otherwise")
-        self.lm, self.cfg = lm, cfg
-        self.key = weights_key(lm)
+        super().__init__(lm, fused)
         self.nh, self.nkv = cfg.num_attention_heads, cfg.num_key_value_heads
         self.hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
         self.eps = cfg.rms_norm_eps
@@ -89,9 +259,7 @@ class GreedyDecoder:
             self.layers.append((l.input_layernorm.weight, wqkv, a.o_proj.weight, l.post_attention_layernorm.weight, wgu,
                                 m.down_proj.weight))
         self.inter = cfg.intermediate_size
-        self.fused = fused
-        self.graphs: Dict[Tuple[int, int, int], dict] = {}
-        self._skinny = None            # per layer (wqkv, wo, wgu, wd) + lm_head in vtgb_gemm_skinny's tiled layout, built on first use
+        self._skinny = None           # per layer (wqkv, wo, wgu, wd) + lm_head in vtgb_gemm_skinny's tiled layout, built on first use
 
     # Projections of the decode step through libvtgb.so's own weight-streaming GEMM (vtgb_gemm_skinny, tiled weights), at every batch
     # it takes (one token per clip, <= 128 rows): no BLAS library call on the f2 path.  Measured on the Vicuna-7B shapes under hipGraph
@@ -101,7 +269,6 @@ class GreedyDecoder:
 
     def _skinny_weights(self):
         if self._skinny is None:
-            from . import ops
             self._skinny = [tuple(ops.SkinnyWeight(w) for w in (wqkv, wo, wgu, wd)) for (_, wqkv, wo, _, wgu, wd) in self.layers]
             self._skinny.append(ops.SkinnyWeight(self.lm.lm_head.weight))
         return self._skinny
@@ -163,28 +330,22 @@ class GreedyDecoder:
         """x [B, P, H] bf16 -> hidden state of the last position [B, H]; fills rows 0..P-1 of every layer's KV cache.  Padded batches:
         ``pos_ids`` [B, P] (the rotary rows) and ``key_mask`` [B, P] fp32 (0 / finfo(float32).min: pad keys get no weight; a query with
         no valid key -- a leading pad -- stays finite)."""
-        import ctypes as C
-        from . import _lib as L, ops
-        lib = L.lib()
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        lib, stream, code = L.lib(), _stream(), dtype_code(x.dtype)
         B, _, H = x.shape
         nh, nkv, hd, M = self.nh, self.nkv, self.hd, B * P
-        code = L.BF16 if x.dtype == torch.bfloat16 else L.F32
         x = x.reshape(M, H).clone()
         h = torch.empty_like(x)
         act = torch.empty(M, self.inter, dtype=x.dtype, device=x.device)
         delta = None
         for li, (ln1, wqkv, wo, ln2, wgu, wd) in enumerate(self.layers):
-            L.check(lib.vtgb_llm_rmsnorm(code, x.data_ptr(), None if delta is None else delta.data_ptr(), ln1.data_ptr(), h.data_ptr(),
-                                         M, H, self.eps, stream))
+            L.check(lib.vtgb_llm_rmsnorm(code, _ptr(x), _ptr(delta), _ptr(ln1), _ptr(h), M, H, self.eps, stream))
             qkv = ops.gemm(h, wqkv).view(B, P, nh + 2 * nkv, hd)
             # rotary on q and k in place + k / v into the cache rows 0 .. P-1: one launch (HF's roundings in the model's dtype)
+            cache = (_ptr(qkv), _ptr(st["kc"][li]), _ptr(st["vc"][li]), _ptr(st["cos"]), _ptr(st["sin"]))
             if pos_ids is None:
-                L.check(lib.vtgb_llm_rope_cache_prefill(code, qkv.data_ptr(), st["kc"][li].data_ptr(), st["vc"][li].data_ptr(), st["cos"].data_ptr(),
-                                                        st["sin"].data_ptr(), B, P, nh, nkv, hd, st["tmax"], stream))
+                L.check(lib.vtgb_llm_rope_cache_prefill(code, *cache, B, P, nh, nkv, hd, st["tmax"], stream))
             else:
-                L.check(lib.vtgb_llm_rope_cache_prefill_pos(code, qkv.data_ptr(), st["kc"][li].data_ptr(), st["vc"][li].data_ptr(), st["cos"].data_ptr(),
-                                                            st["sin"].data_ptr(), pos_ids.data_ptr(), B, P, nh, nkv, hd, st["tmax"], stream))
+                L.check(lib.vtgb_llm_rope_cache_prefill_pos(code, *cache, _ptr(pos_ids), B, P, nh, nkv, hd, st["tmax"], stream))
             flat = qkv.view(B, P, (nh + 2 * nkv) * hd)
             q_, k_, v_ = flat[:, :, : nh * hd], flat[:, :, nh * hd: (nh + nkv) * hd], flat[:, :, (nh + nkv) * hd:]
             if nkv != nh:      # grouped-query attention: every K / V head serves nh / nkv query heads (a copy; the kernel takes equal head counts)
@@ -193,20 +354,17 @@ class GreedyDecoder:
                 v_ = v_.reshape(B, P, nkv, 1, hd).expand(B, P, nkv, rep, hd).reshape(B, P, nh * hd)
             a = ops.attention(q_, k_, v_, nh, float(hd) ** -0.5, key_mask=key_mask, causal=True)
             o = ops.gemm(a.view(M, nh * hd), wo)
-            L.check(lib.vtgb_llm_rmsnorm(code, x.data_ptr(), o.data_ptr(), ln2.data_ptr(), h.data_ptr(), M, H, self.eps, stream))
+            L.check(lib.vtgb_llm_rmsnorm(code, _ptr(x), _ptr(o), _ptr(ln2), _ptr(h), M, H, self.eps, stream))
             gu = ops.gemm(h, wgu)
-            L.check(lib.vtgb_llm_silu_mul(code, gu.data_ptr(), act.data_ptr(), M, self.inter, stream))
+            L.check(lib.vtgb_llm_silu_mul(code, _ptr(gu), _ptr(act), M, self.inter, stream))
             delta = ops.gemm(act, wd)
-        last = (x.view(B, P, H)[:, -1] + delta.view(B, P, H)[:, -1])
-        return last
+        return x.view(B, P, H)[:, -1] + delta.view(B, P, H)[:, -1]
 
     def _head(self, x):
         h = _rms(x, self.lm.model.norm.weight, self.eps)
         if h.is_cuda and h.dim() == 2 and self._use_skinny(h.shape[0], h.dtype):
-            from . import ops
             return ops.gemm_skinny(h.contiguous(), self._skinny_weights()[-1])      # the first token's logits: same kernel as the decode step's
         if h.is_cuda and h.dim() == 2 and self.fused and h.dtype in (torch.float32, torch.bfloat16) and self._gemm_ok(h.dtype):
-            from . import ops
             return ops.gemm(h.contiguous(), self.lm.lm_head.weight)                 # fp32 (exactness mode) / batches beyond the skinny kernel: vtgb_gemm
         return F.linear(h, self.lm.lm_head.weight)
 
@@ -222,71 +380,43 @@ class GreedyDecoder:
         # shape share one graph.  Padded and unpadded states share the MAX_STATES slots, so a loop that alternates both over more than
         # MAX_STATES (batch, bucket, settings) combinations captures graphs again where an unpadded-only loop would not.
         tmax = -(-(P + N) // 64) * 64
-        key = (B, tmax, N, eos, pad, min_new, sample, stop, padded)
-        st = self.graphs.pop(key, None)
-        if st is not None:
-            self.graphs[key] = st                      # most recently used last
-        if st is None:
-            while len(self.graphs) >= self.MAX_STATES:
-                old = self.graphs.pop(next(iter(self.graphs)))
-                old.clear()
+        H, HD, inter = self.cfg.hidden_size, self.nh * self.hd, self.inter
+
+        def z(*shape, dtype=dtype):
+            return torch.zeros(*shape, device=device, dtype=dtype)
+
+        def buffers():
             cos, sin = self._rope(tmax, device, dtype)
-            st = dict(cos=cos, sin=sin, tmax=tmax,
-                      kc=[torch.zeros(B, self.nkv, tmax, self.hd, device=device, dtype=dtype) for _ in self.layers],
-                      vc=[torch.zeros(B, self.nkv, tmax, self.hd, device=device, dtype=dtype) for _ in self.layers],
-                      tok=torch.zeros(B, dtype=torch.long, device=device), pos=torch.zeros(1, dtype=torch.long, device=device),
-                      step=torch.zeros(1, dtype=torch.long, device=device), out=torch.zeros(B, N, dtype=torch.long, device=device),
-                      ar=torch.arange(tmax, device=device), graph=None, eos=eos, pad=pad, min_new=min_new,
-                      fin=torch.zeros(B, dtype=torch.bool, device=device), sample=sample, stop=stop,
-                      stop_t=[torch.tensor(t, dtype=torch.long, device=device) for t in (stop or ())],      # (device copies made outside any capture)
-                      # sampling: one uniform number per (step, row); stopping: the generated length of every row (N = not finished)
-                      u=torch.zeros(N, B, device=device), len=torch.full((B,), N, dtype=torch.long, device=device),
-                      x=torch.zeros(B, self.cfg.hidden_size, device=device, dtype=dtype),
-                      h=torch.zeros(B, self.cfg.hidden_size, device=device, dtype=dtype),
-                      q=torch.zeros(B, self.nh * self.hd, device=device, dtype=dtype),
-                      a=torch.zeros(B, self.nh * self.hd, device=device, dtype=dtype),
-                      act=torch.zeros(B, self.inter, device=device, dtype=dtype))
+            st = dict(cos=cos, sin=sin, tmax=tmax, kc=[z(B, self.nkv, tmax, self.hd) for _ in self.layers],
+                      vc=[z(B, self.nkv, tmax, self.hd) for _ in self.layers], x=z(B, H), h=z(B, H), q=z(B, HD), a=z(B, HD), act=z(B, inter))
             if padded:      # key_valid[b, t]: cache slot t holds a real key of row b; rope_off[b]: rotary row - cache row of its decode steps
-                st.update(key_valid=torch.ones(B, tmax, dtype=torch.uint8, device=device), rope_off=torch.zeros(B, dtype=torch.long, device=device))
+                st.update(key_valid=torch.ones(B, tmax, dtype=torch.uint8, device=device), rope_off=z(B, dtype=torch.long))
             if device.type == "cuda" and self._use_skinny(B, dtype):
-                from . import ops
                 Hq, V = (self.nh + 2 * self.nkv) * self.hd, self.lm.lm_head.weight.shape[0]
-                shapes = ((Hq, self.cfg.hidden_size), (self.cfg.hidden_size, self.nh * self.hd), (2 * self.inter, self.cfg.hidden_size),
-                          (self.cfg.hidden_size, self.inter), (V, self.cfg.hidden_size))
-                st.update(sk_qkv=torch.zeros(B, Hq, device=device, dtype=dtype), sk_o=torch.zeros(B, self.cfg.hidden_size, device=device, dtype=dtype),
-                          sk_gu=torch.zeros(B, 2 * self.inter, device=device, dtype=dtype),
-                          sk_d=torch.zeros(B, self.cfg.hidden_size, device=device, dtype=dtype), sk_logits=torch.zeros(B, V, device=device, dtype=dtype),
-                          sk_ws=torch.zeros(max(ops.gemm_skinny_workspace_bytes(B, n, k) for n, k in shapes), dtype=torch.uint8, device=device))
+                shapes = ((Hq, H), (H, HD), (2 * inter, H), (H, inter), (V, H))
+                st.update(sk_qkv=z(B, Hq), sk_o=z(B, H), sk_gu=z(B, 2 * inter), sk_d=z(B, H), sk_logits=z(B, V),
+                          sk_ws=z(max(ops.gemm_skinny_workspace_bytes(B, n, k) for n, k in shapes), dtype=torch.uint8))
                 self._skinny_weights()
-            self.graphs[key] = st
-        return st
+            return st
+        return self._cached_state((B, tmax, N, eos, pad, min_new, sample, stop, padded), B, N, tmax, device, eos, pad, min_new, sample, stop, buffers)
 
     def _decode_step_fused(self, st):
         """One token for every sequence with the per-layer small ops fused in libvtgb.so
         (include/vtgb.h vtgb_llm_*): per layer 4 GEMMs + 5 fused launches instead of ~25."""
-        import ctypes as C
-        from . import _lib as L
-        lib = L.lib()
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        emb = self.lm.get_input_embeddings()
+        lib, stream = L.lib(), _stream()
         x = st["x"]
-        x.copy_(emb(st["tok"]))
+        x.copy_(self.lm.get_input_embeddings()(st["tok"]))
         B, H = x.shape
-        code = L.BF16 if x.dtype == torch.bfloat16 else L.F32
+        code = dtype_code(x.dtype)
         nq, nkv, hd, tmax = self.nh, self.nkv, self.hd, st["tmax"]
-        pos, padded = st["pos"], "key_valid" in st
+        padded, skinny = "key_valid" in st, "sk_ws" in st
         h, q, a, act = st["h"], st["q"], st["a"], st["act"]
-        delta = None
-        skinny = "sk_ws" in st
         if skinny:
-            from . import ops
             sw, ws = self._skinny_weights(), st["sk_ws"]
 
             def lin(xin, li, which, buf):      # which: 0 qkv, 1 o, 2 gate|up, 3 down
                 return ops.gemm_skinny(xin, sw[li][which], out=st[buf], workspace=ws)
         elif self._gemm_ok(x.dtype):
-            from . import ops
-
             def lin(xin, li, which, buf):      # fp32 (exactness mode) and batches beyond the skinny kernel: libvtgb.so's own GEMM, no BLAS
                 return ops.gemm(xin, self.layers[li][(1, 2, 4, 5)[which]])
         else:
@@ -304,38 +434,26 @@ class GreedyDecoder:
 
         def norm(delta_t, delta_S, wt):
             if delta_t is not None and delta_S > 1:
-                L.check(lib.vtgb_llm_rmsnorm_parts(code, x.data_ptr(), ws.data_ptr(), delta_S, wt.data_ptr(), h.data_ptr(), B, H, self.eps, stream))
+                L.check(lib.vtgb_llm_rmsnorm_parts(code, _ptr(x), _ptr(ws), delta_S, _ptr(wt), _ptr(h), B, H, self.eps, stream))
             else:
-                L.check(lib.vtgb_llm_rmsnorm(code, x.data_ptr(), None if delta_t is None else delta_t.data_ptr(), wt.data_ptr(), h.data_ptr(),
-                                             B, H, self.eps, stream))
-        dS = 1
+                L.check(lib.vtgb_llm_rmsnorm(code, _ptr(x), _ptr(delta_t), _ptr(wt), _ptr(h), B, H, self.eps, stream))
+        # rotary + cache append and attention: vtgb_llm_rope_cache{,_parts}{,_pos} (_parts: q|k|v arrive as split-K fragments; _pos: a padded batch's
+        # per-row rotary offsets) and vtgb_llm_decode_attention{,_masked} take the same pointer lists apart from those extras
+        rope = (_ptr(st["cos"]), _ptr(st["sin"]), _ptr(st["pos"])) + ((_ptr(st["rope_off"]),) if padded else ())
+        attend = lib.vtgb_llm_decode_attention_masked if padded else lib.vtgb_llm_decode_attention
+        attend_pos = (_ptr(st["pos"]),) + ((_ptr(st["key_valid"]),) if padded else ())
+        delta, dS = None, 1
         for li, (ln1, wqkv, wo, ln2, wgu, wd) in enumerate(self.layers):
             norm(delta, dS, ln1)
             qkv, qS = lin_d(h, li, 0, "sk_qkv")
-            if padded and qS > 1:
-                L.check(lib.vtgb_llm_rope_cache_parts_pos(code, ws.data_ptr(), qS, q.data_ptr(), st["kc"][li].data_ptr(), st["vc"][li].data_ptr(),
-                                                          st["cos"].data_ptr(), st["sin"].data_ptr(), pos.data_ptr(), st["rope_off"].data_ptr(), B, nq, nkv,
-                                                          hd, tmax, stream))
-            elif padded:
-                L.check(lib.vtgb_llm_rope_cache_pos(code, qkv.data_ptr(), q.data_ptr(), st["kc"][li].data_ptr(), st["vc"][li].data_ptr(),
-                                                    st["cos"].data_ptr(), st["sin"].data_ptr(), pos.data_ptr(), st["rope_off"].data_ptr(), B, nq, nkv, hd,
-                                                    tmax, stream))
-            elif qS > 1:
-                L.check(lib.vtgb_llm_rope_cache_parts(code, ws.data_ptr(), qS, q.data_ptr(), st["kc"][li].data_ptr(), st["vc"][li].data_ptr(),
-                                                      st["cos"].data_ptr(), st["sin"].data_ptr(), pos.data_ptr(), B, nq, nkv, hd, tmax, stream))
-            else:
-                L.check(lib.vtgb_llm_rope_cache(code, qkv.data_ptr(), q.data_ptr(), st["kc"][li].data_ptr(), st["vc"][li].data_ptr(),
-                                                st["cos"].data_ptr(), st["sin"].data_ptr(), pos.data_ptr(), B, nq, nkv, hd, tmax, stream))
-            if padded:
-                L.check(lib.vtgb_llm_decode_attention_masked(code, q.data_ptr(), st["kc"][li].data_ptr(), st["vc"][li].data_ptr(), a.data_ptr(),
-                                                             pos.data_ptr(), st["key_valid"].data_ptr(), B, nq, nkv, hd, tmax, float(hd) ** -0.5, stream))
-            else:
-                L.check(lib.vtgb_llm_decode_attention(code, q.data_ptr(), st["kc"][li].data_ptr(), st["vc"][li].data_ptr(), a.data_ptr(),
-                                                      pos.data_ptr(), B, nq, nkv, hd, tmax, float(hd) ** -0.5, stream))
+            kv = (_ptr(st["kc"][li]), _ptr(st["vc"][li]))
+            rope_cache = getattr(lib, "vtgb_llm_rope_cache" + ("_parts" if qS > 1 else "") + ("_pos" if padded else ""))
+            L.check(rope_cache(code, *((_ptr(ws), qS) if qS > 1 else (_ptr(qkv),)), _ptr(q), *kv, *rope, B, nq, nkv, hd, tmax, stream))
+            L.check(attend(code, _ptr(q), *kv, _ptr(a), *attend_pos, B, nq, nkv, hd, tmax, float(hd) ** -0.5, stream))
             o, oS = lin_d(a, li, 1, "sk_o")
             norm(o, oS, ln2)
             gu = lin(h, li, 2, "sk_gu")
-            L.check(lib.vtgb_llm_silu_mul(code, gu.data_ptr(), act.data_ptr(), B, self.inter, stream))
+            L.check(lib.vtgb_llm_silu_mul(code, _ptr(gu), _ptr(act), B, self.inter, stream))
             delta, dS = lin_d(act, li, 3, "sk_d")
         norm(delta, dS, self.lm.model.norm.weight)
         if skinny:
@@ -344,63 +462,6 @@ class GreedyDecoder:
             self._emit(st, ops.gemm(h, self.lm.lm_head.weight))
         else:
             self._emit(st, F.linear(h, self.lm.lm_head.weight))
-
-    def _pick(self, st, logits: Tensor, step) -> Tensor:
-        """Next token of every row with HF's EOS semantics (device-side, capturable): EOS masked while step < min_new_tokens, finished rows emit
-        pad, a row finishes when it emits EOS.  Greedy: argmax.  Sampling (``st["sample"] = (temperature, top_k, top_p)``): HF's warpers
-        (TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper; GenerationMixin._sample) then the inverse CDF of the warped distribution at
-        this step's uniform number -- the distribution of torch.multinomial(softmax(.)), a different random stream (HF's is not reproducible
-        across torch versions either); temperature -> 0 degenerates to the greedy token."""
-        eos = st["eos"]
-        if eos is not None and st["min_new"] > 0:
-            blocked = (step < st["min_new"]) if isinstance(step, Tensor) else torch.tensor([step < st["min_new"]], device=logits.device)
-            logits = logits.clone()
-            logits[:, eos] = torch.where(blocked, torch.full_like(logits[:, eos], float("-inf")), logits[:, eos])
-        if st.get("sample") is None:
-            nxt = logits.argmax(-1)
-        else:
-            temperature, top_k, top_p = st["sample"]
-            k = min(int(top_k), logits.shape[-1]) if top_k else logits.shape[-1]
-            vals, idx = (logits.float() / temperature).topk(k, dim=-1)                  # sorted, largest first
-            p = torch.softmax(vals, -1)
-            if top_p is not None and top_p < 1.0:                                        # nucleus: the smallest prefix whose mass reaches top_p
-                keep = (p.cumsum(-1) - p) < top_p
-                p = torch.where(keep, p, torch.zeros_like(p))
-                p = p / p.sum(-1, keepdim=True)
-            u = st["u"][step] if not isinstance(step, Tensor) else st["u"].index_select(0, step)[0]
-            j = (p.cumsum(-1) < u[:, None]).sum(-1).clamp_(max=k - 1)
-            nxt = idx.gather(-1, j[:, None])[:, 0]
-        if eos is not None or st.get("stop") is not None:
-            nxt = torch.where(st["fin"], torch.full_like(nxt, st["pad"]), nxt)
-        if eos is not None:
-            st["fin"].logical_or_(nxt == eos)
-        return nxt
-
-    def _after_token(self, st, step):
-        """Bookkeeping behind the token written to out[:, step]: the keyword-suffix test of KeywordsStoppingCriteria (builder_utils.py:337-339:
-        the last len(k) generated ids equal keyword k's ids) and the finished rows' lengths -- on the device, inside the captured step."""
-        stop = st.get("stop")
-        if stop is not None:
-            L = max(len(t) for t in stop)
-            ar = st["ar"][:L]
-            pos = step - (L - 1) + ar                                                    # the last L positions, right-aligned
-            window = st["out"].index_select(1, pos.clamp(min=0))
-            hit = torch.zeros_like(st["fin"])
-            for t, tail in zip(stop, st["stop_t"]):
-                ok = (window[:, L - len(t):] == tail[None]).all(-1) & (pos[L - len(t)] >= 0)
-                hit = hit | ok
-            st["fin"].logical_or_(hit)
-        if st.get("len") is not None and (st["eos"] is not None or stop is not None):
-            n = st["out"].shape[1]
-            st["len"].copy_(torch.where(st["fin"] & (st["len"] == n), (step + 1).expand_as(st["len"]), st["len"]))
-
-    def _emit(self, st, logits: Tensor):
-        nxt = self._pick(st, logits, st["step"])
-        st["tok"].copy_(nxt)
-        st["out"].index_copy_(1, st["step"], nxt[:, None])
-        self._after_token(st, st["step"])
-        st["pos"].add_(1)
-        st["step"].add_(1)
 
     def _decode_step(self, st):
         """One token for every sequence, entirely on the device (captured)."""
@@ -439,10 +500,7 @@ class GreedyDecoder:
         pmask = _padding(attention_mask, B, P)
         N = max_new_tokens
         dev, dt = inputs_embeds.device, inputs_embeds.dtype
-        if isinstance(eos_token_id, (list, tuple)):
-            if len(eos_token_id) != 1:
-                raise NotImplementedError("GreedyDecoder: one eos_token_id")
-            eos_token_id = eos_token_id[0]
+        eos_token_id, pad_token_id, min_new_tokens = self._special(eos_token_id, pad_token_id, min_new_tokens)
         sample = None
         if do_sample:
             if temperature is None or not float(temperature) > 0.0:
@@ -451,8 +509,7 @@ class GreedyDecoder:
         stop = tuple(tuple(int(v) for v in t) for t in stop_ids if len(t)) if stop_ids else None
         if text_stop is not None and B != 1:
             raise AssertionError("Only support batch size 1 (yet)")                                          # (the reference's criteria: builder_utils.py:334)
-        st = self._state(B, P, N, dev, dt, eos_token_id, int(pad_token_id if pad_token_id is not None else (eos_token_id or 0)), int(min_new_tokens or 0),
-                         sample, stop or None, pmask is not None)
+        st = self._state(B, P, N, dev, dt, eos_token_id, pad_token_id, min_new_tokens, sample, stop or None, pmask is not None)
         if sample is not None:
             if sample_noise is not None:
                 st["u"].copy_(sample_noise.to(dev).reshape(N, B))
@@ -481,70 +538,16 @@ class GreedyDecoder:
             for li, w in enumerate(self.layers):
                 x = self._layer(x, w, cos, sin, st["kc"][li], st["vc"][li], pidx, causal)
             last = x[:, -1]
-        st["fin"].zero_()
-        st["len"].fill_(N)
-        if ending:
-            st["out"].fill_(st["pad"])
-        first = self._pick(st, self._head(last), 0)
+        self._reset(st, ending, P)
+        first = self._pick(st, self._head(last), 0)      # the first token comes from the prefill, eagerly; the loop replays the other N - 1
         st["tok"].copy_(first)
         st["out"][:, 0] = first
-        st["step"].fill_(0)
         self._after_token(st, st["step"])
-        st["pos"].fill_(P)
         st["step"].fill_(1)
-        checked, cut = 0, None        # text test: lengths [1, checked] have been tested; cut = the length at which it first held
-        if N > 1:
-            if use_graph and st["graph"] is None:
-                # warm up on a side stream (handles, workspaces), then capture one step
-                names = ("tok", "pos", "step", "out", "fin", "len")
-                keep = [st[k].clone() for k in names]
-                s = torch.cuda.Stream()
-                s.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(s):
-                    self._decode_step(st)
-                torch.cuda.current_stream().wait_stream(s)
-                for k, v in zip(names, keep):
-                    st[k].copy_(v)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._decode_step(st)
-                st["graph"] = g
-                for k, v in zip(names, keep):
-                    st[k].copy_(v)
-            for i in range(N - 1):
-                if ending and i % 16 == 0:        # one host read per 16 tokens
-                    if text_stop is not None:
-                        cut, checked = self._text_scan(st, text_stop, checked, i + 1)
-                        if cut is not None:
-                            break
-                    if bool(st["fin"].all()):
-                        break                      # every row has finished
-                if use_graph:
-                    st["graph"].replay()
-                else:
-                    self._decode_step(st)
-        out = st["out"].clone()
-        if text_stop is not None and cut is None:
-            cut, checked = self._text_scan(st, text_stop, checked, int(st["step"].item()))
-        if ending:
-            # HF stops at the step where the last row finished: keep the columns up to (and including) that token
-            n = int(st["len"].max().item())
-            if cut is not None:
-                n = min(n, cut)
-            out = out[:, :n]
-        return out
-
-    @staticmethod
-    def _text_scan(st, text_stop, checked: int, upto: int):
-        """The criteria's TEXT test for the lengths checked + 1 .. upto (host; the first length at which it holds, or None)."""
-        ids = st["out"][:, :upto].cpu()
-        for n in range(checked + 1, upto + 1):
-            if text_stop(ids[:, :n]):
-                return n, n
-        return None, upto
+        return self._replay(st, 1, use_graph, ending, text_stop)
 
 
-class T5GreedyDecoder:
+class T5GreedyDecoder(_GraphDecoder):
     """Greedy decode for the seq2seq language model of the BLIP-2 flavours (C1 / C2: Flan-T5 under ``language_model.generate``,
     eval/utils/model.py:432-442; src/models/LSTP_blip2_module.py eval_forward).  HF's generate runs the T5 decoder stack eagerly
     once per token (~1 000 launches per token at 24 layers); here the ENCODER runs once through HF's own module (one pass over
@@ -556,16 +559,13 @@ class T5GreedyDecoder:
     min_new_tokens semantics and the same return convention as HF for encoder-decoder models: ids start with
     ``decoder_start_token_id``.  Scope: greedy; padded encoder inputs (``attention_mask``) mask the pad keys of the encoder's
     self-attention and of every decoder layer's cross-attention, as HF's extended mask does."""
-    MAX_STATES = 4
-
     _ACT_KIND = {"silu": 0, "swish": 0, "gelu_new": 1, "relu": 2, "gelu": 3}
 
     def __init__(self, lm, fused: bool = True):
         cfg = lm.config
         if getattr(cfg, "model_type", "") != "t5":
             raise NotImplementedError("T5GreedyDecoder handles T5ForConditionalGeneration")
-        self.lm, self.cfg = lm, cfg
-        self.key = weights_key(lm)
+        super().__init__(lm, fused)
         self.H, self.dk, self.D = cfg.num_heads, cfg.d_kv, cfg.d_model
         self.eps = cfg.layer_norm_epsilon
         self.start = cfg.decoder_start_token_id if cfg.decoder_start_token_id is not None else cfg.pad_token_id
@@ -594,8 +594,6 @@ class T5GreedyDecoder:
         self.bias_module = sa0
         self.enc_bias_module = lm.encoder.block[0].layer[0].SelfAttention
         self.scale_out = bool(getattr(cfg, "scale_decoder_outputs", getattr(cfg, "tie_word_embeddings", False)))
-        self.fused = fused
-        self.graphs: Dict[tuple, dict] = {}
         self._sk: Dict[int, object] = {}          # id(weight) -> its tiled copy for vtgb_gemm_skinny (built on first use)
 
     # ---- libvtgb.so building blocks (round 4: no torch.matmul / F.linear / F.softmax left in the T5 path on the device; the arithmetic is
@@ -608,7 +606,6 @@ class T5GreedyDecoder:
 
     def _lin(self, x: Tensor, w: Tensor, ws: Optional[Tensor] = None) -> Tensor:
         """x [M, K] @ w[N, K]^T on libvtgb.so: the weight-streaming skinny GEMM for a decode step's rows (bf16, M <= 128, K % 64 == 0), else vtgb_gemm."""
-        from . import ops
         M, K = x.shape
         if x.dtype == torch.bfloat16 and M <= 128 and K % 64 == 0:
             sk = self._sk.get(id(w))
@@ -618,36 +615,24 @@ class T5GreedyDecoder:
         return ops.gemm(x, w)
 
     def _rms(self, x: Tensor, delta: Optional[Tensor], w: Tensor, h: Tensor) -> None:
-        import ctypes as C
-        from . import _lib as L
-        code = L.BF16 if x.dtype == torch.bfloat16 else L.F32
-        L.check(L.lib().vtgb_llm_rmsnorm(code, x.data_ptr(), None if delta is None else delta.data_ptr(), w.data_ptr(), h.data_ptr(), x.shape[0], x.shape[1],
-                                         self.eps, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        L.check(L.lib().vtgb_llm_rmsnorm(dtype_code(x.dtype), _ptr(x), _ptr(delta), _ptr(w), _ptr(h), x.shape[0], x.shape[1], self.eps, _stream()))
 
     def _attn_rows(self, q: Tensor, q_row: int, k: Tensor, v: Tensor, kv_strides, rows: int, rows_per_batch: int, n_keys: int, t_pad: int,
                    bias: Optional[Tensor], bias_strides, pos: Optional[Tensor], key_valid: Optional[Tensor] = None) -> Tensor:
-        import ctypes as C
-        from . import _lib as L
         out = torch.empty(rows, self.H * self.dk, dtype=q.dtype, device=q.device)
-        a = L.LlmAttnRowsArgs(L.BF16 if q.dtype == torch.bfloat16 else L.F32, rows, self.H, self.dk, rows_per_batch, n_keys, t_pad, self.scaling,
-                              q.data_ptr(), q_row, k.data_ptr(), v.data_ptr(), kv_strides[0], kv_strides[1], kv_strides[2],
-                              None if bias is None else bias.data_ptr(), bias_strides[0], bias_strides[1], None if pos is None else pos.data_ptr(),
-                              out.data_ptr(), self.H * self.dk)
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        a = L.LlmAttnRowsArgs(dtype_code(q.dtype), rows, self.H, self.dk, rows_per_batch, n_keys, t_pad, self.scaling, _ptr(q), q_row, _ptr(k), _ptr(v),
+                              *kv_strides, _ptr(bias), *bias_strides, _ptr(pos), _ptr(out), self.H * self.dk)
         if key_valid is None:
-            L.check(L.lib().vtgb_llm_attention_rows(C.byref(a), stream))
+            L.check(L.lib().vtgb_llm_attention_rows(ctypes.byref(a), _stream()))
         else:      # key_valid [K/V batches, stride] uint8: pad keys of a padded encoder input
-            L.check(L.lib().vtgb_llm_attention_rows_masked(C.byref(a), key_valid.data_ptr(), key_valid.stride(0), stream))
+            L.check(L.lib().vtgb_llm_attention_rows_masked(ctypes.byref(a), _ptr(key_valid), key_valid.stride(0), _stream()))
         return out
 
     def _ffn(self, h: Tensor, w: dict, ws: Optional[Tensor] = None) -> Tensor:
-        import ctypes as C
-        from . import _lib as L
         gu = self._lin(h, w["wi"], ws)
         I = gu.shape[1] // 2 if w["gated"] else gu.shape[1]
         act = torch.empty(h.shape[0], I, dtype=h.dtype, device=h.device)
-        L.check(L.lib().vtgb_llm_gated_act(L.BF16 if h.dtype == torch.bfloat16 else L.F32, gu.data_ptr(), act.data_ptr(), h.shape[0], I, self.act_kind,
-                                           1 if w["gated"] else 0, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        L.check(L.lib().vtgb_llm_gated_act(dtype_code(h.dtype), _ptr(gu), _ptr(act), h.shape[0], I, self.act_kind, 1 if w["gated"] else 0, _stream()))
         return self._lin(act, w["wff"], ws)
 
     def _encode_hip(self, inputs_embeds: Tensor, key_valid: Optional[Tensor] = None) -> Tensor:
@@ -675,22 +660,18 @@ class T5GreedyDecoder:
     def _decode_step_hip(self, st):
         """One token for every sequence on libvtgb.so (captured): per layer 6 projections (skinny GEMM), T5 norm x 3, cache append,
         self-attention over the static cache with the relative bias row of *pos, cross-attention over the projected encoder states, gated act."""
-        import ctypes as C
-        from . import _lib as L
-        lib, lm = L.lib(), self.lm
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        lm = self.lm
         B, H, dk, N, Pb = st["tok"].shape[0], self.H, self.dk, st["N"], st["Pb"]
         HD = H * dk
         x, h, q = st["x"], st["h"], st["q"]
         x.copy_(lm.decoder.embed_tokens(st["tok"]))
-        code = L.BF16 if x.dtype == torch.bfloat16 else L.F32
         ws, pos = st.get("sk_ws"), st["pos"]
         delta = None
         for li, w in enumerate(self.layers):
             self._rms(x, delta, w["ln0"], h)
             qkv = self._lin(h, w["wqkv"], ws)                                                                # [B, 3 H dk] = [B, (q | k | v heads), dk]
-            L.check(lib.vtgb_llm_rope_cache(code, qkv.data_ptr(), q.data_ptr(), st["kc"][li].data_ptr(), st["vc"][li].data_ptr(), None, None,
-                                            pos.data_ptr(), B, H, H, dk, N, stream))                         # (no rotary: cache append)
+            L.check(L.lib().vtgb_llm_rope_cache(dtype_code(x.dtype), _ptr(qkv), _ptr(q), _ptr(st["kc"][li]), _ptr(st["vc"][li]), None, None, _ptr(pos),
+                                                B, H, H, dk, N, _stream()))                                  # (no rotary: cache append)
             a = self._attn_rows(q, HD, st["kc"][li], st["vc"][li], (H * N * dk, N * dk, dk), B, 1, 0, N, st["rel"], (N, N * N), pos)
             o = self._lin(a, w["wo"], ws)
             self._rms(x, o, w["ln1"], h)
@@ -703,10 +684,6 @@ class T5GreedyDecoder:
         self._rms(x, delta, lm.decoder.final_layer_norm.weight, h)
         hh = h * (self.D ** -0.5) if self.scale_out else h
         self._emit(st, self._lin(hh, lm.lm_head.weight, ws))
-
-    _pick = GreedyDecoder._pick
-    _emit = GreedyDecoder._emit
-    _after_token = GreedyDecoder._after_token      # (no keyword stopping / length state here: a no-op)
 
     def _norm(self, x: Tensor, w: Tensor) -> Tensor:
         # T5LayerNorm.forward: fp32 variance, no mean subtraction, no bias; cast to the weight's dtype when it is half / bf16
@@ -722,42 +699,34 @@ class T5GreedyDecoder:
         # captured graphs (round-3 VERDICT: the state keyed on the exact P).  The torch path (CPU, fused=False) keeps exact-P caches.
         hip = self._hip(torch.empty(0, device=device, dtype=dtype)) and P <= self.MAX_KEYS and N <= self.MAX_KEYS
         Pb = -(-P // 64) * 64 if hip else P
-        key = (B, Pb, N, eos, pad, min_new, hip, padded)
-        st = self.graphs.pop(key, None)
-        if st is None:
-            while len(self.graphs) >= self.MAX_STATES:
-                self.graphs.pop(next(iter(self.graphs))).clear()
-            H, dk, L = self.H, self.dk, len(self.layers)
+        H, dk, nl = self.H, self.dk, len(self.layers)
+
+        def z(*shape, dtype=dtype):
+            return torch.zeros(*shape, device=device, dtype=dtype)
+
+        def buffers():
             with torch.no_grad():
                 bias = self.bias_module.compute_bias(N, N, device=device)[0].permute(1, 0, 2).contiguous().to(dtype)      # [N (query), H, N (key)]
             ar = torch.arange(N, device=device)
             causal = torch.where(ar[None, :] <= ar[:, None], 0.0, torch.finfo(dtype).min).to(dtype)                      # [N, N]
             st = dict(bias=bias + causal[:, None, :], rel=bias.permute(1, 0, 2).contiguous(), N=N, Pb=Pb, hip=hip,      # rel [H, N (query), N (key)]: the kernel's layout (causality = its key range)
-                      x=torch.zeros(B, self.D, device=device, dtype=dtype), h=torch.zeros(B, self.D, device=device, dtype=dtype),
-                      q=torch.zeros(B, H * dk, device=device, dtype=dtype),
+                      x=z(B, self.D), h=z(B, self.D), q=z(B, H * dk),
                       # cross-attention K | V of every decoder layer [B, Pb, 2 H dk] (fixed addresses: the captured graph reads them) and the encoder length - 1
-                      ckv=[torch.zeros(B, Pb, 2 * H * dk, device=device, dtype=dtype) for _ in range(L)] if hip else [None] * L,
-                      plen=torch.zeros(1, dtype=torch.long, device=device),
-                      kc=[torch.zeros(B, H, N, dk, device=device, dtype=dtype) for _ in range(L)],
-                      vc=[torch.zeros(B, H, N, dk, device=device, dtype=dtype) for _ in range(L)],
-                      ck=[] if hip else [torch.zeros(B, H, P, dk, device=device, dtype=dtype) for _ in range(L)],
-                      cv=[] if hip else [torch.zeros(B, H, P, dk, device=device, dtype=dtype) for _ in range(L)],
-                      tok=torch.zeros(B, dtype=torch.long, device=device), pos=torch.zeros(1, dtype=torch.long, device=device),
-                      step=torch.zeros(1, dtype=torch.long, device=device), out=torch.zeros(B, N, dtype=torch.long, device=device),
-                      fin=torch.zeros(B, dtype=torch.bool, device=device), graph=None, eos=eos, pad=pad, min_new=min_new)
+                      ckv=[z(B, Pb, 2 * H * dk) for _ in range(nl)] if hip else [None] * nl, plen=z(1, dtype=torch.long),
+                      kc=[z(B, H, N, dk) for _ in range(nl)], vc=[z(B, H, N, dk) for _ in range(nl)],
+                      ck=[] if hip else [z(B, H, P, dk) for _ in range(nl)], cv=[] if hip else [z(B, H, P, dk) for _ in range(nl)])
             if padded and hip:      # cross-attention key mask over the bucketed encoder length (written before every call)
-                st["ckv_valid"] = torch.zeros(B, Pb, dtype=torch.uint8, device=device)
+                st["ckv_valid"] = z(B, Pb, dtype=torch.uint8)
             elif padded:
-                st["cmask"] = torch.zeros(B, 1, 1, P, dtype=dtype, device=device)
+                st["cmask"] = z(B, 1, 1, P)
             if device.type == "cuda" and dtype == torch.bfloat16 and self.fused and B <= 128:
-                from . import ops
                 shapes = [(3 * H * dk, self.D), (self.D, H * dk), (H * dk, self.D), (self.layers[0]["wi"].shape[0], self.D), (self.D, self.cfg.d_ff),
                           (self.lm.lm_head.weight.shape[0], self.D)]
                 need = max([ops.gemm_skinny_workspace_bytes(B, n, k) for n, k in shapes if k % 64 == 0] + [0])
                 if need:
-                    st["sk_ws"] = torch.zeros(need, dtype=torch.uint8, device=device)
-        self.graphs[key] = st
-        return st
+                    st["sk_ws"] = z(need, dtype=torch.uint8)
+            return st
+        return self._cached_state((B, Pb, N, eos, pad, min_new, hip, padded), B, N, N, device, eos, pad, min_new, None, None, buffers)
 
     def _decode_step(self, st):
         """One token for every sequence, entirely on the device (captured): `tok` at decoder position `pos` -> next token."""
@@ -806,11 +775,8 @@ class T5GreedyDecoder:
         pmask = _padding(attention_mask, B, P)
         N = max_new_tokens
         dev, dt = inputs_embeds.device, inputs_embeds.dtype
-        if isinstance(eos_token_id, (list, tuple)):
-            if len(eos_token_id) != 1:
-                raise NotImplementedError("T5GreedyDecoder: one eos_token_id")
-            eos_token_id = eos_token_id[0]
-        st = self._state(B, P, N, dev, dt, eos_token_id, int(pad_token_id if pad_token_id is not None else 0), int(min_new_tokens or 0), pmask is not None)
+        eos_token_id, pad_token_id, min_new_tokens = self._special(eos_token_id, pad_token_id, min_new_tokens)
+        st = self._state(B, P, N, dev, dt, eos_token_id, pad_token_id, min_new_tokens, pmask is not None)
         valid = None if pmask is None else (pmask.to(dev) != 0)
         if st["hip"]:
             if valid is not None:
@@ -827,39 +793,9 @@ class T5GreedyDecoder:
             for li, w in enumerate(self.layers):
                 st["ck"][li].copy_(F.linear(enc, w["ck"]).view(B, P, self.H, self.dk).transpose(1, 2))
                 st["cv"][li].copy_(F.linear(enc, w["cv"]).view(B, P, self.H, self.dk).transpose(1, 2))
-        st["fin"].zero_()
-        st["out"].fill_(st["pad"] if eos_token_id is not None else 0)
-        st["tok"].fill_(self.start)
-        st["pos"].zero_()
-        st["step"].zero_()
-        use_graph = use_graph and dev.type == "cuda"
-        if use_graph and st["graph"] is None:
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                self._decode_step(st)                 # warm-up (handles, workspaces); state is reset below
-            torch.cuda.current_stream().wait_stream(s)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._decode_step(st)
-            st["graph"] = g
-            st["fin"].zero_()
-            st["out"].fill_(st["pad"] if eos_token_id is not None else 0)
-            st["tok"].fill_(self.start)
-            st["pos"].zero_()
-            st["step"].zero_()
-        for i in range(N):
-            if eos_token_id is not None and i % 16 == 0 and i > 0 and bool(st["fin"].all()):
-                break
-            if use_graph:
-                st["graph"].replay()
-            else:
-                self._decode_step(st)
-        out = st["out"].clone()
-        if eos_token_id is not None:
-            is_eos = out == eos_token_id
-            first_eos = torch.where(is_eos.any(1), is_eos.float().argmax(1) + 1, torch.full((B,), N, device=dev))
-            out = out[:, : int(first_eos.max().item())]
+        self._reset(st, eos_token_id is not None, 0)
+        st["tok"].fill_(self.start)                                                 # every one of the N tokens is a replayed step from the start token
+        out = self._replay(st, 0, use_graph, eos_token_id is not None)
         return torch.cat([torch.full((B, 1), self.start, dtype=torch.long, device=dev), out], dim=1)
 
 
@@ -897,30 +833,77 @@ def prompt_padding(attention_mask: Tensor) -> Tuple[Optional[bool], Tensor]:
     return not bool((m != 0).all()), m
 
 
-_GREEDY_KEYS = {"max_new_tokens", "min_new_tokens", "do_sample", "num_beams", "eos_token_id", "pad_token_id", "use_cache", "temperature", "top_p",
-                "length_penalty", "repetition_penalty"}
+def decoder_for(owner, lm):
+    """The graph decoder for ``lm``, cached on ``owner`` (attribute ``_decoder``): the cached one when it was built for this ``lm`` and the
+    weights it re-packed are still the model's (``weights_key``), else a new one (``make_decoder``)."""
+    dec = getattr(owner, "_decoder", None)
+    if dec is None or dec.lm is not lm or dec.key != weights_key(lm):
+        dec = owner._decoder = make_decoder(lm)
+    return dec
 
 
-def graph_generate(owner, lm, inputs_embeds: Tensor, attention_mask: Tensor, generate_configs: dict):
-    """``lm.generate(inputs_embeds=..., attention_mask=..., **generate_configs)`` through the graph decoder when the configuration is
-    one it reproduces exactly -- greedy (no sampling, one beam, neutral penalties), ``max_new_tokens`` given, a 0 / 1 attention mask with a
-    token in every row (padded or not), a Llama or T5 language model -- else None (the caller then runs HF generate).  The decoder is
-    cached on ``owner``."""
-    gc = dict(generate_configs or {})
-    if set(gc) - _GREEDY_KEYS or "max_new_tokens" not in gc or gc.get("do_sample", False) or gc.get("num_beams", 1) != 1:
+class Envelope(NamedTuple):
+    """What a caller lets the graph decoders serve: the request keys it knows, the values of beam / penalty keys that leave the ids those of
+    plain decoding, whether sampling is served (Llama), whether ``max_new_tokens`` must be in the request."""
+    keys: frozenset
+    neutral: dict
+    sampling: bool
+    need_max_new: bool
+
+
+_COMMON_KEYS = {"do_sample", "temperature", "top_p", "min_new_tokens", "eos_token_id", "pad_token_id", "num_beams", "repetition_penalty", "length_penalty"}
+# LSTP.generate(**gen_kwargs): sampling and KeywordsStoppingCriteria on Llama (max_new_tokens / use_cache are its own parameters, handed to the decoder
+# by the caller)
+GENERATE_ENVELOPE = Envelope(frozenset(_COMMON_KEYS | {"top_k", "sample_noise", "generator", "stopping_criteria"}),
+                             {"num_beams": (1,), "repetition_penalty": (None, 1.0), "length_penalty": (None, 1.0)}, sampling=True, need_max_new=False)
+# the LightningModule twins' ``generate_configs``: greedy only (length_penalty has no effect on one beam)
+MODULE_ENVELOPE = Envelope(frozenset(_COMMON_KEYS | {"max_new_tokens", "use_cache"}), {"num_beams": (1,), "repetition_penalty": (1.0,)},
+                           sampling=False, need_max_new=True)
+
+
+def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: Envelope) -> Optional[dict]:
+    """The keyword arguments of ``decoder_for(owner, lm).generate(inputs_embeds, max_new_tokens, **plan)`` for a request HF ``generate`` would get
+    as ``generate(inputs_embeds=..., attention_mask=..., **request)``, or None when it is outside what the graph decoders reproduce (then HF
+    ``generate`` runs it).  Inside: a Llama / T5 language model on the device, only keys ``env`` knows, one beam, neutral penalties, a 0 / 1
+    attention mask with a token in every row (a padded mask goes into the plan as its host copy); greedy, or -- Llama, where ``env`` serves it --
+    sampling with temperature / top_k / top_p; ``stopping_criteria`` None or (Llama) KeywordsStoppingCriteria objects (eval/utils/builder_utils.py:
+    320-346: recognised by their ``keyword_ids`` / ``keywords`` / ``tokenizer`` attributes)."""
+    mt = getattr(lm.config, "model_type", "")
+    if not inputs_embeds.is_cuda or not ("llama" in mt or mt == "t5"):
         return None
-    if gc.get("repetition_penalty", 1.0) != 1.0 or not inputs_embeds.is_cuda:
+    if set(request) - env.keys or (env.need_max_new and "max_new_tokens" not in request):
+        return None
+    if any(k in request and request[k] not in ok for k, ok in env.neutral.items()):
+        return None
+    do_sample = bool(request.get("do_sample", False))
+    crit = list(request["stopping_criteria"]) if request.get("stopping_criteria") is not None else []
+    if (do_sample and not env.sampling) or any(not all(hasattr(c, a) for a in ("keyword_ids", "keywords", "tokenizer")) for c in crit):
+        return None
+    if mt == "t5" and (do_sample or crit):
         return None
     padded, host_mask = prompt_padding(attention_mask)
     if padded is None:
         return None
-    try:
-        dec = getattr(owner, "_graph_decoder", None)
-        if dec is None or dec.lm is not lm or dec.key != weights_key(lm):
-            dec = owner._graph_decoder = make_decoder(lm)
-    except NotImplementedError:
+    gc = getattr(lm, "generation_config", None)     # HF generate's defaults come from the generation config
+    plan = dict(eos_token_id=request.get("eos_token_id", getattr(gc, "eos_token_id", None)),
+                pad_token_id=request.get("pad_token_id", getattr(gc, "pad_token_id", None)), min_new_tokens=int(request.get("min_new_tokens", 0) or 0))
+    if padded:
+        plan["attention_mask"] = host_mask      # (the host copy: the decoder classifies it again without reading the device)
+    if do_sample:
+        plan.update(do_sample=True, temperature=request.get("temperature"), top_k=request.get("top_k", getattr(gc, "top_k", 50)),
+                    top_p=request.get("top_p", getattr(gc, "top_p", 1.0)), sample_noise=request.get("sample_noise"), generator=request.get("generator"))
+    if crit:
+        if inputs_embeds.shape[0] != 1:
+            raise AssertionError("Only support batch size 1 (yet)")      # (the reference's criteria)
+        plan.update(keyword_stop_plan(crit))
+    return plan
+
+
+def graph_generate(owner, lm, inputs_embeds: Tensor, attention_mask: Tensor, generate_configs: dict):
+    """``lm.generate(inputs_embeds=..., attention_mask=..., **generate_configs)`` through the graph decoder when the configuration is inside
+    MODULE_ENVELOPE (``plan_decode``), else None (the caller then runs HF generate).  The decoder is cached on ``owner``."""
+    gc = dict(generate_configs or {})
+    plan = plan_decode(lm, inputs_embeds, attention_mask, gc, MODULE_ENVELOPE)
+    if plan is None:
         return None
-    g = getattr(lm, "generation_config", None)
-    return dec.generate(inputs_embeds, int(gc["max_new_tokens"]), eos_token_id=gc.get("eos_token_id", getattr(g, "eos_token_id", None)),
-                        pad_token_id=gc.get("pad_token_id", getattr(g, "pad_token_id", None)), min_new_tokens=int(gc.get("min_new_tokens", 0) or 0),
-                        attention_mask=host_mask if padded else None)
+    return decoder_for(owner, lm).generate(inputs_embeds, int(gc["max_new_tokens"]), **plan)

@@ -569,42 +569,10 @@ class _LSTPBase(nn.Module):
 
     @staticmethod
     def _graph_plan(lm, inputs_embeds, attention_mask, do_sample, temperature, stopping_criteria, kw):
-        """The keyword arguments of ``decode.*Decoder.generate`` for this request, or None when it is outside what the graph decoders reproduce
-        (then HF ``generate`` runs it): a Llama / T5 language model on the device, a 0 / 1 attention mask with a token in every row (a padded
-        mask goes into the plan as ``attention_mask``), one beam, neutral penalties; greedy, or (Llama) sampling with temperature / top_k / top_p;
-        ``stopping_criteria`` None or KeywordsStoppingCriteria objects (eval/utils/builder_utils.py:320-346: recognised by their ``keyword_ids`` /
-        ``keywords`` / ``tokenizer`` attributes)."""
-        from .decode import prompt_padding
-        mt = getattr(lm.config, "model_type", "")
-        if not inputs_embeds.is_cuda or not ("llama" in mt or mt == "t5"):
-            return None
-        padded, host_mask = prompt_padding(attention_mask)
-        if padded is None:
-            return None
-        gc = getattr(lm, "generation_config", None)     # HF generate's defaults come from the generation config
-        plan = dict(eos_token_id=kw.pop("eos_token_id", getattr(gc, "eos_token_id", None)), pad_token_id=kw.pop("pad_token_id", getattr(gc, "pad_token_id", None)),
-                    min_new_tokens=kw.pop("min_new_tokens", 0))
-        if padded:
-            plan["attention_mask"] = host_mask      # (the host copy: the decoder classifies it again without reading the device)
-        if kw.pop("num_beams", 1) != 1 or kw.pop("repetition_penalty", 1.0) not in (None, 1.0) or kw.pop("length_penalty", 1.0) not in (None, 1.0):
-            return None
-        top_k, top_p = kw.pop("top_k", getattr(gc, "top_k", 50)), kw.pop("top_p", getattr(gc, "top_p", 1.0))
-        noise, gen = kw.pop("sample_noise", None), kw.pop("generator", None)
-        if kw:
-            return None
-        crit = list(stopping_criteria) if stopping_criteria is not None else []
-        if any(not all(hasattr(c, a) for a in ("keyword_ids", "keywords", "tokenizer")) for c in crit):
-            return None
-        if mt == "t5":
-            return plan if not do_sample and not crit else None
-        if do_sample:
-            plan.update(do_sample=True, temperature=temperature, top_k=top_k, top_p=top_p, sample_noise=noise, generator=gen)
-        if crit:
-            if inputs_embeds.shape[0] != 1:
-                raise AssertionError("Only support batch size 1 (yet)")      # (the reference's criteria)
-            from .decode import keyword_stop_plan
-            plan.update(keyword_stop_plan(crit))
-        return plan
+        """``decode.plan_decode`` for LSTP.generate's own parameters and its ``**gen_kwargs`` (``kw``): the decoder's keyword arguments, or None."""
+        from .decode import GENERATE_ENVELOPE, plan_decode
+        return plan_decode(lm, inputs_embeds, attention_mask, dict(kw, do_sample=do_sample, temperature=temperature, stopping_criteria=stopping_criteria),
+                           GENERATE_ENVELOPE)
 
     # ---- the reference entry point ---------------------------------------------------------------
     @torch.no_grad()
@@ -655,10 +623,8 @@ class _LSTPBase(nn.Module):
             raise TypeError(f"generate(fast_decode=True): outside the graph decoder's envelope (do_sample={do_sample}, stopping_criteria="
                             f"{type(stopping_criteria).__name__}, kwargs {sorted(gen_kwargs)}); call with fast_decode=False or \"auto\"")
         if plan is not None:
-            from .decode import make_decoder, weights_key
-            if getattr(self, "_decoder", None) is None or self._decoder.lm is not lm or self._decoder.key != weights_key(lm):
-                self._decoder = make_decoder(lm)      # Llama (causal) or T5 (seq2seq, LSTP_blip2)
-            outputs = self._decoder.generate(inputs_embeds, max_new_tokens, **plan)
+            from .decode import decoder_for
+            outputs = decoder_for(self, lm).generate(inputs_embeds, max_new_tokens, **plan)      # Llama (causal) or T5 (seq2seq, LSTP_blip2)
         else:
             outputs = lm.generate(inputs_embeds=inputs_embeds, attention_mask=attention_mask, do_sample=do_sample,
                                   temperature=temperature, max_new_tokens=max_new_tokens, use_cache=use_cache,

@@ -95,7 +95,7 @@ def frame_answers(lstp, frames: Tensor, batch_size: int, qformer_text: Optional[
     Padded questions decode with their mask (``question_mask`` repeated per frame behind the all-ones prefix), as the reference's
     ``generate(inputs_embeds=..., attention_mask=...)`` does; returns ids [B*num_frames, <= n_new] (rows end at EOS and are padded, as HF
     generate returns them) with the LLaMA 0 -> 2 patch applied."""
-    from .decode import GreedyDecoder
+    from .decode import decoder_for
     n_all = frames.shape[0]
     num_frames = n_all // batch_size
     enc = None
@@ -110,14 +110,12 @@ def frame_answers(lstp, frames: Tensor, batch_size: int, qformer_text: Optional[
     n_new = max_length - emb.shape[1]
     if n_new <= 0:
         raise ValueError(f"max_length={max_length} leaves no room after the {emb.shape[1]}-token prompt")
-    if getattr(lstp, "_decoder", None) is None or lstp._decoder.lm is not lm:
-        lstp._decoder = GreedyDecoder(lm)
     gc = getattr(lm, "generation_config", None)     # HF generate's defaults: stop at EOS, pad afterwards
     mask, qm = None, question_mask.detach().cpu()          # (built on the host: the decoder checks it without reading the device again)
     if not bool((qm != 0).all()):
         mask = torch.cat([torch.ones(lm_inputs.shape[:2], dtype=torch.long), torch.repeat_interleave(qm, num_frames, 0).long()], dim=1)
-    out = lstp._decoder.generate(emb, n_new, eos_token_id=getattr(gc, "eos_token_id", None), pad_token_id=getattr(gc, "pad_token_id", None) or 0,
-                                 attention_mask=mask)
+    out = decoder_for(lstp, lm).generate(emb, n_new, eos_token_id=getattr(gc, "eos_token_id", None), pad_token_id=getattr(gc, "pad_token_id", None) or 0,
+                                         attention_mask=mask)
     if lstp.model.config.text_config.architectures[0] == "LLaMAForCausalLM":
         out[out == 0] = 2
     return out
