@@ -624,6 +624,20 @@ int vtgb_pack_skinny_weight(const void* w, int64_t ldw, int32_t N, int32_t K, vo
 size_t vtgb_gemm_skinny_workspace_bytes(const vtgb_gemm_skinny_args* a);
 int vtgb_gemm_skinny(const vtgb_gemm_skinny_args* a, vtgb_stream_t stream);
 
+/* The same weight stream in fp8 (opt-in: decode_weights = "fp8").  Row n of a weight matrix is stored as OCP e4m3 codes q[n, :] and one power-of-two
+ * scale[n] = 2^e, e = the smallest integer with amax[n] * 2^-e <= 448 (0 for a zero row); q = the row times 2^-e rounded to nearest even.  q * scale
+ * is exactly a bf16 number, so the entries below compute what vtgb_gemm_skinny computes from the bf16 matrix dq = q * scale, bit for bit:
+ *   vtgb_pack_skinny_weight_fp8: quantises a bf16 [N, K] matrix (row amax included) into the kernel's stream -- per (128-row tile, 64-deep k-tile)
+ *     one 8 KiB block, row r = 64 bytes, 16-byte slot g = the 8 codes of k 8g .. 8g+7 then the 8 codes of k 32+8g .. 32+8g+7; rows beyond N are
+ *     zero codes -- and writes scale_out[N] (fp32).  Half the bytes of vtgb_pack_skinny_weight's form.
+ *   vtgb_gemm_skinny_fp8: out = (x . q^T) * scale[n], the scale applied to the fp32 accumulators before a fragment is written; `w` is the
+ *     packed stream, w_tiled must be 1 and ldw is ignored.  n_splits, the workspace and defer_reduce are vtgb_gemm_skinny's
+ *     (vtgb_gemm_skinny_splits / vtgb_gemm_skinny_workspace_bytes serve both), and so are the consumers of a deferred split.  Only the
+ *     16-row blocks of x that hold rows < M are staged and multiplied. */
+size_t vtgb_pack_skinny_weight_fp8_bytes(int32_t N, int32_t K);
+int vtgb_pack_skinny_weight_fp8(const void* w, int64_t ldw, int32_t N, int32_t K, void* dst, float* scale_out, vtgb_stream_t stream);
+int vtgb_gemm_skinny_fp8(const vtgb_gemm_skinny_args* a, const float* w_scale, vtgb_stream_t stream);
+
 /* ---- attention for the TRAINABLE stages (config C5, SF flavours): forward + backward, fp32 ---------------------------
  * Replaces, with its autograd, the matmul / softmax / dropout / matmul sequence of InstructBlipQFormerMultiHeadAttention.forward
  * (xinstructblip.py:611-694; BLIP-2 twin xblip2.py) and RopeBertSelfAttention.forward (xropebert.py:243-332; the rotary

@@ -56,6 +56,16 @@ def _rot_half(x: Tensor) -> Tensor:
     return torch.cat((-x[..., h:], x[..., :h]), dim=-1)
 
 
+DECODE_WEIGHTS = ("bf16", "fp8")
+
+
+def check_decode_weights(weights) -> str:
+    """The decode-weight mode as the decoders take it: "bf16" (the model's own weights) or "fp8" (Llama: per-row e4m3 weight stream); ValueError otherwise."""
+    if weights not in DECODE_WEIGHTS:
+        raise ValueError(f"decode_weights must be one of {DECODE_WEIGHTS}, got {weights!r}")
+    return weights
+
+
 def weights_key(lm):
     """(in-place version, storage address) of every parameter: the decoders hold re-packed COPIES of the language model's weights
     (concatenated q|k|v, tiled decode weights, captured graphs), so an optimizer step, a load_state_dict or a `.data` swap on
@@ -82,8 +92,8 @@ class _GraphDecoder:
     MAX_STATES = 4
     FEEDBACK = ("tok", "pos", "step", "out", "fin", "len")      # what one step writes besides the model's caches
 
-    def __init__(self, lm, fused: bool):
-        self.lm, self.cfg, self.fused = lm, lm.config, fused
+    def __init__(self, lm, fused: bool, weights: str = "bf16"):
+        self.lm, self.cfg, self.fused, self.weights = lm, lm.config, fused, check_decode_weights(weights)
         self.key = weights_key(lm)
         self.graphs: Dict[tuple, dict] = {}
 
@@ -240,11 +250,25 @@ class _GraphDecoder:
 
 
 class GreedyDecoder(_GraphDecoder):
-    def __init__(self, lm, fused: bool = True):
+    """``weights="fp8"`` (opt-in): the seven projections of every layer and lm_head are quantised per output row to e4m3 with a power-of-two scale
+    (ops.quantize_fp8_rows) and the decode step streams those codes (ops.SkinnyWeightFp8: half the bytes per token).  ``self.layers`` / ``self.head_w``
+    -- what the prefill, batches beyond the skinny kernel and the torch path multiply by -- then hold the DEQUANTISED weights, which are exactly bf16
+    numbers, so every path decodes the same model: an ordinary Llama whose projection weights are q * scale.  Embeddings and norms are the
+    model's own.  The fused path takes a bf16 model; the torch path (``fused=False``) also an fp32 one, quantised from its bf16 cast."""
+
+    def __init__(self, lm, fused: bool = True, weights: str = "bf16"):
         cfg = lm.config
         if "llama" not in cfg.model_type:
             raise NotImplementedError("GreedyDecoder handles Llama-architecture models; use HF generate otherwise")
-        super().__init__(lm, fused)
+        super().__init__(lm, fused, weights)
+        wdt = lm.lm_head.weight.dtype
+        if self.weights == "fp8" and wdt != torch.bfloat16 and (fused or wdt != torch.float32):
+            raise ValueError(f"decode_weights='fp8' needs a bf16 language model, got {wdt}")
+
+        def prep(w):      # the matrix every path multiplies by: the model's own, or (fp8) its dequantised copy
+            if self.weights == "bf16":
+                return w
+            return ops.dequantize_fp8_rows(*ops.quantize_fp8_rows(w.detach().bfloat16()), dtype=w.dtype)
         self.nh, self.nkv = cfg.num_attention_heads, cfg.num_key_value_heads
         self.hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
         self.eps = cfg.rms_norm_eps
@@ -256,8 +280,9 @@ class GreedyDecoder(_GraphDecoder):
             a, m = l.self_attn, l.mlp
             wqkv = torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], dim=0).contiguous()
             wgu = torch.cat([m.gate_proj.weight, m.up_proj.weight], dim=0).contiguous()
-            self.layers.append((l.input_layernorm.weight, wqkv, a.o_proj.weight, l.post_attention_layernorm.weight, wgu,
-                                m.down_proj.weight))
+            self.layers.append((l.input_layernorm.weight, prep(wqkv), prep(a.o_proj.weight), l.post_attention_layernorm.weight, prep(wgu),
+                                prep(m.down_proj.weight)))
+        self.head_w = prep(lm.lm_head.weight)
         self.inter = cfg.intermediate_size
         self._skinny = None           # per layer (wqkv, wo, wgu, wd) + lm_head in vtgb_gemm_skinny's tiled layout, built on first use
 
@@ -269,8 +294,11 @@ class GreedyDecoder(_GraphDecoder):
 
     def _skinny_weights(self):
         if self._skinny is None:
-            self._skinny = [tuple(ops.SkinnyWeight(w) for w in (wqkv, wo, wgu, wd)) for (_, wqkv, wo, _, wgu, wd) in self.layers]
-            self._skinny.append(ops.SkinnyWeight(self.lm.lm_head.weight))
+            # (fp8: re-quantising the dequantised weights gives the same q * scale -- a row whose largest code rounded down to 224 comes back
+            # as twice the codes under half the scale, the same numbers)
+            pack = ops.SkinnyWeightFp8 if self.weights == "fp8" else ops.SkinnyWeight
+            self._skinny = [tuple(pack(w) for w in (wqkv, wo, wgu, wd)) for (_, wqkv, wo, _, wgu, wd) in self.layers]
+            self._skinny.append(pack(self.head_w))
         return self._skinny
 
     def _use_skinny(self, B: int, dtype) -> bool:
@@ -365,8 +393,8 @@ class GreedyDecoder(_GraphDecoder):
         if h.is_cuda and h.dim() == 2 and self._use_skinny(h.shape[0], h.dtype):
             return ops.gemm_skinny(h.contiguous(), self._skinny_weights()[-1])      # the first token's logits: same kernel as the decode step's
         if h.is_cuda and h.dim() == 2 and self.fused and h.dtype in (torch.float32, torch.bfloat16) and self._gemm_ok(h.dtype):
-            return ops.gemm(h.contiguous(), self.lm.lm_head.weight)                 # fp32 (exactness mode) / batches beyond the skinny kernel: vtgb_gemm
-        return F.linear(h, self.lm.lm_head.weight)
+            return ops.gemm(h.contiguous(), self.head_w)                            # fp32 (exactness mode) / batches beyond the skinny kernel: vtgb_gemm
+        return F.linear(h, self.head_w)
 
     def _gemm_ok(self, dtype) -> bool:
         """vtgb_gemm takes these projections: any shape at fp32; bf16 needs 8-aligned rows."""
@@ -392,7 +420,7 @@ class GreedyDecoder(_GraphDecoder):
             if padded:      # key_valid[b, t]: cache slot t holds a real key of row b; rope_off[b]: rotary row - cache row of its decode steps
                 st.update(key_valid=torch.ones(B, tmax, dtype=torch.uint8, device=device), rope_off=z(B, dtype=torch.long))
             if device.type == "cuda" and self._use_skinny(B, dtype):
-                Hq, V = (self.nh + 2 * self.nkv) * self.hd, self.lm.lm_head.weight.shape[0]
+                Hq, V = (self.nh + 2 * self.nkv) * self.hd, self.head_w.shape[0]
                 shapes = ((Hq, H), (H, HD), (2 * inter, H), (H, inter), (V, H))
                 st.update(sk_qkv=z(B, Hq), sk_o=z(B, H), sk_gu=z(B, 2 * inter), sk_d=z(B, H), sk_logits=z(B, V),
                           sk_ws=z(max(ops.gemm_skinny_workspace_bytes(B, n, k) for n, k in shapes), dtype=torch.uint8))
@@ -459,9 +487,9 @@ class GreedyDecoder(_GraphDecoder):
         if skinny:
             self._emit(st, ops.gemm_skinny(h, sw[-1], out=st["sk_logits"], workspace=ws))
         elif self._gemm_ok(x.dtype):
-            self._emit(st, ops.gemm(h, self.lm.lm_head.weight))
+            self._emit(st, ops.gemm(h, self.head_w))
         else:
-            self._emit(st, F.linear(h, self.lm.lm_head.weight))
+            self._emit(st, F.linear(h, self.head_w))
 
     def _decode_step(self, st):
         """One token for every sequence, entirely on the device (captured)."""
@@ -561,11 +589,13 @@ class T5GreedyDecoder(_GraphDecoder):
     self-attention and of every decoder layer's cross-attention, as HF's extended mask does."""
     _ACT_KIND = {"silu": 0, "swish": 0, "gelu_new": 1, "relu": 2, "gelu": 3}
 
-    def __init__(self, lm, fused: bool = True):
+    def __init__(self, lm, fused: bool = True, weights: str = "bf16"):
         cfg = lm.config
         if getattr(cfg, "model_type", "") != "t5":
             raise NotImplementedError("T5GreedyDecoder handles T5ForConditionalGeneration")
-        super().__init__(lm, fused)
+        if check_decode_weights(weights) != "bf16":
+            raise NotImplementedError("decode_weights='fp8' is implemented for the Llama decoder only")
+        super().__init__(lm, fused, weights)
         self.H, self.dk, self.D = cfg.num_heads, cfg.d_kv, cfg.d_model
         self.eps = cfg.layer_norm_epsilon
         self.start = cfg.decoder_start_token_id if cfg.decoder_start_token_id is not None else cfg.pad_token_id
@@ -816,11 +846,12 @@ def keyword_stop_plan(criteria) -> dict:
     return dict(stop_ids=[[int(v) for v in t.tolist()] for c in crit for t in c.keyword_ids], text_stop=text_stop)
 
 
-def make_decoder(lm):
-    """The graph decoder for a language model: Llama-architecture causal LMs and T5 seq2seq LMs; NotImplementedError otherwise."""
+def make_decoder(lm, weights: str = "bf16"):
+    """The graph decoder for a language model: Llama-architecture causal LMs and T5 seq2seq LMs; NotImplementedError otherwise.
+    ``weights``: "bf16", or "fp8" (Llama only: GreedyDecoder)."""
     if getattr(lm.config, "model_type", "") == "t5":
-        return T5GreedyDecoder(lm)
-    return GreedyDecoder(lm)
+        return T5GreedyDecoder(lm, weights=weights)
+    return GreedyDecoder(lm, weights=weights)
 
 
 def prompt_padding(attention_mask: Tensor) -> Tuple[Optional[bool], Tensor]:
@@ -835,10 +866,12 @@ def prompt_padding(attention_mask: Tensor) -> Tuple[Optional[bool], Tensor]:
 
 def decoder_for(owner, lm):
     """The graph decoder for ``lm``, cached on ``owner`` (attribute ``_decoder``): the cached one when it was built for this ``lm`` and the
-    weights it re-packed are still the model's (``weights_key``), else a new one (``make_decoder``)."""
+    weights it re-packed are still the model's (``weights_key``) and in the owner's mode (attribute ``decode_weights``, "bf16" when it has
+    none), else a new one (``make_decoder``)."""
+    mode = check_decode_weights(getattr(owner, "decode_weights", "bf16"))
     dec = getattr(owner, "_decoder", None)
-    if dec is None or dec.lm is not lm or dec.key != weights_key(lm):
-        dec = owner._decoder = make_decoder(lm)
+    if dec is None or dec.lm is not lm or dec.key != weights_key(lm) or getattr(dec, "weights", "bf16") != mode:
+        dec = owner._decoder = make_decoder(lm) if mode == "bf16" else make_decoder(lm, weights=mode)
     return dec
 
 

@@ -439,7 +439,7 @@ class _LSTPBase(nn.Module):
     MAP = "A"
 
     def __init__(self, base_model_path, device="cuda", lora: bool = False, language_model: Optional[nn.Module] = None,
-                 compute_dtype="bf16", raft_dtype=None, lm_dtype=None, tgb_cfg: Optional[synth.TgbCfg] = None):
+                 compute_dtype="bf16", raft_dtype=None, lm_dtype=None, tgb_cfg: Optional[synth.TgbCfg] = None, decode_weights: str = "bf16"):
         """Reference signature (eval/utils/model.py:21-45, :240-264): ``LSTP(base_model_path, device, lora=False)`` -- the
         HF config in ``base_model_path`` sizes the vision tower, Q-Former and language model (random init, the checkpoint
         fills them), the TGB is BERT-base with fusion_layer 6, RAFT is RAFT-large.  ``base_model_path`` may also be a
@@ -447,8 +447,12 @@ class _LSTPBase(nn.Module):
         ("bf16" / "f32") of the HIP stages, ``raft_dtype`` ("f16c8" by default next to bf16 stages: the reference's fp32 RAFT accuracy on the matrix cores -- update
         block on fp16 + fp8-correction operands, encoders / correlation on split-bf16 operands; "bf16x3" = split-bf16 operands everywhere (round 5's default,
         same accuracy class, 1.2 x slower); "bf16" = the fast REDUCED-PRECISION RAFT; "f32" = the fp32 FMA chain), ``lm_dtype`` of the built LLM
-        (default: bf16 with compute_dtype "bf16", else fp32), ``tgb_cfg`` to size the TGB differently from BERT-base (tests)."""
+        (default: bf16 with compute_dtype "bf16", else fp32), ``tgb_cfg`` to size the TGB differently from BERT-base (tests), ``decode_weights``
+        ("bf16"; "fp8" = opt-in: the graph decoder streams the Llama projections and lm_head as per-row e4m3 codes -- half the weight bytes per
+        token, and the ids are those of the quantised model, not the reference's; see decode.GreedyDecoder)."""
         super().__init__()
+        from .decode import check_decode_weights
+        self.decode_weights = check_decode_weights(decode_weights)      # (decode.decoder_for reads it from its owner)
         hf_config = None
         if isinstance(base_model_path, synth.PathCfg):
             cfg = base_model_path
@@ -461,6 +465,8 @@ class _LSTPBase(nn.Module):
                 if lm_dtype is None:
                     lm_dtype = torch.bfloat16 if ops.dtype_code(compute_dtype) == ops.BF16 else torch.float32
                 language_model = build_language_model(hf_config, lm_dtype)
+        if self.decode_weights == "fp8" and getattr(getattr(language_model, "config", None), "model_type", "") == "t5":
+            raise NotImplementedError("decode_weights='fp8' is implemented for the Llama decoder only")
         self.cfg = cfg
         self.model = PathModel(cfg, language_model, compute_dtype, hf_config=hf_config)
         self.temporal_encoder = TemporalEncoder(cfg.tgb, compute_dtype)
@@ -485,8 +491,9 @@ class _LSTPBase(nn.Module):
         return "f16c8" if ops.dtype_code(compute_dtype) == ops.BF16 else "f32"
 
     @classmethod
-    def from_cfg(cls, cfg: synth.PathCfg, device="cuda", language_model: Optional[nn.Module] = None, compute_dtype="bf16", raft_dtype=None):
-        return cls(cfg, device, False, language_model, compute_dtype, raft_dtype)
+    def from_cfg(cls, cfg: synth.PathCfg, device="cuda", language_model: Optional[nn.Module] = None, compute_dtype="bf16", raft_dtype=None,
+                 decode_weights: str = "bf16"):
+        return cls(cfg, device, False, language_model, compute_dtype, raft_dtype, decode_weights=decode_weights)
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         """Accepts a reference (Lightning) checkpoint's ``state_dict`` as is: peft's ``language_model.base_model.model.``

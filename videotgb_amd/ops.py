@@ -207,6 +207,57 @@ class SkinnyWeight:
         L.check(L.lib().vtgb_pack_skinny_weight(w.data_ptr(), w.stride(0), self.N, self.K, self.data.data_ptr(), _stream()))
 
 
+FP8_MAX = 448.0      # largest finite OCP e4m3fn value
+
+
+def quantize_fp8_rows(w: Tensor) -> Tuple[Tensor, Tensor]:
+    """nn.Linear.weight [N, K] -> (q [N, K] torch.float8_e4m3fn, scale [N] fp32): THE definition of the fp8 weight format (decode_weights="fp8";
+    vtgb_pack_skinny_weight_fp8 computes the same on the device, bit for bit).  Per output row n: e[n] = the smallest integer with
+    amax[n] * 2^-e <= 448 (from the binary exponent: exact; 0 for a zero row), scale[n] = 2^e[n], q[n, :] = w[n, :] * 2^-e rounded to nearest
+    even.  The scale is a power of two so that q * scale is exactly representable in bf16: the fp8 model is an ordinary bf16 model whose
+    weights are ``dequantize_fp8_rows(q, scale)``.  Runs on any device; a non-finite weight raises ValueError."""
+    if w.dim() != 2 or not w.is_floating_point():
+        raise ValueError(f"quantize_fp8_rows: a floating-point [N, K] matrix, got {w.dtype} {tuple(w.shape)}")
+    wf = w.detach().float()
+    if not bool(torch.isfinite(wf).all()):
+        raise ValueError("quantize_fp8_rows: the weights hold Inf or NaN")
+    amax = wf.abs().amax(dim=1)
+    m, x = torch.frexp(amax)                                     # amax = m * 2^x with 0.5 <= m < 1; 448 = 0.875 * 2^9
+    e = torch.where(amax > 0, x - 9 + (m > 0.875).to(x.dtype), torch.zeros_like(x))
+    q = torch.ldexp(wf, -e[:, None]).to(torch.float8_e4m3fn)
+    return q, torch.ldexp(torch.ones_like(amax), e)
+
+
+def dequantize_fp8_rows(q: Tensor, scale: Tensor, dtype: torch.dtype = torch.bfloat16) -> Tensor:
+    """q * scale [N, K]: exact in bf16 (and so in fp32) for the pairs ``quantize_fp8_rows`` returns."""
+    return (q.float() * scale.float()[:, None]).to(dtype)
+
+
+class SkinnyWeightFp8:
+    """nn.Linear.weight [N, K] (bf16) quantised per row to e4m3 and re-laid for vtgb_gemm_skinny_fp8's weight stream
+    (vtgb_pack_skinny_weight_fp8; one-time): ``data`` = the codes, half the bytes of SkinnyWeight's; ``scale`` [N] fp32 powers of two."""
+
+    def __init__(self, w: Tensor):
+        _need_cuda(w)
+        w = w.detach()
+        assert w.dtype == torch.bfloat16 and w.dim() == 2 and w.stride(1) == 1
+        if not bool(torch.isfinite(w).all()):
+            raise ValueError("SkinnyWeightFp8: the weights hold Inf or NaN")
+        self.N, self.K = w.shape
+        nbytes = L.lib().vtgb_pack_skinny_weight_fp8_bytes(self.N, self.K)
+        if nbytes == 0:
+            raise NotImplementedError(f"SkinnyWeightFp8: K={self.K} must be a multiple of 64")
+        self.data = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+        self.scale = torch.empty(self.N, dtype=torch.float32, device=w.device)
+        L.check(L.lib().vtgb_pack_skinny_weight_fp8(w.data_ptr(), w.stride(0), self.N, self.K, self.data.data_ptr(), self.scale.data_ptr(), _stream()))
+
+    def codes(self) -> Tensor:
+        """q [N, K] float8_e4m3fn, un-tiled (tests): the inverse of the stream's layout -- [tile][k-tile][row][slot g][half][8 codes]."""
+        nt, nk = (self.N + 127) // 128, self.K // 64
+        t = self.data.view(nt, nk, 128, 4, 2, 8).permute(0, 2, 1, 4, 3, 5).reshape(nt * 128, self.K)
+        return t[: self.N].contiguous().view(torch.float8_e4m3fn)
+
+
 def gemm_skinny_workspace_bytes(M: int, N: int, K: int, n_splits: int = 0) -> int:
     a = L.GemmSkinnyArgs(M, N, K, n_splits, None, K, None, K, None, N, BF16, 0, None, 0)
     return int(L.lib().vtgb_gemm_skinny_workspace_bytes(C.byref(a)))
@@ -216,9 +267,11 @@ def gemm_skinny(x: Tensor, w: Tensor, out: Optional[Tensor] = None, n_splits: in
                 workspace: Optional[Tensor] = None, defer_reduce: bool = False):
     """``defer_reduce``: returns (out, n_splits, workspace) and leaves the K-split fragments to the consumer (see below).
     x [M <= 128, K] bf16, w [N, K] bf16 (nn.Linear.weight, or its SkinnyWeight) -> x @ w.T [M, N]: the decode step's projections (vtgb_gemm_skinny:
-    the weights stream once, K split over workgroups, fp32 partials added in a fixed order).  ``out`` may be a preallocated
+    the weights stream once, K split over workgroups, fp32 partials added in a fixed order).  A ``SkinnyWeightFp8`` streams e4m3 codes instead
+    (vtgb_gemm_skinny_fp8): the result is that of the bf16 weights ``dequantize_fp8_rows(*quantize_fp8_rows(w))``, bit for bit.  ``out`` may be a preallocated
     [M, N] tensor and ``workspace`` a preallocated uint8 scratch (hipGraph capture: fixed addresses, no allocation)."""
-    tiled = isinstance(w, SkinnyWeight)
+    fp8 = isinstance(w, SkinnyWeightFp8)
+    tiled = fp8 or isinstance(w, SkinnyWeight)
     _need_cuda(x, w.data if tiled else w)
     assert x.dtype == torch.bfloat16 and x.stride(1) == 1 and (tiled or (w.dtype == torch.bfloat16 and w.stride(1) == 1))
     M, K = x.shape
@@ -232,7 +285,10 @@ def gemm_skinny(x: Tensor, w: Tensor, out: Optional[Tensor] = None, n_splits: in
     if need:
         ws = workspace if workspace is not None else _ws.get(need, x.device)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-    L.check(L.lib().vtgb_gemm_skinny(C.byref(a), _stream()))
+    if fp8:
+        L.check(L.lib().vtgb_gemm_skinny_fp8(C.byref(a), w.scale.data_ptr(), _stream()))
+    else:
+        L.check(L.lib().vtgb_gemm_skinny(C.byref(a), _stream()))
     if defer_reduce:
         # (out, n_splits, fragments): n_splits > 1 -> `out` is NOT written; the consumer (vtgb_llm_rmsnorm_parts / vtgb_llm_rope_cache_parts) adds the
         # fragments left in the workspace
