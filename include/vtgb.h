@@ -347,6 +347,32 @@ typedef struct {
 } vtgb_attention_args;
 int vtgb_attention(const vtgb_attention_args* a, vtgb_stream_t stream);
 
+/* Tiled attention for the language model's prefill (HF LlamaAttention as called from eval/utils/model.py:217; added at version 601
+ * without a version bump): bf16 in / out, fp32 scores and accumulator, online softmax over 64-key tiles, so s_kv is not bound by
+ * LDS (<= 4096), and grouped-query heads: query head h reads K/V head h / (heads / kv_heads) in place.  head_dim 64 or 128.
+ * Q is [batch, s_q, heads * head_dim], K/V are [batch, s_kv, kv_heads * head_dim], token-major with the strides below.
+ * key_mask: a value <= finfo(float32).min masks the key HARD -- weight exactly 0 and its K/V rows are never read (a pad slot may hold
+ * NaN); any other value is added to the scaled score.  A query with no visible key gets an all-zero output row.  A row's result does
+ * not depend on batch, on the other rows or on run order (no atomics, keys are not split over workgroups).
+ * Errors, on the host before any launch: VTGB_EINVAL for a NULL args / q / k / v / out, a non-positive size or heads % kv_heads != 0;
+ * VTGB_EUNSUPPORTED for head_dim outside {64, 128}, s_kv > 4096, batch or heads > 65535, strides that break 16-byte alignment
+ * (token and batch strides of q / k / v multiples of 8 elements, of out multiples of 4), or base pointers that do: q / k / v 16-byte,
+ * out 8-byte, key_mask 4-byte aligned (the kernel moves 16-byte pieces of Q, K and V and 8-byte pieces of the output). */
+typedef struct {
+    int32_t batch, heads, kv_heads, head_dim, s_q, s_kv;
+    const void* q;
+    const void* k;
+    const void* v;
+    int64_t q_tok_stride, kv_tok_stride; /* elements between consecutive tokens                         */
+    int64_t q_batch_stride, kv_batch_stride;
+    const float* key_mask;               /* [batch, s_kv] fp32 (see above) or NULL                      */
+    float scale;
+    int32_t causal;                      /* != 0: query q attends keys <= q + (s_kv - s_q)              */
+    void* out;                           /* [batch, s_q, heads*head_dim] bf16                           */
+    int64_t out_tok_stride, out_batch_stride;
+} vtgb_attention_tiled_args;
+int vtgb_attention_tiled(const vtgb_attention_tiled_args* a, vtgb_stream_t stream);
+
 /* LayerNorm over the last dim of fp32 rows; writes fp32 and/or `dtype` copies. */
 typedef struct {
     int32_t dtype, M, D;

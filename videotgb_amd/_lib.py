@@ -42,7 +42,7 @@ EXPORTS = [
     "vtgb_attn_train_forward", "vtgb_attn_train_backward",
     "vtgb_gemm_train", "vtgb_gemm_train_workspace_bytes", "vtgb_col_sum_parts", "vtgb_col_sum_f32", "vtgb_layernorm_train_partials", "vtgb_layernorm_train_forward", "vtgb_layernorm_train_backward",
     "vtgb_gelu_forward", "vtgb_gelu_backward",
-    "vtgb_pair_pack", "vtgb_pair_conv", "vtgb_pair_conv_ex",
+    "vtgb_pair_pack", "vtgb_pair_conv", "vtgb_pair_conv_ex", "vtgb_attention_tiled",
 ]
 COMM_ID_BYTES = 128
 
@@ -176,6 +176,13 @@ class AttentionArgs(C.Structure):
                 ("out_tok_stride", i64), ("out_batch_stride", i64), ("causal", i32)]
 
 
+class AttentionTiledArgs(C.Structure):
+    _fields_ = [("batch", i32), ("heads", i32), ("kv_heads", i32), ("head_dim", i32), ("s_q", i32), ("s_kv", i32),
+                ("q", vp), ("k", vp), ("v", vp), ("q_tok_stride", i64), ("kv_tok_stride", i64), ("q_batch_stride", i64),
+                ("kv_batch_stride", i64), ("key_mask", vp), ("scale", f32), ("causal", i32), ("out", vp),
+                ("out_tok_stride", i64), ("out_batch_stride", i64)]
+
+
 class LlmAttnRowsArgs(C.Structure):
     _fields_ = [("dtype", i32), ("rows", i32), ("heads", i32), ("head_dim", i32), ("rows_per_batch", i32), ("n_keys", i32), ("t_pad", i32),
                 ("scale", f32), ("q", vp), ("q_row", i64), ("k", vp), ("v", vp), ("kv_batch", i64), ("kv_head", i64), ("kv_tok", i64),
@@ -207,7 +214,7 @@ def lib() -> C.CDLL:
     for name, st in (("span_select", SpanSelectArgs), ("span_to_frames", SpanToFramesArgs),
                      ("gather_frames", GatherFramesArgs), ("vit_forward", VitArgs), ("qformer_forward", QFormerArgs),
                      ("pool_project", PoolProjectArgs), ("tgb_forward", TgbArgs), ("gemm", GemmArgs),
-                     ("attention", AttentionArgs), ("layernorm", LayerNormArgs)):
+                     ("attention", AttentionArgs), ("attention_tiled", AttentionTiledArgs), ("layernorm", LayerNormArgs)):
         fn = getattr(L, "vtgb_" + name)
         fn.argtypes = [C.POINTER(st), vp]
         fn.restype = C.c_int

@@ -335,11 +335,14 @@ class GreedyDecoder(_GraphDecoder):
         return x + F.linear(F.silu(gu[..., : self.inter]) * gu[..., self.inter:], wd)
 
     # Prefill on libvtgb.so: the four projections of a layer through vtgb_gemm (bf16: the persistent MFMA kernel, M = B*P rows; fp32:
-    # the FMA kernel), the causal attention through vtgb_attention (bf16: head_dim <= 128, whole K/V of a head in LDS; fp32: the
-    # exactness kernel), RMSNorm(+residual), rotary + cache fill and SwiGLU through the vtgb_llm_* kernels of the decode step -- no
-    # BLAS library call is left on the f2 path, in either dtype (round 4: the fp32 mode, whose ids are compared token for token with
-    # HF generate, runs on libvtgb.so too; grouped-query models repeat K / V heads for the attention call).
-    PREFILL_MAX_TOKENS = 288
+    # the FMA kernel), the causal attention through ops.attention (bf16: vtgb_attention with the whole K/V of a head in LDS up to 288
+    # tokens of equal head counts -- head_dim <= 128 --, vtgb_attention_tiled for longer prompts and grouped-query heads -- head_dim 64 /
+    # 128, K / V heads read in place; fp32: the exactness kernel), RMSNorm(+residual), rotary + cache fill and SwiGLU through the
+    # vtgb_llm_* kernels of the decode step -- no BLAS library call is left on the f2 path, in either dtype (round 4: the fp32 mode, whose
+    # ids are compared token for token with HF generate, runs on libvtgb.so too; there grouped-query models repeat K / V heads).
+    # PREFILL_MAX_TOKENS = 0 forces the torch path.  Activation memory of the bf16 path: B * P x intermediate_size bf16 (+ twice that for
+    # gate | up) -- 0.72 GB (+ 1.44 GB) at B = 16, P = 2048 of Vicuna-7B.
+    PREFILL_MAX_TOKENS = 2048
     PREFILL_MAX_TOKENS_F32 = 1024
 
     def _use_hip_prefill(self, x: Tensor, P: int) -> bool:
@@ -347,8 +350,13 @@ class GreedyDecoder(_GraphDecoder):
             return False
         if x.dtype == torch.float32:
             return P <= self.PREFILL_MAX_TOKENS_F32 and self.hd % 2 == 0 and self.hd <= 128
-        return (x.dtype == torch.bfloat16 and self.nq_eq_nkv and P <= self.PREFILL_MAX_TOKENS
-                and self.hd % 16 == 0 and self.hd <= 128 and self.cfg.hidden_size % 64 == 0 and self.inter % 64 == 0)
+        if not (x.dtype == torch.bfloat16 and P <= self.PREFILL_MAX_TOKENS and self.cfg.hidden_size % 64 == 0 and self.inter % 64 == 0):
+            return False
+        if self.nq_eq_nkv and P <= 288:      # every head_dim the single-pass kernel takes at 288 keys (its bound at head_dim 96 and 128)
+            return self.hd % 16 == 0 and self.hd <= 128
+        # grouped heads or a longer prompt: ops.attention picks the kernel -- the tiled one, or still the single-pass one for equal
+        # heads of head_dim 64 up to its 512 keys (ops._SINGLE_PASS_KEYS)
+        return self.hd in ops._SINGLE_PASS_KEYS and self.nh % self.nkv == 0
 
     @property
     def nq_eq_nkv(self) -> bool:
@@ -376,11 +384,11 @@ class GreedyDecoder(_GraphDecoder):
                 L.check(lib.vtgb_llm_rope_cache_prefill_pos(code, *cache, _ptr(pos_ids), B, P, nh, nkv, hd, st["tmax"], stream))
             flat = qkv.view(B, P, (nh + 2 * nkv) * hd)
             q_, k_, v_ = flat[:, :, : nh * hd], flat[:, :, nh * hd: (nh + nkv) * hd], flat[:, :, (nh + nkv) * hd:]
-            if nkv != nh:      # grouped-query attention: every K / V head serves nh / nkv query heads (a copy; the kernel takes equal head counts)
+            if nkv != nh and x.dtype != torch.bfloat16:      # fp32, grouped-query attention: every K / V head serves nh / nkv query heads (a copy; bf16 reads them in place)
                 rep = nh // nkv
                 k_ = k_.reshape(B, P, nkv, 1, hd).expand(B, P, nkv, rep, hd).reshape(B, P, nh * hd)
                 v_ = v_.reshape(B, P, nkv, 1, hd).expand(B, P, nkv, rep, hd).reshape(B, P, nh * hd)
-            a = ops.attention(q_, k_, v_, nh, float(hd) ** -0.5, key_mask=key_mask, causal=True)
+            a = ops.attention(q_, k_, v_, nh, float(hd) ** -0.5, key_mask=key_mask, causal=True, kv_heads=nkv if x.dtype == torch.bfloat16 else None)
             o = ops.gemm(a.view(M, nh * hd), wo)
             L.check(lib.vtgb_llm_rmsnorm(code, _ptr(x), _ptr(o), _ptr(ln2), _ptr(h), M, H, self.eps, stream))
             gu = ops.gemm(h, wgu)

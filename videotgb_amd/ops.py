@@ -297,11 +297,27 @@ def gemm_skinny(x: Tensor, w: Tensor, out: Optional[Tensor] = None, n_splits: in
     return out
 
 
+# keys one (batch, head) of vtgb_attention's bf16 kernel holds in LDS, by head_dim (attn.hip's ladder); past them the tiled kernel takes over
+_SINGLE_PASS_KEYS = {128: 288, 64: 512}
+
+
 def attention(q: Tensor, k: Tensor, v: Tensor, heads: int, scale: float, key_mask: Optional[Tensor] = None,
-              rope_q: Optional[Tensor] = None, rope_k: Optional[Tensor] = None, causal: bool = False) -> Tensor:
+              rope_q: Optional[Tensor] = None, rope_k: Optional[Tensor] = None, causal: bool = False,
+              kv_heads: Optional[int] = None) -> Tensor:
     """q [B, Sq, H*hd], k/v [B, Skv, H*hd] (any token/batch strides, unit channel stride) -> [B, Sq, H*hd].
-    ``causal``: query q attends keys <= q + (Skv - Sq)."""
+    ``causal``: query q attends keys <= q + (Skv - Sq).  ``kv_heads`` (grouped-query attention): k/v are [B, Skv, kv_heads*hd] and
+    query head h reads K/V head h // (heads // kv_heads).  bf16 causal calls without rotary tables whose keys exceed the single-pass
+    kernel's LDS (288 at head_dim 128, 512 at 64) or whose ``kv_heads`` differs from ``heads`` run on the tiled kernel
+    (``attention_tiled``); every other call is vtgb_attention, which takes equal head counts only."""
     _need_cuda(q, k, v)
+    hd = q.shape[2] // heads
+    grouped = kv_heads is not None and kv_heads != heads
+    if q.dtype == torch.bfloat16 and causal and rope_q is None and rope_k is None and hd in _SINGLE_PASS_KEYS and (
+            grouped or k.shape[1] > _SINGLE_PASS_KEYS[hd]):
+        return attention_tiled(q, k, v, heads, scale, kv_heads=kv_heads, key_mask=key_mask, causal=True)
+    if grouped:
+        raise NotImplementedError(f"ops.attention: kv_heads={kv_heads} != heads={heads} is implemented for bf16 causal calls without "
+                                  f"rotary tables at head_dim 64 / 128 (the tiled kernel)")
     code = dtype_code(q.dtype)
     B, Sq, D = q.shape
     Skv = k.shape[1]
@@ -311,6 +327,25 @@ def attention(q: Tensor, k: Tensor, v: Tensor, heads: int, scale: float, key_mas
                         q.stride(0), k.stride(0), _ptr(key_mask), _ptr(rope_q), _ptr(rope_k), float(scale), out.data_ptr(),
                         out.stride(1), out.stride(0), int(causal))
     L.check(L.lib().vtgb_attention(C.byref(a), _stream()))
+    return out
+
+
+def attention_tiled(q: Tensor, k: Tensor, v: Tensor, heads: int, scale: float, kv_heads: Optional[int] = None,
+                    key_mask: Optional[Tensor] = None, causal: bool = True) -> Tensor:
+    """vtgb_attention_tiled: bf16 q [B, Sq, heads*hd], k/v [B, Skv <= 4096, kv_heads*hd] (hd 64 or 128) -> [B, Sq, heads*hd]; online
+    softmax over 64-key tiles, K/V heads read in place.  ``key_mask`` [B, Skv] fp32: finfo(float32).min masks a key hard (weight
+    exactly 0, its K/V rows never read), other values are added to the scaled score."""
+    _need_cuda(q, k, v)
+    assert q.dtype == k.dtype == v.dtype == torch.bfloat16, "attention_tiled is a bf16 kernel"
+    kv_heads = heads if kv_heads is None else kv_heads
+    B, Sq, D = q.shape
+    Skv = k.shape[1]
+    assert k.stride() == v.stride() and q.stride(2) == 1 and k.stride(2) == 1
+    assert key_mask is None or (key_mask.dtype == torch.float32 and key_mask.shape == (B, Skv) and key_mask.is_contiguous())
+    out = torch.empty(B, Sq, D, dtype=q.dtype, device=q.device)
+    a = L.AttentionTiledArgs(B, heads, kv_heads, D // heads, Sq, Skv, q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(1), k.stride(1),
+                             q.stride(0), k.stride(0), _ptr(key_mask), float(scale), int(causal), out.data_ptr(), out.stride(1), out.stride(0))
+    L.check(L.lib().vtgb_attention_tiled(C.byref(a), _stream()))
     return out
 
 
