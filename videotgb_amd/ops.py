@@ -192,18 +192,28 @@ def gemm(A: Tensor, W: Tensor, bias: Optional[Tensor] = None, epilogue: int = L.
     return out
 
 
+def _skinny_stream_init(self, w: Tensor, nbytes_of, finite: bool = False) -> Tensor:
+    """What SkinnyWeight and SkinnyWeightFp8 share: the checks of nn.Linear.weight [N, K] (bf16), ``N``, ``K`` and the allocation of ``data`` (the
+    re-laid weight stream, ``nbytes_of(N, K)`` bytes).  Returns the detached weight for the caller's pack call."""
+    _need_cuda(w)
+    w = w.detach()
+    assert w.dtype == torch.bfloat16 and w.dim() == 2 and w.stride(1) == 1
+    name = type(self).__name__
+    if finite and not bool(torch.isfinite(w).all()):
+        raise ValueError(f"{name}: the weights hold Inf or NaN")
+    self.N, self.K = w.shape
+    nbytes = nbytes_of(self.N, self.K)
+    if nbytes == 0:
+        raise NotImplementedError(f"{name}: K={self.K} must be a multiple of 64")
+    self.data = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    return w
+
+
 class SkinnyWeight:
     """nn.Linear.weight [N, K] (bf16) re-laid for vtgb_gemm_skinny's weight stream (vtgb_pack_skinny_weight; one-time)."""
 
     def __init__(self, w: Tensor):
-        _need_cuda(w)
-        w = w.detach()
-        assert w.dtype == torch.bfloat16 and w.dim() == 2 and w.stride(1) == 1
-        self.N, self.K = w.shape
-        nbytes = L.lib().vtgb_pack_skinny_weight_bytes(self.N, self.K)
-        if nbytes == 0:
-            raise NotImplementedError(f"SkinnyWeight: K={self.K} must be a multiple of 64")
-        self.data = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+        w = _skinny_stream_init(self, w, L.lib().vtgb_pack_skinny_weight_bytes)
         L.check(L.lib().vtgb_pack_skinny_weight(w.data_ptr(), w.stride(0), self.N, self.K, self.data.data_ptr(), _stream()))
 
 
@@ -238,16 +248,7 @@ class SkinnyWeightFp8:
     (vtgb_pack_skinny_weight_fp8; one-time): ``data`` = the codes, half the bytes of SkinnyWeight's; ``scale`` [N] fp32 powers of two."""
 
     def __init__(self, w: Tensor):
-        _need_cuda(w)
-        w = w.detach()
-        assert w.dtype == torch.bfloat16 and w.dim() == 2 and w.stride(1) == 1
-        if not bool(torch.isfinite(w).all()):
-            raise ValueError("SkinnyWeightFp8: the weights hold Inf or NaN")
-        self.N, self.K = w.shape
-        nbytes = L.lib().vtgb_pack_skinny_weight_fp8_bytes(self.N, self.K)
-        if nbytes == 0:
-            raise NotImplementedError(f"SkinnyWeightFp8: K={self.K} must be a multiple of 64")
-        self.data = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+        w = _skinny_stream_init(self, w, L.lib().vtgb_pack_skinny_weight_fp8_bytes, finite=True)
         self.scale = torch.empty(self.N, dtype=torch.float32, device=w.device)
         L.check(L.lib().vtgb_pack_skinny_weight_fp8(w.data_ptr(), w.stride(0), self.N, self.K, self.data.data_ptr(), self.scale.data_ptr(), _stream()))
 
