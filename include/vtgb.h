@@ -645,6 +645,29 @@ int vtgb_llm_decode_attention_masked(int dtype, const void* q, const void* kc, c
 int vtgb_llm_attention_rows_masked(const vtgb_llm_attn_rows_args* a, const uint8_t* key_valid, int64_t key_valid_batch_stride,
                                    vtgb_stream_t stream);
 
+/* ---- Split-KV decode attention (attn_decode.hip): vtgb_llm_decode_attention{,_masked} for long caches and grouped-query heads.
+ *   out[B, nq*hd] = softmax(scale q K[0..*pos]^T) V[0..*pos] over the static cache kc / vc [B, nkv, tmax, hd], query head h reading K/V
+ *   head h / (nq / nkv) in place.  key_valid [B, tmax] uint8 or NULL (every key valid).  Limits: hd 64 or 128, tmax a multiple of 64 up
+ *   to 16384, nq % nkv == 0 (VTGB_EINVAL otherwise), q / kc / vc / out / workspace 16-byte aligned; anything else is VTGB_EUNSUPPORTED
+ *   on the host, before any launch.  `dtype` VTGB_BF16 / VTGB_F32; scores, softmax weights and sums are fp32.
+ * Two launches, no atomics.  Pass 1: one workgroup per (chunk of 256 consecutive keys, K/V head x block of up to 8 of its query heads,
+ *   batch row) -- the grid depends on tmax only and a workgroup whose chunk starts past *pos leaves at once, so one captured graph serves
+ *   every step; K/V of a chunk are read once for all the query heads of the block.  It leaves fp32 partials per (row r = b * nq + head,
+ *   chunk c) in `workspace`, NC = ceil(tmax / 256):
+ *     float O [B * nq][NC][hd]   O[r][c][:] = sum over the chunk's visible keys of exp(s - m) v
+ *     float ml[B * nq][NC][2]    m = the largest scaled score s of the chunk's visible keys (-inf: none), l = sum exp(s - m)
+ *   = vtgb_llm_decode_attention_split_workspace_bytes = B * nq * NC * (hd + 2) * 4 bytes (0 for an empty shape).
+ *   Pass 2, per row: M = max_c m_c, w_c = exp(m_c - M), out = (sum_c w_c O_c) / (sum_c w_c l_c) over the chunks 0 .. *pos / 256 in
+ *   ascending order, rounded once to `dtype`; a chunk without a visible key has weight 0.
+ * Visible keys: key <= *pos and key_valid[b, key] != 0.  Nothing past *pos is read; the K and V values of a masked key never enter a
+ *   product (weight exactly 0), so a pad slot may hold anything, NaN included.  No visible key: the output row is 0.
+ * Which keys share a partial sum and the order inside every sum depend on the key index, dtype and hd only: a row's bits do not depend on
+ *   B, tmax, nq / nkv or the other rows (they differ from vtgb_llm_decode_attention's in the last bits: another summation order). */
+int64_t vtgb_llm_decode_attention_split_workspace_bytes(int32_t B, int32_t nq, int32_t hd, int32_t tmax);
+int vtgb_llm_decode_attention_split(int dtype, const void* q, const void* kc, const void* vc, void* out, const int64_t* pos,
+                                    const uint8_t* key_valid /* NULL: none */, void* workspace, int32_t B, int32_t nq, int32_t nkv, int32_t hd,
+                                    int32_t tmax, float scale, vtgb_stream_t stream);
+
 size_t vtgb_pack_skinny_weight_bytes(int32_t N, int32_t K);
 int vtgb_pack_skinny_weight(const void* w, int64_t ldw, int32_t N, int32_t K, void* dst, vtgb_stream_t stream);
 size_t vtgb_gemm_skinny_workspace_bytes(const vtgb_gemm_skinny_args* a);

@@ -43,6 +43,7 @@ EXPORTS = [
     "vtgb_gemm_train", "vtgb_gemm_train_workspace_bytes", "vtgb_col_sum_parts", "vtgb_col_sum_f32", "vtgb_layernorm_train_partials", "vtgb_layernorm_train_forward", "vtgb_layernorm_train_backward",
     "vtgb_gelu_forward", "vtgb_gelu_backward",
     "vtgb_pair_pack", "vtgb_pair_conv", "vtgb_pair_conv_ex", "vtgb_attention_tiled",
+    "vtgb_llm_decode_attention_split_workspace_bytes", "vtgb_llm_decode_attention_split",
 ]
 COMM_ID_BYTES = 128
 
@@ -266,6 +267,10 @@ def lib() -> C.CDLL:
     for fn in (L.vtgb_llm_rope_cache_pos, L.vtgb_llm_rope_cache_parts_pos, L.vtgb_llm_rope_cache_prefill_pos, L.vtgb_llm_decode_attention_masked,
                L.vtgb_llm_attention_rows_masked):
         fn.restype = C.c_int
+    L.vtgb_llm_decode_attention_split_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    L.vtgb_llm_decode_attention_split_workspace_bytes.restype = i64
+    L.vtgb_llm_decode_attention_split.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]
+    L.vtgb_llm_decode_attention_split.restype = C.c_int
     L.vtgb_gemm_skinny_splits.argtypes = [C.POINTER(GemmSkinnyArgs)]
     L.vtgb_gemm_skinny_splits.restype = i32
     L.vtgb_gemm_skinny.argtypes = [C.POINTER(GemmSkinnyArgs), vp]

@@ -1,0 +1,253 @@
+// attn_decode.hip -- split-KV ("flash-decoding") single-query attention over the static K/V cache of the decode step, for caches the
+// one-wave-per-head kernel of llm.hip cannot hold (its scores live in LDS: 2048 keys) or serves badly (8 workgroups at batch 1).
+// Two launches, no atomics:
+//
+// Pass 1, llm_decode_attn_split_kernel.  Grid (key chunk, K/V head x query-head block, batch row), fixed by tmax, so one captured graph
+// serves every step: a workgroup whose chunk starts past *pos leaves after reading *pos.  A chunk is DEC_SPLIT_CHUNK = 256 keys, 64 per
+// wave.  A wave holds its 64 K rows in registers -- 16-byte loads, consecutive lanes on consecutive 16-byte pieces of a row, so one load
+// instruction reads 64 / LPR whole rows (LPR = lanes per row = hd * sizeof(T) / 16) -- and every query head of the block (at most
+// DEC_SPLIT_HEADS = 8 heads of ONE K/V head; a larger nq / nkv takes more blocks) takes its scores from those registers; the V rows then
+// replace them and serve every head again.  K/V are read once per group of query heads, in place from [B, nkv, tmax, hd].
+// Per (row, query head, chunk) the workgroup leaves fp32 partials in the workspace: m = the largest scaled score of the chunk's visible
+// keys (-inf: none), l = sum exp(s - m), O[hd] = sum exp(s - m) v.  A key is visible if key <= *pos (and key_valid[b, key] != 0, MASKED);
+// nothing past *pos is read, and the K and V values of any other key are replaced by zeros before any product -- its score is -inf, its weight
+// exactly 0 --, so what a pad slot or the cache past *pos holds (NaN included) cannot reach an output.
+//
+// Pass 2, llm_decode_attn_combine_kernel.  Per (row, query head): M = max_c m_c, w_c = exp(m_c - M), out = (sum_c w_c O_c) / (sum_c w_c l_c)
+// over the chunks 0 .. *pos / 256 in ascending order, rounded once to T.  A chunk without a visible key (m_c = -inf) is skipped: weight 0,
+// no exp(-inf - -inf).  No visible key at all: a zero row.
+//
+// Determinism.  Which keys share a partial sum (chunk = key / 256, wave = key / 64 % 4, a lane's keys = key % (64 / LPR)) and the order
+// inside every sum depend on the key index, T and hd alone -- not on B, tmax, the grid, the number of query heads per K/V head or which
+// heads share a workgroup (a head's arithmetic never sees another head's values).  An invisible key adds an exact +0.  So a row's output
+// is a function of (q, K/V[0..*pos], key_valid[0..*pos]): the same bits in any batch, any cache length, grouped or replicated K/V.
+#include "common.h"
+
+#include <math.h>
+
+constexpr int DEC_SPLIT_CHUNK = 256;      // keys per workgroup: 4 waves x 64
+constexpr int DEC_SPLIT_HEADS = 8;        // query heads per workgroup (of one K/V head)
+constexpr int DEC_SPLIT_MAX_T = 16384;
+
+// v + (v of lane ^ MASK): MASK < 16 on the VALU (DPP, inside a row of 16 lanes), else through the LDS crossbar.  Both lanes of a pair
+// compute the same sum (a + b == b + a), so after the steps MASK = 1, 2, 4 ... every lane of the group holds the group's total.
+template <int MASK>
+__device__ __forceinline__ float add_xor(float v) {
+    if constexpr (MASK == 1 || MASK == 2) {
+        constexpr int ctrl = MASK == 1 ? 0xB1 : 0x4E;      // quad_perm [1,0,3,2] / [2,3,0,1]
+        return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xF, 0xF, false));
+    } else {
+        return v + __shfl_xor(v, MASK);
+    }
+}
+
+template <int W>      // sum over aligned groups of W lanes (W a power of two <= 64)
+__device__ __forceinline__ float group_sum(float v) {
+    if constexpr (W > 1) v = add_xor<1>(v);
+    if constexpr (W > 2) v = add_xor<2>(v);
+    if constexpr (W > 4) v = add_xor<4>(v);
+    if constexpr (W > 8) v = add_xor<8>(v);
+    if constexpr (W > 16) v = add_xor<16>(v);
+    if constexpr (W > 32) v = add_xor<32>(v);
+    return v;
+}
+
+template <typename T, int HD, bool MASKED>
+__global__ __launch_bounds__(256) void llm_decode_attn_split_kernel(const T* __restrict__ q, const T* __restrict__ kc, const T* __restrict__ vc,
+                                                                    float* __restrict__ ws, const int64_t* __restrict__ pos_p,
+                                                                    const uint8_t* __restrict__ key_valid, int B, int nq, int nkv, int tmax,
+                                                                    float scale) {
+    constexpr int EPL = 16 / (int)sizeof(T);      // elements per lane: one 16-byte piece of a row
+    constexpr int LPR = HD / EPL;                 // lanes per row
+    constexpr int RPI = 64 / LPR;                 // rows per load instruction
+    constexpr int NI = 64 / RPI;                  // load instructions per wave (== LPR)
+    typedef T TV __attribute__((ext_vector_type(EPL)));
+    __shared__ float qs[DEC_SPLIT_HEADS][HD];
+    __shared__ float sc[DEC_SPLIT_HEADS][DEC_SPLIT_CHUNK];
+    __shared__ __attribute__((aligned(16))) float red[4][DEC_SPLIT_HEADS][HD];
+
+    const int chunk = blockIdx.x, b = blockIdx.z;
+    const int pos = min((int)(*pos_p), tmax - 1);
+    if (chunk * DEC_SPLIT_CHUNK > pos) return;
+    const int group = nq / nkv, nhb = (group + DEC_SPLIT_HEADS - 1) / DEC_SPLIT_HEADS;
+    const int kvh = blockIdx.y / nhb, hb = blockIdx.y % nhb;
+    const int head0 = kvh * group + hb * DEC_SPLIT_HEADS, nh = min(DEC_SPLIT_HEADS, group - hb * DEC_SPLIT_HEADS);
+    const int nc = (tmax + DEC_SPLIT_CHUNK - 1) / DEC_SPLIT_CHUNK;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c = lane % LPR, rs = lane / LPR;      // this lane's 16-byte piece and row slot
+
+    for (int i = tid; i < nh * HD; i += 256) qs[i / HD][i % HD] = (float)q[((int64_t)b * nq + head0) * HD + i];
+
+    // ---- K: the wave's 64 rows -> registers (row kl0 + i * RPI of instruction i); invisible rows stay zeros
+    const int kl0 = wave * 64 + rs, key0 = chunk * DEC_SPLIT_CHUNK + kl0;
+    const int64_t base = ((int64_t)b * nkv + kvh) * tmax * HD + c * EPL;
+    const uint8_t* kvr = MASKED ? key_valid + (int64_t)b * tmax : nullptr;
+    unsigned vis = 0;
+#pragma unroll
+    for (int i = 0; i < NI; i++) {
+        const int key = key0 + i * RPI;
+        bool ok = key <= pos;
+        if (MASKED && ok) ok = kvr[key] != 0;
+        vis |= ok ? 1u << i : 0u;
+    }
+    // No branch per row: an invisible row's load goes to row *pos (in bounds, one row for the whole grid) and its value is selected away,
+    // so all NI loads are in flight together and nothing a pad slot holds reaches a product.
+    TV zero;
+#pragma unroll
+    for (int e = 0; e < EPL; e++) zero[e] = (T)0.f;
+    auto load_rows = [&](const T* __restrict__ src, TV (&reg)[NI]) {
+#pragma unroll
+        for (int i = 0; i < NI; i++) {
+            const bool ok = vis >> i & 1;
+            const TV v = *reinterpret_cast<const TV*>(src + base + (int64_t)(ok ? key0 + i * RPI : pos) * HD);
+            reg[i] = ok ? v : zero;
+        }
+    };
+    TV reg[NI];
+    load_rows(kc, reg);
+    __syncthreads();      // qs
+
+    // ---- scores: per head, the lane's piece of every row, then the row's LPR lanes
+    for (int h = 0; h < nh; h++) {
+        float qv[EPL];
+#pragma unroll
+        for (int e = 0; e < EPL; e++) qv[e] = qs[h][c * EPL + e];
+#pragma unroll
+        for (int i = 0; i < NI; i++) {
+            float dot = 0.f;
+#pragma unroll
+            for (int e = 0; e < EPL; e++) dot = fmaf(qv[e], (float)reg[i][e], dot);
+            dot = group_sum<LPR>(dot);
+            if (c == 0) sc[h][kl0 + i * RPI] = (vis >> i & 1) ? dot * scale : -INFINITY;
+        }
+    }
+    // ---- V replaces K in the registers (the loads fly behind the softmax)
+    load_rows(vc, reg);
+    __syncthreads();      // sc
+
+    // ---- softmax statistics of the chunk: wave w takes the heads w, w + 4
+    for (int h = wave; h < nh; h += 4) {
+        float s[4], m = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            s[j] = sc[h][lane + 64 * j];
+            m = fmaxf(m, s[j]);
+        }
+        for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            s[j] = s[j] == -INFINITY ? 0.f : expf(s[j] - m);      // (an invisible key: exactly 0, also when the chunk has no visible key)
+            sc[h][lane + 64 * j] = s[j];
+        }
+        const float l = group_sum<64>((s[0] + s[1]) + (s[2] + s[3]));
+        if (lane == 0) {
+            float* ml = ws + (int64_t)B * nq * nc * HD + (((int64_t)b * nq + head0 + h) * nc + chunk) * 2;
+            ml[0] = m;
+            ml[1] = l;
+        }
+    }
+    __syncthreads();      // sc = weights
+
+    // ---- O: per head, the lane's rows in ascending order, then the wave's row slots, then (below) the four waves
+    for (int h = 0; h < nh; h++) {
+        float acc[EPL];
+#pragma unroll
+        for (int e = 0; e < EPL; e++) acc[e] = 0.f;
+#pragma unroll
+        for (int i = 0; i < NI; i++) {
+            const float p = sc[h][kl0 + i * RPI];
+#pragma unroll
+            for (int e = 0; e < EPL; e++) acc[e] = fmaf(p, (float)reg[i][e], acc[e]);
+        }
+#pragma unroll
+        for (int e = 0; e < EPL; e++) {
+            float v = acc[e];
+            if constexpr (RPI > 1) v += __shfl_xor(v, LPR);
+            if constexpr (RPI > 2) v += __shfl_xor(v, 2 * LPR);
+            if constexpr (RPI > 4) v += __shfl_xor(v, 4 * LPR);
+            acc[e] = v;
+        }
+        if (rs == 0) {
+#pragma unroll
+            for (int e = 0; e < EPL; e += 4)
+                *reinterpret_cast<f32x4*>(&red[wave][h][c * EPL + e]) = f32x4{acc[e], acc[e + 1], acc[e + 2], acc[e + 3]};
+        }
+    }
+    __syncthreads();      // red
+    for (int i = tid; i < nh * HD; i += 256) {
+        const int h = i / HD, d = i % HD;
+        ws[(((int64_t)b * nq + head0 + h) * nc + chunk) * HD + d] = ((red[0][h][d] + red[1][h][d]) + red[2][h][d]) + red[3][h][d];
+    }
+}
+
+// One workgroup of hd threads per (row, query head).
+template <typename T>
+__global__ __launch_bounds__(128) void llm_decode_attn_combine_kernel(const float* __restrict__ ws, T* __restrict__ out, const int64_t* __restrict__ pos_p,
+                                                                      int64_t rows, int hd, int tmax) {
+    const int64_t row = blockIdx.x;
+    const int d = threadIdx.x;
+    const int nc = (tmax + DEC_SPLIT_CHUNK - 1) / DEC_SPLIT_CHUNK;
+    const int pos = min((int)(*pos_p), tmax - 1);
+    const int n = pos < 0 ? 0 : pos / DEC_SPLIT_CHUNK + 1;
+    const float* O = ws + row * nc * hd + d;
+    const float* ml = ws + rows * nc * hd + row * nc * 2;
+    float M = -INFINITY;
+    for (int ch = 0; ch < n; ch++) M = fmaxf(M, ml[2 * ch]);
+    float num = 0.f, den = 0.f;
+    for (int ch = 0; ch < n; ch++) {
+        const float m = ml[2 * ch];
+        if (m == -INFINITY) continue;      // no visible key in this chunk: weight 0
+        const float w = expf(m - M);
+        num = fmaf(w, O[(int64_t)ch * hd], num);
+        den = fmaf(w, ml[2 * ch + 1], den);
+    }
+    out[row * hd + d] = (T)(den > 0.f ? num / den : 0.f);
+}
+
+template <typename T, int HD>
+static int launch_split(const void* q, const void* kc, const void* vc, void* out, const int64_t* pos, const uint8_t* key_valid, void* workspace,
+                        int B, int nq, int nkv, int tmax, float scale, hipStream_t s) {
+    const int group = nq / nkv, nhb = (group + DEC_SPLIT_HEADS - 1) / DEC_SPLIT_HEADS, nc = (tmax + DEC_SPLIT_CHUNK - 1) / DEC_SPLIT_CHUNK;
+    const dim3 grid(nc, nkv * nhb, B);
+    float* ws = (float*)workspace;
+    if (key_valid)
+        hipLaunchKernelGGL((llm_decode_attn_split_kernel<T, HD, true>), grid, dim3(256), 0, s, (const T*)q, (const T*)kc, (const T*)vc, ws, pos, key_valid,
+                           B, nq, nkv, tmax, scale);
+    else
+        hipLaunchKernelGGL((llm_decode_attn_split_kernel<T, HD, false>), grid, dim3(256), 0, s, (const T*)q, (const T*)kc, (const T*)vc, ws, pos,
+                           (const uint8_t*)nullptr, B, nq, nkv, tmax, scale);
+    VTGB_HIP(hipGetLastError());
+    hipLaunchKernelGGL(llm_decode_attn_combine_kernel<T>, dim3((unsigned)((int64_t)B * nq)), dim3(HD), 0, s, (const float*)ws, (T*)out, pos,
+                       (int64_t)B * nq, HD, tmax);
+    VTGB_HIP(hipGetLastError());
+    return VTGB_OK;
+}
+
+extern "C" int64_t vtgb_llm_decode_attention_split_workspace_bytes(int32_t B, int32_t nq, int32_t hd, int32_t tmax) {
+    if (B <= 0 || nq <= 0 || hd <= 0 || tmax <= 0) return 0;
+    const int64_t nc = (tmax + DEC_SPLIT_CHUNK - 1) / DEC_SPLIT_CHUNK;
+    return (int64_t)B * nq * nc * (hd + 2) * (int64_t)sizeof(float);
+}
+
+extern "C" int vtgb_llm_decode_attention_split(int dtype, const void* q, const void* kc, const void* vc, void* out, const int64_t* pos,
+                                               const uint8_t* key_valid, void* workspace, int32_t B, int32_t nq, int32_t nkv, int32_t hd,
+                                               int32_t tmax, float scale, vtgb_stream_t stream) {
+    VTGB_REQUIRE(q && kc && vc && out && pos && workspace, VTGB_EINVAL, "llm_decode_attention_split: NULL operand");
+    VTGB_REQUIRE((dtype == VTGB_BF16 || dtype == VTGB_F32) && B > 0 && nq > 0 && nkv > 0 && tmax > 0, VTGB_EINVAL,
+                 "llm_decode_attention_split: bad argument");
+    VTGB_REQUIRE(nq % nkv == 0, VTGB_EINVAL, "llm_decode_attention_split: nq=%d is not a multiple of nkv=%d", nq, nkv);
+    VTGB_REQUIRE(hd == 64 || hd == 128, VTGB_EUNSUPPORTED, "llm_decode_attention_split: hd=%d, built for 64 and 128", hd);
+    VTGB_REQUIRE(tmax % 64 == 0 && tmax <= DEC_SPLIT_MAX_T, VTGB_EUNSUPPORTED, "llm_decode_attention_split: tmax=%d is not a multiple of 64 up to %d",
+                 tmax, DEC_SPLIT_MAX_T);
+    const int nhb = (nq / nkv + DEC_SPLIT_HEADS - 1) / DEC_SPLIT_HEADS;
+    VTGB_REQUIRE(B <= 65535 && (int64_t)nkv * nhb <= 65535, VTGB_EUNSUPPORTED, "llm_decode_attention_split: B=%d / nq=%d exceed the grid", B, nq);
+    const auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+    VTGB_REQUIRE(!misaligned(q) && !misaligned(kc) && !misaligned(vc) && !misaligned(out) && !misaligned(workspace), VTGB_EUNSUPPORTED,
+                 "llm_decode_attention_split: q / kc / vc / out / workspace need 16-byte alignment");
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == VTGB_BF16)
+        return hd == 128 ? launch_split<bf16_t, 128>(q, kc, vc, out, pos, key_valid, workspace, B, nq, nkv, tmax, scale, s)
+                         : launch_split<bf16_t, 64>(q, kc, vc, out, pos, key_valid, workspace, B, nq, nkv, tmax, scale, s);
+    return hd == 128 ? launch_split<float, 128>(q, kc, vc, out, pos, key_valid, workspace, B, nq, nkv, tmax, scale, s)
+                     : launch_split<float, 64>(q, kc, vc, out, pos, key_valid, workspace, B, nq, nkv, tmax, scale, s);
+}

@@ -340,7 +340,8 @@ class GreedyDecoder(_GraphDecoder):
     # 128, K / V heads read in place; fp32: the exactness kernel), RMSNorm(+residual), rotary + cache fill and SwiGLU through the
     # vtgb_llm_* kernels of the decode step -- no BLAS library call is left on the f2 path, in either dtype (round 4: the fp32 mode, whose
     # ids are compared token for token with HF generate, runs on libvtgb.so too; there grouped-query models repeat K / V heads).
-    # PREFILL_MAX_TOKENS = 0 forces the torch path.  Activation memory of the bf16 path: B * P x intermediate_size bf16 (+ twice that for
+    # PREFILL_MAX_TOKENS = 0 forces the torch path.  (The bound is the prefill's alone: the decode step's cache is P + max_new_tokens slots
+    # rounded up to 64, and which attention kernel serves it is decided by DECODE_SPLIT_MIN_KEYS below.)  Activation memory of the bf16 path: B * P x intermediate_size bf16 (+ twice that for
     # gate | up) -- 0.72 GB (+ 1.44 GB) at B = 16, P = 2048 of Vicuna-7B.
     PREFILL_MAX_TOKENS = 2048
     PREFILL_MAX_TOKENS_F32 = 1024
@@ -408,6 +409,18 @@ class GreedyDecoder(_GraphDecoder):
         """vtgb_gemm takes these projections: any shape at fp32; bf16 needs 8-aligned rows."""
         return dtype == torch.float32 or (self.cfg.hidden_size % 8 == 0 and self.inter % 8 == 0 and (self.nh * self.hd) % 8 == 0)
 
+    # Decode attention: caches of DECODE_SPLIT_MIN_KEYS slots and more (head_dim 64 / 128, up to 16384 slots) run on the split-KV kernel
+    # (vtgb_llm_decode_attention_split: 256-key chunks over workgroups, K/V read once per group of query heads), shorter ones on the
+    # one-wave-per-head kernel, which ends at 2048 slots.  The value (2112) is the routing rule's fallback -- the split kernel only where the
+    # other refuses -- until the two kernels are timed against each other (DESIGN.md section 4, "Split-KV decode attention"); from a lower
+    # value upward bf16 ids may differ from the other kernel's where two logits tie within a rounding (another summation order).  A cache
+    # neither kernel takes (more than 2048 slots at another head_dim, or more than 16384) decodes on the torch step.  The kernel is picked
+    # once per state, when its buffers are built (st["attn"]: "split", "single" or None), and the step follows the state.
+    DECODE_SPLIT_MIN_KEYS = ops.DECODE_SPLIT_MIN_KEYS
+
+    def _attn_route(self, tmax: int) -> Optional[str]:
+        return ops.decode_attention_route(tmax, self.hd, self.DECODE_SPLIT_MIN_KEYS)
+
     def _state(self, B: int, P: int, N: int, device, dtype, eos=None, pad=0, min_new=0, sample=None, stop=None, padded=False):
         # The cache length is bucketed (multiples of 64) and the true prompt length is device data (`pos`): an eval loop over real
         # questions with varying P reuses a handful of graphs instead of capturing one -- and allocating 2 x n_layers KV caches --
@@ -423,10 +436,13 @@ class GreedyDecoder(_GraphDecoder):
 
         def buffers():
             cos, sin = self._rope(tmax, device, dtype)
-            st = dict(cos=cos, sin=sin, tmax=tmax, kc=[z(B, self.nkv, tmax, self.hd) for _ in self.layers],
+            attn = self._attn_route(tmax) if device.type == "cuda" and self.fused else None
+            st = dict(cos=cos, sin=sin, tmax=tmax, attn=attn, kc=[z(B, self.nkv, tmax, self.hd) for _ in self.layers],
                       vc=[z(B, self.nkv, tmax, self.hd) for _ in self.layers], x=z(B, H), h=z(B, H), q=z(B, HD), a=z(B, HD), act=z(B, inter))
             if padded:      # key_valid[b, t]: cache slot t holds a real key of row b; rope_off[b]: rotary row - cache row of its decode steps
                 st.update(key_valid=torch.ones(B, tmax, dtype=torch.uint8, device=device), rope_off=z(B, dtype=torch.long))
+            if attn == "split":      # the split kernel's per-chunk partials
+                st.update(attn_ws=z(ops.decode_attention_workspace_bytes(B, self.nh, self.hd, tmax), dtype=torch.uint8))
             if device.type == "cuda" and self._use_skinny(B, dtype):
                 Hq, V = (self.nh + 2 * self.nkv) * self.hd, self.head_w.shape[0]
                 shapes = ((Hq, H), (H, HD), (2 * inter, H), (H, inter), (V, H))
@@ -473,11 +489,11 @@ class GreedyDecoder(_GraphDecoder):
                 L.check(lib.vtgb_llm_rmsnorm_parts(code, _ptr(x), _ptr(ws), delta_S, _ptr(wt), _ptr(h), B, H, self.eps, stream))
             else:
                 L.check(lib.vtgb_llm_rmsnorm(code, _ptr(x), _ptr(delta_t), _ptr(wt), _ptr(h), B, H, self.eps, stream))
-        # rotary + cache append and attention: vtgb_llm_rope_cache{,_parts}{,_pos} (_parts: q|k|v arrive as split-K fragments; _pos: a padded batch's
-        # per-row rotary offsets) and vtgb_llm_decode_attention{,_masked} take the same pointer lists apart from those extras
+        # rotary + cache append: vtgb_llm_rope_cache{,_parts}{,_pos} (_parts: q|k|v arrive as split-K fragments; _pos: a padded batch's per-row
+        # rotary offsets) take the same pointer lists apart from those extras.  Attention: ops.decode_attention, the kernel fixed by the state
+        # (its workspace exists exactly where the split kernel serves it)
         rope = (_ptr(st["cos"]), _ptr(st["sin"]), _ptr(st["pos"])) + ((_ptr(st["rope_off"]),) if padded else ())
-        attend = lib.vtgb_llm_decode_attention_masked if padded else lib.vtgb_llm_decode_attention
-        attend_pos = (_ptr(st["pos"]),) + ((_ptr(st["key_valid"]),) if padded else ())
+        attn_ws, key_valid = st.get("attn_ws"), st.get("key_valid")
         delta, dS = None, 1
         for li, (ln1, wqkv, wo, ln2, wgu, wd) in enumerate(self.layers):
             norm(delta, dS, ln1)
@@ -485,7 +501,8 @@ class GreedyDecoder(_GraphDecoder):
             kv = (_ptr(st["kc"][li]), _ptr(st["vc"][li]))
             rope_cache = getattr(lib, "vtgb_llm_rope_cache" + ("_parts" if qS > 1 else "") + ("_pos" if padded else ""))
             L.check(rope_cache(code, *((_ptr(ws), qS) if qS > 1 else (_ptr(qkv),)), _ptr(q), *kv, *rope, B, nq, nkv, hd, tmax, stream))
-            L.check(attend(code, _ptr(q), *kv, _ptr(a), *attend_pos, B, nq, nkv, hd, tmax, float(hd) ** -0.5, stream))
+            ops.decode_attention(q, st["kc"][li], st["vc"][li], st["pos"], float(hd) ** -0.5, key_valid=key_valid, out=a, workspace=attn_ws,
+                                 split=st["attn"] == "split")
             o, oS = lin_d(a, li, 1, "sk_o")
             norm(o, oS, ln2)
             gu = lin(h, li, 2, "sk_gu")
@@ -501,7 +518,7 @@ class GreedyDecoder(_GraphDecoder):
 
     def _decode_step(self, st):
         """One token for every sequence, entirely on the device (captured)."""
-        if self.fused and st["tok"].is_cuda:
+        if st["attn"] is not None:      # fused, on the device, and a kernel takes the cache
             return self._decode_step_fused(st)
         emb = self.lm.get_input_embeddings()
         x = emb(st["tok"])[:, None, :]

@@ -350,6 +350,64 @@ def attention_tiled(q: Tensor, k: Tensor, v: Tensor, heads: int, scale: float, k
     return out
 
 
+# ---- single-query attention of the decode step.  Two kernels: vtgb_llm_decode_attention{,_masked} (one wave per (row, head), every score in
+# LDS: caches up to 2048 slots, any head_dim <= 256) and vtgb_llm_decode_attention_split (256-key chunks over workgroups + a combine launch:
+# caches up to 16384 slots, head_dim 64 / 128, K/V read once per group of query heads).  DECODE_SPLIT_MIN_KEYS: the cache length from which
+# the split kernel is used where both apply.  2112 = only where the one-wave kernel refuses: the fallback of the routing rule, the two kernels
+# have not been timed against each other yet ("Split-KV decode attention").
+DECODE_SINGLE_MAX_KEYS = 2048
+DECODE_SPLIT_MAX_KEYS = 16384
+DECODE_SPLIT_CHUNK = 256
+DECODE_SPLIT_MIN_KEYS = 2112
+
+
+def decode_attention_route(tmax: int, hd: int, min_keys: Optional[int] = None) -> Optional[str]:
+    """The kernel a cache of ``tmax`` slots and head_dim ``hd`` decodes on: "split", "single", or None where neither takes it."""
+    min_keys = DECODE_SPLIT_MIN_KEYS if min_keys is None else min_keys
+    split_ok = hd in (64, 128) and tmax % 64 == 0 and tmax <= DECODE_SPLIT_MAX_KEYS
+    single_ok = tmax <= DECODE_SINGLE_MAX_KEYS and hd <= 256
+    if split_ok and (tmax >= min_keys or not single_ok):
+        return "split"
+    return "single" if single_ok else None
+
+
+def decode_attention_workspace_bytes(B: int, nq: int, hd: int, tmax: int) -> int:
+    return int(L.lib().vtgb_llm_decode_attention_split_workspace_bytes(B, nq, hd, tmax))
+
+
+def decode_attention(q: Tensor, kc: Tensor, vc: Tensor, pos: Tensor, scale: float, key_valid: Optional[Tensor] = None,
+                     out: Optional[Tensor] = None, workspace: Optional[Tensor] = None, split: Optional[bool] = None) -> Tensor:
+    """q [B, nq*hd], kc / vc [B, nkv, tmax, hd] (the static cache), pos: device int64 -> out [B, nq*hd] = softmax(scale q K[0..pos]^T) V[0..pos].
+    ``key_valid`` [B, tmax] uint8: keys with 0 get no weight.  The one place that picks the kernel: ``split=None`` follows
+    ``decode_attention_route``; True / False force one (False past 2048 keys raises what vtgb_llm_decode_attention raises).  The split
+    kernel's ``workspace`` (uint8, ``decode_attention_workspace_bytes``) is allocated here when None."""
+    _need_cuda(q, kc, vc, pos)
+    B, nkv, tmax, hd = kc.shape
+    nq = q.numel() // (B * hd)
+    assert kc.is_contiguous() and vc.is_contiguous() and q.is_contiguous() and vc.shape == kc.shape and q.dtype == kc.dtype == vc.dtype
+    assert pos.dtype == torch.int64 and (key_valid is None or (key_valid.dtype == torch.uint8 and key_valid.shape == (B, tmax) and key_valid.is_contiguous()))
+    if split is None:
+        route = decode_attention_route(tmax, hd)
+        split = route == "split" if route is not None else tmax > DECODE_SINGLE_MAX_KEYS      # (neither: the entry that refuses it names the reason)
+    code = dtype_code(q.dtype)
+    if out is None:
+        out = torch.empty(B, nq * hd, dtype=q.dtype, device=q.device)
+    lib = L.lib()
+    if split:
+        need = decode_attention_workspace_bytes(B, nq, hd, tmax)
+        if workspace is None:
+            workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)
+        assert workspace.numel() * workspace.element_size() >= need, "decode_attention: workspace too small"
+        L.check(lib.vtgb_llm_decode_attention_split(code, _ptr(q), _ptr(kc), _ptr(vc), _ptr(out), _ptr(pos), _ptr(key_valid), _ptr(workspace), B, nq, nkv,
+                                                    hd, tmax, float(scale), _stream()))
+    elif key_valid is not None:
+        L.check(lib.vtgb_llm_decode_attention_masked(code, _ptr(q), _ptr(kc), _ptr(vc), _ptr(out), _ptr(pos), _ptr(key_valid), B, nq, nkv, hd, tmax,
+                                                     float(scale), _stream()))
+    else:
+        L.check(lib.vtgb_llm_decode_attention(code, _ptr(q), _ptr(kc), _ptr(vc), _ptr(out), _ptr(pos), B, nq, nkv, hd, tmax, float(scale), _stream()))
+    return out
+
+
 def layernorm(x: Tensor, gamma: Tensor, beta: Tensor, eps: float, out_dtype=torch.float32) -> Tensor:
     _need_cuda(x, gamma, beta)
     x = x.contiguous().float()
