@@ -668,6 +668,47 @@ int vtgb_llm_decode_attention_split(int dtype, const void* q, const void* kc, co
                                     const uint8_t* key_valid /* NULL: none */, void* workspace, int32_t B, int32_t nq, int32_t nkv, int32_t hd,
                                     int32_t tmax, float scale, vtgb_stream_t stream);
 
+/* ---- fp8 K/V cache of the Llama decode step (opt-in: kv_cache = "fp8"; attn_decode.hip, llm.hip).  Every K row (after rotary) and every V
+ *   row -- one token of one K/V head, hd values -- is stored as OCP e4m3fn codes and one power-of-two scale:
+ *     uint8 kc8 / vc8 [B, nkv, tmax, hd]    float ks / vs [B, nkv, tmax]
+ *   scale = 2^e, e = the smallest integer with amax * 2^-e <= 448 (from the binary exponent; 0 for a zero row), clamped below at -100;
+ *   codes = row * 2^-e rounded to nearest even (ops.quantize_fp8_kv is the definition; the writers reproduce it bit for bit).  code * scale
+ *   is exactly a bf16 number: the mode is a bf16 model whose K/V pass through that rounding as they are produced.  Non-finite K/V are
+ *   outside the contract.  Activations are VTGB_BF16 (any other dtype: VTGB_EINVAL); hd 64 or 128 (VTGB_EUNSUPPORTED otherwise).
+ * vtgb_llm_decode_attention_split_fp8: vtgb_llm_decode_attention_split over that cache.  Same q / out layout, key_valid, visibility rules
+ *   (nothing past *pos is read, codes or scales; a masked or stale slot may hold anything, the e4m3 NaN code and NaN scales included),
+ *   workspace (vtgb_llm_decode_attention_split_workspace_bytes), pass 2, limits and error codes: VTGB_EINVAL for a NULL operand, a
+ *   non-positive size, nq % nkv != 0 or a dtype other than VTGB_BF16; VTGB_EUNSUPPORTED for hd outside {64, 128}, tmax not a multiple of
+ *   64 up to 16384, q / kc8 / vc8 / out / workspace not 16-byte or ks / vs not 4-byte aligned -- on the host, before any launch.
+ *   The output equals, BIT FOR BIT, vtgb_llm_decode_attention_split(VTGB_BF16) on the dequantised cache (kc = kc8 * ks, vc = vc8 * vs):
+ *   the same partition of every sum, the scales applied as exact power-of-two factors (to a row's score, to its softmax weight).
+ * vtgb_llm_rope_cache_fp8: the decode step's rotary + append (vtgb_llm_rope_cache and its _parts / _pos forms in one args struct).
+ *   q_out: the bits of the existing entries; the K row after rotary (rounded to bf16 as there) and the V row are quantised into row *pos
+ *   of kc8 / ks and vc8 / vs (*pos outside [0, tmax): no cache write).  Exactly one of qkv and part (VTGB_EINVAL otherwise).
+ * vtgb_llm_rope_cache_prefill_fp8: vtgb_llm_rope_cache_prefill{,_pos} (pos_ids NULL: the rotary row of position s is s): q and k rotated
+ *   in place, codes and scales of rows 0 .. S-1 written, and the DEQUANTISED k and v written back in place into qkv, so that the prefill
+ *   attention attends over the values the decode steps will read. */
+typedef struct {
+    int32_t dtype;                       /* VTGB_BF16 */
+    int32_t B, nq, nkv, hd, tmax;
+    int32_t n_splits;                    /* with `part`: > 1 */
+    const void* qkv;                     /* bf16 [B, (nq + 2 nkv) * hd], or NULL with `part` */
+    const float* part;                   /* the deferred K-split fragments of the q|k|v projection (vtgb_gemm_skinny, defer_reduce; B <= 128) */
+    void* q_out;                         /* bf16 [B, nq * hd] */
+    uint8_t* kc8; uint8_t* vc8;          /* [B, nkv, tmax, hd] */
+    float* ks; float* vs;                /* [B, nkv, tmax] */
+    const void* cos_t; const void* sin_t;/* bf16 [tmax, hd] */
+    const int64_t* pos;                  /* device: the cache row */
+    const int64_t* rope_off;             /* NULL, or [B]: the rotary row of batch entry b is *pos + rope_off[b] (padded batches) */
+} vtgb_llm_rope_cache_fp8_args;
+int vtgb_llm_rope_cache_fp8(const vtgb_llm_rope_cache_fp8_args* a, vtgb_stream_t stream);
+int vtgb_llm_rope_cache_prefill_fp8(int dtype, void* qkv, uint8_t* kc8, uint8_t* vc8, float* ks, float* vs, const void* cos_t, const void* sin_t,
+                                    const int64_t* pos_ids /* NULL: none */, int32_t B, int32_t S, int32_t nq, int32_t nkv, int32_t hd, int32_t tmax,
+                                    vtgb_stream_t stream);
+int vtgb_llm_decode_attention_split_fp8(int dtype, const void* q, const uint8_t* kc8, const uint8_t* vc8, const float* ks, const float* vs, void* out,
+                                        const int64_t* pos, const uint8_t* key_valid /* NULL: none */, void* workspace, int32_t B, int32_t nq,
+                                        int32_t nkv, int32_t hd, int32_t tmax, float scale, vtgb_stream_t stream);
+
 size_t vtgb_pack_skinny_weight_bytes(int32_t N, int32_t K);
 int vtgb_pack_skinny_weight(const void* w, int64_t ldw, int32_t N, int32_t K, void* dst, vtgb_stream_t stream);
 size_t vtgb_gemm_skinny_workspace_bytes(const vtgb_gemm_skinny_args* a);

@@ -44,6 +44,7 @@ EXPORTS = [
     "vtgb_gelu_forward", "vtgb_gelu_backward",
     "vtgb_pair_pack", "vtgb_pair_conv", "vtgb_pair_conv_ex", "vtgb_attention_tiled",
     "vtgb_llm_decode_attention_split_workspace_bytes", "vtgb_llm_decode_attention_split",
+    "vtgb_llm_decode_attention_split_fp8", "vtgb_llm_rope_cache_fp8", "vtgb_llm_rope_cache_prefill_fp8",
 ]
 COMM_ID_BYTES = 128
 
@@ -165,6 +166,12 @@ class GemmSkinnyArgs(C.Structure):
                 ("out_dtype", i32), ("w_tiled", i32), ("workspace", vp), ("workspace_bytes", sz), ("defer_reduce", i32)]
 
 
+class LlmRopeCacheFp8Args(C.Structure):
+    """vtgb_llm_rope_cache_fp8_args: the decode step's rotary + append into the fp8 K/V cache (exactly one of qkv / part)."""
+    _fields_ = [("dtype", i32), ("B", i32), ("nq", i32), ("nkv", i32), ("hd", i32), ("tmax", i32), ("n_splits", i32), ("qkv", vp), ("part", vp),
+                ("q_out", vp), ("kc8", vp), ("vc8", vp), ("ks", vp), ("vs", vp), ("cos_t", vp), ("sin_t", vp), ("pos", vp), ("rope_off", vp)]
+
+
 class GemmArgs(C.Structure):
     _fields_ = [("dtype", i32), ("M", i32), ("N", i32), ("K", i32), ("epilogue", i32), ("A", vp), ("lda", i64),
                 ("W", vp), ("ldw", i64), ("bias", vp), ("resid", vp), ("out", vp), ("ldo", i64)]
@@ -271,6 +278,12 @@ def lib() -> C.CDLL:
     L.vtgb_llm_decode_attention_split_workspace_bytes.restype = i64
     L.vtgb_llm_decode_attention_split.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]
     L.vtgb_llm_decode_attention_split.restype = C.c_int
+    L.vtgb_llm_decode_attention_split_fp8.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]
+    L.vtgb_llm_decode_attention_split_fp8.restype = C.c_int
+    L.vtgb_llm_rope_cache_fp8.argtypes = [C.POINTER(LlmRopeCacheFp8Args), vp]
+    L.vtgb_llm_rope_cache_fp8.restype = C.c_int
+    L.vtgb_llm_rope_cache_prefill_fp8.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    L.vtgb_llm_rope_cache_prefill_fp8.restype = C.c_int
     L.vtgb_gemm_skinny_splits.argtypes = [C.POINTER(GemmSkinnyArgs)]
     L.vtgb_gemm_skinny_splits.restype = i32
     L.vtgb_gemm_skinny.argtypes = [C.POINTER(GemmSkinnyArgs), vp]

@@ -22,6 +22,7 @@
 // heads share a workgroup (a head's arithmetic never sees another head's values).  An invisible key adds an exact +0.  So a row's output
 // is a function of (q, K/V[0..*pos], key_valid[0..*pos]): the same bits in any batch, any cache length, grouped or replicated K/V.
 #include "common.h"
+#include "fp8_code.h"
 
 #include <math.h>
 
@@ -250,4 +251,204 @@ extern "C" int vtgb_llm_decode_attention_split(int dtype, const void* q, const v
                          : launch_split<bf16_t, 64>(q, kc, vc, out, pos, key_valid, workspace, B, nq, nkv, tmax, scale, s);
     return hd == 128 ? launch_split<float, 128>(q, kc, vc, out, pos, key_valid, workspace, B, nq, nkv, tmax, scale, s)
                      : launch_split<float, 64>(q, kc, vc, out, pos, key_valid, workspace, B, nq, nkv, tmax, scale, s);
+}
+
+// ---- fp8 K/V cache (opt-in: kv_cache="fp8").  The cache of a layer is e4m3 codes kc8 / vc8 [B, nkv, tmax, hd] (uint8) and one power-of-two
+// scale per row ks / vs [B, nkv, tmax] (ops.quantize_fp8_kv; fp8_code.h), so code * scale is exactly a bf16 number and the cache is an
+// ordinary bf16 cache stored in half the bytes.  Pass 1 below is llm_decode_attn_split_kernel<bf16_t, HD, MASKED> reading that format; the
+// workspace and pass 2 are the ones above.
+// Contract: the output equals, bit for bit, what vtgb_llm_decode_attention_split returns on the dequantised cache.  The partition is the
+// bf16 instantiation's -- 8 consecutive elements of a row per lane (an 8-byte load here), LPR = hd / 8 lanes per row, the same rows per
+// lane, waves and chunks -- and a scale 2^e moves through every rounding unchanged (no overflow, no subnormal: |e| <= 120 and fp32
+// partial sums of bf16 products): sum_e fmaf(q, c 2^e, .) = 2^e sum_e fmaf(q, c, .), so the K scale multiplies the row's score after its
+// lanes are summed, and fmaf(p, c 2^e, acc) = fmaf(p 2^e, c, acc), so the V scale multiplies the softmax weight.  Both scales are read in
+// the softmax stage (four coalesced keys per lane), where the weights pass through LDS anyway.
+// Visibility is the bf16 kernel's: nothing past *pos is read -- codes or scales --, an invisible key's codes are replaced by zeros and its
+// scales by 1 before any product, so a stale or masked slot may hold anything (the e4m3 NaN code, a NaN scale).
+template <int HD, bool MASKED>
+__global__ __launch_bounds__(256) void llm_decode_attn_split_fp8_kernel(const bf16_t* __restrict__ q, const uint8_t* __restrict__ kc8,
+                                                                        const uint8_t* __restrict__ vc8, const float* __restrict__ ks,
+                                                                        const float* __restrict__ vs, float* __restrict__ ws,
+                                                                        const int64_t* __restrict__ pos_p, const uint8_t* __restrict__ key_valid,
+                                                                        int B, int nq, int nkv, int tmax, float scale) {
+    constexpr int EPL = 8;                        // elements per lane: as llm_decode_attn_split_kernel<bf16_t> (there 16 bytes, here 8)
+    constexpr int LPR = HD / EPL;                 // lanes per row
+    constexpr int RPI = 64 / LPR;                 // rows per load instruction
+    constexpr int NI = 64 / RPI;                  // load instructions per wave (== LPR)
+    __shared__ float qs[DEC_SPLIT_HEADS][HD];
+    __shared__ float sc[DEC_SPLIT_HEADS][DEC_SPLIT_CHUNK];
+    __shared__ __attribute__((aligned(16))) float red[4][DEC_SPLIT_HEADS][HD];
+
+    const int chunk = blockIdx.x, b = blockIdx.z;
+    const int pos = min((int)(*pos_p), tmax - 1);
+    if (chunk * DEC_SPLIT_CHUNK > pos) return;
+    const int group = nq / nkv, nhb = (group + DEC_SPLIT_HEADS - 1) / DEC_SPLIT_HEADS;
+    const int kvh = blockIdx.y / nhb, hb = blockIdx.y % nhb;
+    const int head0 = kvh * group + hb * DEC_SPLIT_HEADS, nh = min(DEC_SPLIT_HEADS, group - hb * DEC_SPLIT_HEADS);
+    const int nc = (tmax + DEC_SPLIT_CHUNK - 1) / DEC_SPLIT_CHUNK;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c = lane % LPR, rs = lane / LPR;      // this lane's 8-byte piece and row slot
+
+    for (int i = tid; i < nh * HD; i += 256) qs[i / HD][i % HD] = (float)q[((int64_t)b * nq + head0) * HD + i];
+
+    // ---- K: the wave's 64 rows of codes -> registers (row kl0 + i * RPI of instruction i); invisible rows stay zeros
+    const int kl0 = wave * 64 + rs, key0 = chunk * DEC_SPLIT_CHUNK + kl0;
+    const int64_t row0 = ((int64_t)b * nkv + kvh) * tmax;      // the (b, kvh) cache's first row: codes at row * HD, scales at row
+    const uint8_t* kvr = MASKED ? key_valid + (int64_t)b * tmax : nullptr;
+    unsigned vis = 0;
+#pragma unroll
+    for (int i = 0; i < NI; i++) {
+        const int key = key0 + i * RPI;
+        bool ok = key <= pos;
+        if (MASKED && ok) ok = kvr[key] != 0;
+        vis |= ok ? 1u << i : 0u;
+    }
+    // (as above: an invisible row's load goes to row *pos and its value is selected away)
+    auto load_rows = [&](const uint8_t* __restrict__ src, uint2 (&reg)[NI]) {
+#pragma unroll
+        for (int i = 0; i < NI; i++) {
+            const bool ok = vis >> i & 1;
+            const uint2 v = *reinterpret_cast<const uint2*>(src + (row0 + (ok ? key0 + i * RPI : pos)) * HD + c * EPL);
+            reg[i] = ok ? v : make_uint2(0u, 0u);
+        }
+    };
+    uint2 reg[NI];
+    load_rows(kc8, reg);
+    __syncthreads();      // qs
+
+    // ---- unscaled scores q . codes: per head, the lane's piece of every row, then the row's LPR lanes
+    for (int h = 0; h < nh; h++) {
+        float qv[EPL];
+#pragma unroll
+        for (int e = 0; e < EPL; e++) qv[e] = qs[h][c * EPL + e];
+#pragma unroll
+        for (int i = 0; i < NI; i++) {
+            float lo[4], hi[4];
+            kv8_widen4(reg[i].x, lo);
+            kv8_widen4(reg[i].y, hi);
+            float dot = 0.f;
+#pragma unroll
+            for (int e = 0; e < 4; e++) dot = fmaf(qv[e], lo[e], dot);
+#pragma unroll
+            for (int e = 0; e < 4; e++) dot = fmaf(qv[4 + e], hi[e], dot);
+            dot = group_sum<LPR>(dot);
+            if (c == 0) sc[h][kl0 + i * RPI] = (vis >> i & 1) ? dot : -INFINITY;
+        }
+    }
+    // ---- V replaces K in the registers (the loads fly behind the softmax)
+    load_rows(vc8, reg);
+    __syncthreads();      // sc
+
+    // ---- softmax statistics of the chunk: wave w takes the heads w, w + 4.  A lane's four keys lane + 64 j: their K scale makes the
+    // score (dot * 2^ek) * scale = the bf16 kernel's dot * scale, their V scale goes into the weight left in sc
+    if (wave < nh) {
+        float sk[4], sv[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int key = chunk * DEC_SPLIT_CHUNK + lane + 64 * j;
+            bool ok = key <= pos;
+            if (MASKED && ok) ok = kvr[key] != 0;
+            const float a = ks[row0 + (ok ? key : pos)], v = vs[row0 + (ok ? key : pos)];
+            sk[j] = ok ? a : 1.f;
+            sv[j] = ok ? v : 1.f;
+        }
+        for (int h = wave; h < nh; h += 4) {
+            float s[4], m = -INFINITY;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const float d = sc[h][lane + 64 * j];
+                s[j] = d == -INFINITY ? d : (d * sk[j]) * scale;
+                m = fmaxf(m, s[j]);
+            }
+            for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                s[j] = s[j] == -INFINITY ? 0.f : expf(s[j] - m);      // (an invisible key: exactly 0, also when the chunk has no visible key)
+                sc[h][lane + 64 * j] = s[j] * sv[j];
+            }
+            const float l = group_sum<64>((s[0] + s[1]) + (s[2] + s[3]));
+            if (lane == 0) {
+                float* ml = ws + (int64_t)B * nq * nc * HD + (((int64_t)b * nq + head0 + h) * nc + chunk) * 2;
+                ml[0] = m;
+                ml[1] = l;
+            }
+        }
+    }
+    __syncthreads();      // sc = weights x V scales
+
+    // ---- O: per head, the lane's rows in ascending order, then the wave's row slots, then (below) the four waves
+    for (int h = 0; h < nh; h++) {
+        float acc[EPL];
+#pragma unroll
+        for (int e = 0; e < EPL; e++) acc[e] = 0.f;
+#pragma unroll
+        for (int i = 0; i < NI; i++) {
+            const float p = sc[h][kl0 + i * RPI];
+            float lo[4], hi[4];
+            kv8_widen4(reg[i].x, lo);
+            kv8_widen4(reg[i].y, hi);
+#pragma unroll
+            for (int e = 0; e < 4; e++) acc[e] = fmaf(p, lo[e], acc[e]);
+#pragma unroll
+            for (int e = 0; e < 4; e++) acc[4 + e] = fmaf(p, hi[e], acc[4 + e]);
+        }
+#pragma unroll
+        for (int e = 0; e < EPL; e++) {
+            float v = acc[e];
+            if constexpr (RPI > 1) v += __shfl_xor(v, LPR);
+            if constexpr (RPI > 2) v += __shfl_xor(v, 2 * LPR);
+            if constexpr (RPI > 4) v += __shfl_xor(v, 4 * LPR);
+            acc[e] = v;
+        }
+        if (rs == 0) {
+#pragma unroll
+            for (int e = 0; e < EPL; e += 4)
+                *reinterpret_cast<f32x4*>(&red[wave][h][c * EPL + e]) = f32x4{acc[e], acc[e + 1], acc[e + 2], acc[e + 3]};
+        }
+    }
+    __syncthreads();      // red
+    for (int i = tid; i < nh * HD; i += 256) {
+        const int h = i / HD, d = i % HD;
+        ws[(((int64_t)b * nq + head0 + h) * nc + chunk) * HD + d] = ((red[0][h][d] + red[1][h][d]) + red[2][h][d]) + red[3][h][d];
+    }
+}
+
+template <int HD>
+static int launch_split_fp8(const void* q, const uint8_t* kc8, const uint8_t* vc8, const float* ks, const float* vs, void* out, const int64_t* pos,
+                            const uint8_t* key_valid, void* workspace, int B, int nq, int nkv, int tmax, float scale, hipStream_t s) {
+    const int group = nq / nkv, nhb = (group + DEC_SPLIT_HEADS - 1) / DEC_SPLIT_HEADS, nc = (tmax + DEC_SPLIT_CHUNK - 1) / DEC_SPLIT_CHUNK;
+    const dim3 grid(nc, nkv * nhb, B);
+    float* ws = (float*)workspace;
+    if (key_valid)
+        hipLaunchKernelGGL((llm_decode_attn_split_fp8_kernel<HD, true>), grid, dim3(256), 0, s, (const bf16_t*)q, kc8, vc8, ks, vs, ws, pos, key_valid, B, nq,
+                           nkv, tmax, scale);
+    else
+        hipLaunchKernelGGL((llm_decode_attn_split_fp8_kernel<HD, false>), grid, dim3(256), 0, s, (const bf16_t*)q, kc8, vc8, ks, vs, ws, pos,
+                           (const uint8_t*)nullptr, B, nq, nkv, tmax, scale);
+    VTGB_HIP(hipGetLastError());
+    hipLaunchKernelGGL(llm_decode_attn_combine_kernel<bf16_t>, dim3((unsigned)((int64_t)B * nq)), dim3(HD), 0, s, (const float*)ws, (bf16_t*)out, pos,
+                       (int64_t)B * nq, HD, tmax);
+    VTGB_HIP(hipGetLastError());
+    return VTGB_OK;
+}
+
+extern "C" int vtgb_llm_decode_attention_split_fp8(int dtype, const void* q, const uint8_t* kc8, const uint8_t* vc8, const float* ks, const float* vs,
+                                                   void* out, const int64_t* pos, const uint8_t* key_valid, void* workspace, int32_t B, int32_t nq,
+                                                   int32_t nkv, int32_t hd, int32_t tmax, float scale, vtgb_stream_t stream) {
+    VTGB_REQUIRE(q && kc8 && vc8 && ks && vs && out && pos && workspace, VTGB_EINVAL, "llm_decode_attention_split_fp8: NULL operand");
+    VTGB_REQUIRE(dtype == VTGB_BF16 && B > 0 && nq > 0 && nkv > 0 && tmax > 0, VTGB_EINVAL,
+                 "llm_decode_attention_split_fp8: bad argument (activations are VTGB_BF16)");
+    VTGB_REQUIRE(nq % nkv == 0, VTGB_EINVAL, "llm_decode_attention_split_fp8: nq=%d is not a multiple of nkv=%d", nq, nkv);
+    VTGB_REQUIRE(hd == 64 || hd == 128, VTGB_EUNSUPPORTED, "llm_decode_attention_split_fp8: hd=%d, built for 64 and 128", hd);
+    VTGB_REQUIRE(tmax % 64 == 0 && tmax <= DEC_SPLIT_MAX_T, VTGB_EUNSUPPORTED,
+                 "llm_decode_attention_split_fp8: tmax=%d is not a multiple of 64 up to %d", tmax, DEC_SPLIT_MAX_T);
+    const int nhb = (nq / nkv + DEC_SPLIT_HEADS - 1) / DEC_SPLIT_HEADS;
+    VTGB_REQUIRE(B <= 65535 && (int64_t)nkv * nhb <= 65535, VTGB_EUNSUPPORTED, "llm_decode_attention_split_fp8: B=%d / nq=%d exceed the grid", B, nq);
+    const auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
+    VTGB_REQUIRE(!misaligned(q, 16) && !misaligned(kc8, 16) && !misaligned(vc8, 16) && !misaligned(out, 16) && !misaligned(workspace, 16) &&
+                     !misaligned(ks, 4) && !misaligned(vs, 4),
+                 VTGB_EUNSUPPORTED, "llm_decode_attention_split_fp8: q / kc8 / vc8 / out / workspace need 16-byte, ks / vs 4-byte alignment");
+    hipStream_t s = (hipStream_t)stream;
+    return hd == 128 ? launch_split_fp8<128>(q, kc8, vc8, ks, vs, out, pos, key_valid, workspace, B, nq, nkv, tmax, scale, s)
+                     : launch_split_fp8<64>(q, kc8, vc8, ks, vs, out, pos, key_valid, workspace, B, nq, nkv, tmax, scale, s);
 }

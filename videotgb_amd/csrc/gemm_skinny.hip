@@ -1,5 +1,6 @@
 // gemm_skinny.hip -- the decode step's projections: one weight-streaming kernel, two weight streams (bf16, and e4m3 codes with a row scale).
 #include "common.h"
+#include "fp8_code.h"
 
 #include <math.h>
 
@@ -326,27 +327,6 @@ extern "C" int vtgb_pack_skinny_weight(const void* w, int64_t ldw, int32_t N, in
     hipLaunchKernelGGL(skinny_pack_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, (const bf16_t*)w, ldw, N, K / SK_BK, (bf16_t*)dst, chunks);
     VTGB_HIP(hipGetLastError());
     return VTGB_OK;
-}
-
-// The fp8 quantisation recipe (ops.quantize_fp8_rows states it for the host).  e: the smallest integer with amax 2^-e <= 448 = 0.875 x 2^9,
-// exactly, from the binary exponent (no log2); 0 for a zero row.
-__host__ __device__ inline int sk8_row_exp(float amax) {
-    if (!(amax > 0.f)) return 0;
-    int ex;
-    const float m = frexpf(amax, &ex);                         // amax = m 2^ex, 0.5 <= m < 1
-    return ex - 9 + (m > 0.875f ? 1 : 0);
-}
-
-// v (|v| <= 448) rounded to nearest even into an OCP e4m3fn code, on the bits: normal codes keep 3 mantissa bits; below 2^-6 the code is
-// the integer round(|v| 2^9) (subnormals, 8 = the smallest normal)
-__host__ __device__ inline uint8_t sk8_code(float v) {
-    union { float f; uint32_t u; } c;
-    c.f = v;
-    const uint32_t sign = (c.u >> 24) & 0x80u;
-    c.u &= 0x7FFFFFFFu;
-    if (c.f < 0.015625f) return (uint8_t)(sign | (uint32_t)rintf(c.f * 512.f));
-    c.u += 0x7FFFFu + ((c.u >> 20) & 1u);
-    return (uint8_t)(sign | ((((c.u >> 23) - 120u) << 3) | ((c.u >> 20) & 7u)));
 }
 
 // scale[n] = 2^e[n]: one wave per weight row

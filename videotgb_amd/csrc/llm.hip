@@ -729,3 +729,161 @@ extern "C" int vtgb_llm_gated_act(int dtype, const void* gu, void* act, int64_t 
     VTGB_HIP(hipGetLastError());
     return VTGB_OK;
 }
+
+// ---- fp8 K/V cache (opt-in: kv_cache="fp8"; attn_decode.hip reads it).  The writers: rotary + append of the decode step and rotary +
+// cache fill of the prefill, with the row quantisation of ops.quantize_fp8_kv (fp8_code.h: e from the row's amax, clamped at -100, codes =
+// row * 2^-e rounded to nearest even) reproduced bit for bit.  One WAVE per head row (one token of one head), so the row's amax is a
+// wave reduction: no atomics, no LDS.  A lane holds the channel pair (d, d + hd / 2), d = lane < hd / 2 -- rotary partners, so the
+// arithmetic is rope_cache_body's / rope_cache_prefill_body's with both operands in registers (hd <= 128: one pair per lane).
+#include "fp8_code.h"
+
+// largest |value| of the wave's row: every lane ends with it
+__device__ __forceinline__ float kv8_wave_amax(float a, float b) {
+    float m = fmaxf(fabsf(a), fabsf(b));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    return m;
+}
+
+// the value an e4m3 code stands for (exact)
+__device__ __forceinline__ float kv8_value(uint8_t code) {
+    float o[4];
+    kv8_widen4(code, o);
+    return o[0];
+}
+
+// Decode step: grid (ceil((nq + 2 nkv) / 4), B), 4 waves = 4 head rows per workgroup.  q heads: q_out as vtgb_llm_rope_cache writes it;
+// k heads: rotary, rounded to bf16, quantised into row *pos of kc8 / ks; v heads: quantised into row *pos of vc8 / vs.
+__global__ __launch_bounds__(256) void llm_rope_cache_fp8_kernel(const vtgb_llm_rope_cache_fp8_args a) {
+#pragma clang fp contract(off)      // (rope_cache_body's three roundings, no FMA)
+    const int nq = a.nq, nkv = a.nkv, hd = a.hd, half = hd >> 1;
+    const int b = blockIdx.y, head = blockIdx.x * 4 + (threadIdx.x >> 6), d = threadIdx.x & 63;
+    if (head >= nq + 2 * nkv) return;      // (whole waves)
+    const int64_t pos = *a.pos;
+    int64_t rp = pos;
+    if (a.rope_off) rp += a.rope_off[b];
+    rp = rp < 0 ? 0 : rp >= a.tmax ? a.tmax - 1 : rp;      // (the tables have tmax rows; the decoder keeps rp in [0, pos])
+    const bf16_t* src = a.qkv ? (const bf16_t*)a.qkv + ((int64_t)b * (nq + 2 * nkv) + head) * hd : nullptr;
+    const float* part = a.part;
+    const int S = a.n_splits, M = a.B;
+    auto at = [&](int dd) -> float {      // (rope_cache_body's: the value, or the fragments' sum in split order rounded once)
+        if (!part) return (float)src[dd];
+        const int col = head * hd + dd;
+        float t = 0.f;
+        for (int sp = 0; sp < S; sp++) t += part[((int64_t)((col >> 7) * S + sp) * M + b) * 128 + (col & 127)];
+        return Cvt<bf16_t>::rnd(t);
+    };
+    const bool active = d < half;
+    float o0 = 0.f, o1 = 0.f;
+    if (active) {
+        const float x0 = at(d), x1 = at(d + half);
+        o0 = x0, o1 = x1;
+        if (head < nq + nkv) {
+            const bf16_t* cr = (const bf16_t*)a.cos_t + rp * hd;
+            const bf16_t* sr = (const bf16_t*)a.sin_t + rp * hd;
+            const float c0 = (float)cr[d], s0 = (float)sr[d], c1 = (float)cr[d + half], s1 = (float)sr[d + half];
+            const float p00 = Cvt<bf16_t>::rnd(x0 * c0), p01 = Cvt<bf16_t>::rnd(-x1 * s0);
+            const float p10 = Cvt<bf16_t>::rnd(x1 * c1), p11 = Cvt<bf16_t>::rnd(x0 * s1);
+            o0 = Cvt<bf16_t>::rnd(p00 + p01);
+            o1 = Cvt<bf16_t>::rnd(p10 + p11);
+        }
+    }
+    if (head < nq) {
+        if (active) {
+            bf16_t* qo = (bf16_t*)a.q_out + ((int64_t)b * nq + head) * hd;
+            qo[d] = (bf16_t)o0;
+            qo[d + half] = (bf16_t)o1;
+        }
+        return;
+    }
+    if (pos < 0 || pos >= a.tmax) return;      // (no cache row to write)
+    const bool isk = head < nq + nkv;
+    const int64_t row = ((int64_t)b * nkv + (isk ? head - nq : head - nq - nkv)) * a.tmax + pos;
+    const int e = kv8_row_exp(kv8_wave_amax(o0, o1));
+    if (active) {
+        uint8_t* c8 = (isk ? a.kc8 : a.vc8) + row * hd;
+        c8[d] = sk8_code(ldexpf(o0, -e));
+        c8[d + half] = sk8_code(ldexpf(o1, -e));
+    }
+    if (d == 0) (isk ? a.ks : a.vs)[row] = ldexpf(1.f, e);
+}
+
+// Prefill: grid (S, B), 4 waves; wave w takes the head rows w, w + 4 ... of its position.  q and k rotated in place in qkv as
+// vtgb_llm_rope_cache_prefill{,_pos} does; codes and scales of k and v into the cache rows 0 .. S - 1; and the DEQUANTISED k and v written
+// back in place, so that the prefill attention (unchanged kernels) attends over the values every later step reads from the cache.
+__global__ __launch_bounds__(256) void llm_rope_cache_prefill_fp8_kernel(bf16_t* __restrict__ qkv, uint8_t* __restrict__ kc8, uint8_t* __restrict__ vc8,
+                                                                         float* __restrict__ ks, float* __restrict__ vs, const bf16_t* __restrict__ cos_t,
+                                                                         const bf16_t* __restrict__ sin_t, const int64_t* __restrict__ pos_ids, int S, int nq,
+                                                                         int nkv, int hd, int tmax) {
+#pragma clang fp contract(off)
+    const int spos = blockIdx.x, b = blockIdx.y, half = hd >> 1, d = threadIdx.x & 63;
+    bf16_t* const row = qkv + ((int64_t)b * S + spos) * (nq + 2 * nkv) * hd;
+    int64_t rp = spos;
+    if (pos_ids) {
+        rp = pos_ids[(int64_t)b * S + spos];
+        rp = rp < 0 ? 0 : rp >= tmax ? tmax - 1 : rp;
+    }
+    const bf16_t* const cr = cos_t + rp * hd;
+    const bf16_t* const sr = sin_t + rp * hd;
+    const bool active = d < half;
+    for (int head = threadIdx.x >> 6; head < nq + 2 * nkv; head += 4) {
+        bf16_t* const hp = row + head * hd;
+        float o0 = 0.f, o1 = 0.f;
+        if (active) {
+            const float x0 = (float)hp[d], x1 = (float)hp[d + half];
+            o0 = x0, o1 = x1;
+            if (head < nq + nkv) {
+                const float c0 = (float)cr[d], s0 = (float)sr[d], c1 = (float)cr[d + half], s1 = (float)sr[d + half];
+                const float p00 = Cvt<bf16_t>::rnd(x0 * c0), p01 = Cvt<bf16_t>::rnd(-x1 * s0);
+                const float p10 = Cvt<bf16_t>::rnd(x1 * c1), p11 = Cvt<bf16_t>::rnd(x0 * s1);
+                o0 = Cvt<bf16_t>::rnd(p00 + p01);
+                o1 = Cvt<bf16_t>::rnd(p10 + p11);
+            }
+        }
+        if (head >= nq) {
+            const bool isk = head < nq + nkv;
+            const int64_t crow = ((int64_t)b * nkv + (isk ? head - nq : head - nq - nkv)) * tmax + spos;
+            const int e = kv8_row_exp(kv8_wave_amax(o0, o1));
+            const float sc = ldexpf(1.f, e);
+            if (active) {
+                const uint8_t q0 = sk8_code(ldexpf(o0, -e)), q1 = sk8_code(ldexpf(o1, -e));
+                uint8_t* c8 = (isk ? kc8 : vc8) + crow * hd;
+                c8[d] = q0;
+                c8[d + half] = q1;
+                o0 = kv8_value(q0) * sc;      // (exact: a bf16 number)
+                o1 = kv8_value(q1) * sc;
+            }
+            if (d == 0) (isk ? ks : vs)[crow] = sc;
+        }
+        if (active) {
+            hp[d] = (bf16_t)o0;
+            hp[d + half] = (bf16_t)o1;
+        }
+    }
+}
+
+extern "C" int vtgb_llm_rope_cache_fp8(const vtgb_llm_rope_cache_fp8_args* a, vtgb_stream_t s) {
+    VTGB_REQUIRE(a, VTGB_EINVAL, "llm_rope_cache_fp8: NULL args");
+    VTGB_REQUIRE(a->q_out && a->kc8 && a->vc8 && a->ks && a->vs && a->cos_t && a->sin_t && a->pos, VTGB_EINVAL, "llm_rope_cache_fp8: NULL operand");
+    VTGB_REQUIRE((a->qkv != nullptr) != (a->part != nullptr), VTGB_EINVAL, "llm_rope_cache_fp8: exactly one of qkv and part");
+    VTGB_REQUIRE(!a->part || (a->n_splits > 1 && a->B <= 128), VTGB_EINVAL, "llm_rope_cache_fp8: part needs n_splits > 1 and B <= 128");
+    VTGB_REQUIRE(a->dtype == VTGB_BF16 && a->B > 0 && a->B <= 65535 && a->nq > 0 && a->nkv > 0 && a->tmax > 0, VTGB_EINVAL,
+                 "llm_rope_cache_fp8: bad argument (activations are VTGB_BF16)");
+    VTGB_REQUIRE(a->hd == 64 || a->hd == 128, VTGB_EUNSUPPORTED, "llm_rope_cache_fp8: hd=%d, built for 64 and 128", a->hd);
+    hipLaunchKernelGGL(llm_rope_cache_fp8_kernel, dim3((a->nq + 2 * a->nkv + 3) / 4, a->B), dim3(256), 0, (hipStream_t)s, *a);
+    VTGB_HIP(hipGetLastError());
+    return VTGB_OK;
+}
+
+extern "C" int vtgb_llm_rope_cache_prefill_fp8(int dtype, void* qkv, uint8_t* kc8, uint8_t* vc8, float* ks, float* vs, const void* cos_t,
+                                               const void* sin_t, const int64_t* pos_ids, int32_t B, int32_t S, int32_t nq, int32_t nkv, int32_t hd,
+                                               int32_t tmax, vtgb_stream_t s) {
+    VTGB_REQUIRE(qkv && kc8 && vc8 && ks && vs && cos_t && sin_t, VTGB_EINVAL, "llm_rope_cache_prefill_fp8: NULL operand");
+    VTGB_REQUIRE(dtype == VTGB_BF16 && B > 0 && B <= 65535 && S > 0 && S <= tmax && nq > 0 && nkv > 0, VTGB_EINVAL,
+                 "llm_rope_cache_prefill_fp8: bad argument (activations are VTGB_BF16)");
+    VTGB_REQUIRE(hd == 64 || hd == 128, VTGB_EUNSUPPORTED, "llm_rope_cache_prefill_fp8: hd=%d, built for 64 and 128", hd);
+    hipLaunchKernelGGL(llm_rope_cache_prefill_fp8_kernel, dim3(S, B), dim3(256), 0, (hipStream_t)s, (bf16_t*)qkv, kc8, vc8, ks, vs, (const bf16_t*)cos_t,
+                       (const bf16_t*)sin_t, pos_ids, S, nq, nkv, hd, tmax);
+    VTGB_HIP(hipGetLastError());
+    return VTGB_OK;
+}

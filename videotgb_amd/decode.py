@@ -66,6 +66,16 @@ def check_decode_weights(weights) -> str:
     return weights
 
 
+KV_CACHE = ("bf16", "fp8")
+
+
+def check_kv_cache(kv_cache) -> str:
+    """The K/V cache mode as the decoders take it: "bf16" (the model's own K/V) or "fp8" (Llama: per-row e4m3 K/V cache); ValueError otherwise."""
+    if kv_cache not in KV_CACHE:
+        raise ValueError(f"kv_cache must be one of {KV_CACHE}, got {kv_cache!r}")
+    return kv_cache
+
+
 def weights_key(lm):
     """(in-place version, storage address) of every parameter: the decoders hold re-packed COPIES of the language model's weights
     (concatenated q|k|v, tiled decode weights, captured graphs), so an optimizer step, a load_state_dict or a `.data` swap on
@@ -92,8 +102,9 @@ class _GraphDecoder:
     MAX_STATES = 4
     FEEDBACK = ("tok", "pos", "step", "out", "fin", "len")      # what one step writes besides the model's caches
 
-    def __init__(self, lm, fused: bool, weights: str = "bf16"):
+    def __init__(self, lm, fused: bool, weights: str = "bf16", kv_cache: str = "bf16"):
         self.lm, self.cfg, self.fused, self.weights = lm, lm.config, fused, check_decode_weights(weights)
+        self.kv_cache = check_kv_cache(kv_cache)
         self.key = weights_key(lm)
         self.graphs: Dict[tuple, dict] = {}
 
@@ -254,14 +265,24 @@ class GreedyDecoder(_GraphDecoder):
     (ops.quantize_fp8_rows) and the decode step streams those codes (ops.SkinnyWeightFp8: half the bytes per token).  ``self.layers`` / ``self.head_w``
     -- what the prefill, batches beyond the skinny kernel and the torch path multiply by -- then hold the DEQUANTISED weights, which are exactly bf16
     numbers, so every path decodes the same model: an ordinary Llama whose projection weights are q * scale.  Embeddings and norms are the
-    model's own.  The fused path takes a bf16 model; the torch path (``fused=False``) also an fp32 one, quantised from its bf16 cast."""
+    model's own.  The fused path takes a bf16 model; the torch path (``fused=False``) also an fp32 one, quantised from its bf16 cast.
 
-    def __init__(self, lm, fused: bool = True, weights: str = "bf16"):
+    ``kv_cache="fp8"`` (opt-in, orthogonal to ``weights``): every K row (after rotary) and every V row -- one token of one K/V head -- is rounded
+    once, as it is produced, to e4m3 codes with a power-of-two row scale (ops.quantize_fp8_kv), and the prefill attention, every decode step and
+    every fallback attend over the dequantised values, which are exactly bf16 numbers: the mode is an ordinary bf16 Llama whose K/V pass
+    through ``ops.fp8_kv_round``.  On the device, fused, with a cache the split-KV kernel takes (head_dim 64 / 128, up to 16384 slots) the state
+    holds the codes and scales (half the bytes: ``st["attn"] == "split_fp8"``, vtgb_llm_rope_cache{,_prefill}_fp8 +
+    vtgb_llm_decode_attention_split_fp8); otherwise it keeps bf16 caches of dequantised values and decodes on the torch step (``_layer`` states
+    the model; no memory is saved).  The fused path takes a bf16 model; the torch path also an fp32 one."""
+
+    def __init__(self, lm, fused: bool = True, weights: str = "bf16", kv_cache: str = "bf16"):
         cfg = lm.config
         if "llama" not in cfg.model_type:
             raise NotImplementedError("GreedyDecoder handles Llama-architecture models; use HF generate otherwise")
-        super().__init__(lm, fused, weights)
+        super().__init__(lm, fused, weights, kv_cache)
         wdt = lm.lm_head.weight.dtype
+        if self.kv_cache == "fp8" and wdt != torch.bfloat16 and (fused or wdt != torch.float32):
+            raise ValueError(f"kv_cache='fp8' needs a bf16 language model, got {wdt}")
         if self.weights == "fp8" and wdt != torch.bfloat16 and (fused or wdt != torch.float32):
             raise ValueError(f"decode_weights='fp8' needs a bf16 language model, got {wdt}")
 
@@ -311,9 +332,11 @@ class GreedyDecoder(_GraphDecoder):
         emb = torch.cat((fr, fr), dim=-1)
         return emb.cos().to(dtype), emb.sin().to(dtype)
 
-    def _layer(self, x, w, cos, sin, kc, vc, pos_idx, mask):
+    def _layer(self, x, w, cos, sin, kc, vc, pos_idx, mask, codes=None):
         """x [B, S, H]; cos/sin [S, hd] (padded batches: [B, 1, S, hd], per-row positions); kc/vc [B, nkv, Tmax, hd]; pos_idx [S] cache rows
-        to write; mask additive, broadcast to [B, 1, S, Tmax]."""
+        to write; mask additive, broadcast to [B, 1, S, Tmax].  kv_cache="fp8": k and v pass through dq(q(.)) before the cache write and
+        the attention -- the kernel-independent statement of the model.  ``codes`` = (kc8, vc8, ks, vs) of an fp8 state (prefill only,
+        pos_idx = 0 .. S-1; kc / vc None): codes and scales go to the cache and the attention runs over the prompt's own dequantised K/V."""
         ln1, wqkv, wo, ln2, wgu, wd = w
         B, S, _ = x.shape
         nq, nkv, hd = self.nh, self.nkv, self.hd
@@ -322,12 +345,24 @@ class GreedyDecoder(_GraphDecoder):
         qk = qkv[:, : nq + nkv]
         qk = qk * cos + _rot_half(qk) * sin                                        # rotary on q and k together
         q, k, v = qk[:, :nq], qk[:, nq:], qkv[:, nq + nkv:]
-        kc.index_copy_(2, pos_idx, k)
-        vc.index_copy_(2, pos_idx, v)
-        kk, vv = kc, vc
+        if codes is not None:
+            kc8, vc8, ks, vs = codes
+            (qk8, sk), (qv8, sv) = ops.quantize_fp8_kv(k), ops.quantize_fp8_kv(v)
+            kc8.index_copy_(2, pos_idx, qk8.view(torch.uint8))
+            vc8.index_copy_(2, pos_idx, qv8.view(torch.uint8))
+            ks.index_copy_(2, pos_idx, sk)
+            vs.index_copy_(2, pos_idx, sv)
+            kk, vv = ops.dequantize_fp8_kv(qk8, sk, k.dtype), ops.dequantize_fp8_kv(qv8, sv, v.dtype)
+            mask = mask[..., :S]
+        else:
+            if self.kv_cache == "fp8":
+                k, v = ops.fp8_kv_round(k), ops.fp8_kv_round(v)
+            kc.index_copy_(2, pos_idx, k)
+            vc.index_copy_(2, pos_idx, v)
+            kk, vv = kc, vc
         if nkv != nq:
             rep = nq // nkv
-            kk, vv = kc.repeat_interleave(rep, 1), vc.repeat_interleave(rep, 1)
+            kk, vv = kk.repeat_interleave(rep, 1), vv.repeat_interleave(rep, 1)
         a = F.scaled_dot_product_attention(q, kk, vv, attn_mask=mask)
         x = x + F.linear(a.transpose(1, 2).reshape(B, S, nq * hd), wo)
         h = _rms(x, ln2, self.eps)
@@ -378,11 +413,16 @@ class GreedyDecoder(_GraphDecoder):
             L.check(lib.vtgb_llm_rmsnorm(code, _ptr(x), _ptr(delta), _ptr(ln1), _ptr(h), M, H, self.eps, stream))
             qkv = ops.gemm(h, wqkv).view(B, P, nh + 2 * nkv, hd)
             # rotary on q and k in place + k / v into the cache rows 0 .. P-1: one launch (HF's roundings in the model's dtype)
-            cache = (_ptr(qkv), _ptr(st["kc"][li]), _ptr(st["vc"][li]), _ptr(st["cos"]), _ptr(st["sin"]))
-            if pos_ids is None:
-                L.check(lib.vtgb_llm_rope_cache_prefill(code, *cache, B, P, nh, nkv, hd, st["tmax"], stream))
+            if st["attn"] == "split_fp8":      # codes + scales into the cache, the dequantised k / v back into qkv for the attention below
+                L.check(lib.vtgb_llm_rope_cache_prefill_fp8(code, _ptr(qkv), _ptr(st["kc8"][li]), _ptr(st["vc8"][li]), _ptr(st["ks"][li]),
+                                                            _ptr(st["vs"][li]), _ptr(st["cos"]), _ptr(st["sin"]), _ptr(pos_ids), B, P, nh, nkv, hd,
+                                                            st["tmax"], stream))
             else:
-                L.check(lib.vtgb_llm_rope_cache_prefill_pos(code, *cache, _ptr(pos_ids), B, P, nh, nkv, hd, st["tmax"], stream))
+                cache = (_ptr(qkv), _ptr(st["kc"][li]), _ptr(st["vc"][li]), _ptr(st["cos"]), _ptr(st["sin"]))
+                if pos_ids is None:
+                    L.check(lib.vtgb_llm_rope_cache_prefill(code, *cache, B, P, nh, nkv, hd, st["tmax"], stream))
+                else:
+                    L.check(lib.vtgb_llm_rope_cache_prefill_pos(code, *cache, _ptr(pos_ids), B, P, nh, nkv, hd, st["tmax"], stream))
             flat = qkv.view(B, P, (nh + 2 * nkv) * hd)
             q_, k_, v_ = flat[:, :, : nh * hd], flat[:, :, nh * hd: (nh + nkv) * hd], flat[:, :, (nh + nkv) * hd:]
             if nkv != nh and x.dtype != torch.bfloat16:      # fp32, grouped-query attention: every K / V head serves nh / nkv query heads (a copy; bf16 reads them in place)
@@ -437,11 +477,20 @@ class GreedyDecoder(_GraphDecoder):
         def buffers():
             cos, sin = self._rope(tmax, device, dtype)
             attn = self._attn_route(tmax) if device.type == "cuda" and self.fused else None
-            st = dict(cos=cos, sin=sin, tmax=tmax, attn=attn, kc=[z(B, self.nkv, tmax, self.hd) for _ in self.layers],
-                      vc=[z(B, self.nkv, tmax, self.hd) for _ in self.layers], x=z(B, H), h=z(B, H), q=z(B, HD), a=z(B, HD), act=z(B, inter))
+            if self.kv_cache == "fp8":      # the code caches where the fp8 split kernel serves the state, else bf16 caches of dequantised values + the torch step
+                attn = "split_fp8" if (attn is not None and dtype == torch.bfloat16 and ops.decode_attention_fp8_ok(tmax, self.hd)
+                                       and self.nh % self.nkv == 0) else None
+            st = dict(cos=cos, sin=sin, tmax=tmax, attn=attn, x=z(B, H), h=z(B, H), q=z(B, HD), a=z(B, HD), act=z(B, inter))
+            if attn == "split_fp8":
+                st.update(kc8=[z(B, self.nkv, tmax, self.hd, dtype=torch.uint8) for _ in self.layers],
+                          vc8=[z(B, self.nkv, tmax, self.hd, dtype=torch.uint8) for _ in self.layers],
+                          ks=[z(B, self.nkv, tmax, dtype=torch.float32) for _ in self.layers],
+                          vs=[z(B, self.nkv, tmax, dtype=torch.float32) for _ in self.layers])
+            else:
+                st.update(kc=[z(B, self.nkv, tmax, self.hd) for _ in self.layers], vc=[z(B, self.nkv, tmax, self.hd) for _ in self.layers])
             if padded:      # key_valid[b, t]: cache slot t holds a real key of row b; rope_off[b]: rotary row - cache row of its decode steps
                 st.update(key_valid=torch.ones(B, tmax, dtype=torch.uint8, device=device), rope_off=z(B, dtype=torch.long))
-            if attn == "split":      # the split kernel's per-chunk partials
+            if attn in ("split", "split_fp8"):      # the split kernel's per-chunk partials
                 st.update(attn_ws=z(ops.decode_attention_workspace_bytes(B, self.nh, self.hd, tmax), dtype=torch.uint8))
             if device.type == "cuda" and self._use_skinny(B, dtype):
                 Hq, V = (self.nh + 2 * self.nkv) * self.hd, self.head_w.shape[0]
@@ -450,7 +499,8 @@ class GreedyDecoder(_GraphDecoder):
                           sk_ws=z(max(ops.gemm_skinny_workspace_bytes(B, n, k) for n, k in shapes), dtype=torch.uint8))
                 self._skinny_weights()
             return st
-        return self._cached_state((B, tmax, N, eos, pad, min_new, sample, stop, padded), B, N, tmax, device, eos, pad, min_new, sample, stop, buffers)
+        key = (B, tmax, N, eos, pad, min_new, sample, stop, padded) + ((self.kv_cache,) if self.kv_cache != "bf16" else ())
+        return self._cached_state(key, B, N, tmax, device, eos, pad, min_new, sample, stop, buffers)
 
     def _decode_step_fused(self, st):
         """One token for every sequence with the per-layer small ops fused in libvtgb.so
@@ -494,15 +544,23 @@ class GreedyDecoder(_GraphDecoder):
         # (its workspace exists exactly where the split kernel serves it)
         rope = (_ptr(st["cos"]), _ptr(st["sin"]), _ptr(st["pos"])) + ((_ptr(st["rope_off"]),) if padded else ())
         attn_ws, key_valid = st.get("attn_ws"), st.get("key_valid")
+        fp8_kv = st["attn"] == "split_fp8"      # kv_cache="fp8": the append quantises the K / V rows, the attention reads codes and scales
         delta, dS = None, 1
         for li, (ln1, wqkv, wo, ln2, wgu, wd) in enumerate(self.layers):
             norm(delta, dS, ln1)
             qkv, qS = lin_d(h, li, 0, "sk_qkv")
-            kv = (_ptr(st["kc"][li]), _ptr(st["vc"][li]))
-            rope_cache = getattr(lib, "vtgb_llm_rope_cache" + ("_parts" if qS > 1 else "") + ("_pos" if padded else ""))
-            L.check(rope_cache(code, *((_ptr(ws), qS) if qS > 1 else (_ptr(qkv),)), _ptr(q), *kv, *rope, B, nq, nkv, hd, tmax, stream))
-            ops.decode_attention(q, st["kc"][li], st["vc"][li], st["pos"], float(hd) ** -0.5, key_valid=key_valid, out=a, workspace=attn_ws,
-                                 split=st["attn"] == "split")
+            if fp8_kv:
+                kv8 = (st["kc8"][li], st["vc8"][li], st["ks"][li], st["vs"][li])
+                ra = L.LlmRopeCacheFp8Args(code, B, nq, nkv, hd, tmax, qS if qS > 1 else 0, None if qS > 1 else _ptr(qkv), _ptr(ws) if qS > 1 else None,
+                                           _ptr(q), *(_ptr(t) for t in kv8), *rope[:3], rope[3] if padded else None)
+                L.check(lib.vtgb_llm_rope_cache_fp8(ctypes.byref(ra), stream))
+                ops.decode_attention_fp8(q, *kv8, st["pos"], float(hd) ** -0.5, key_valid=key_valid, out=a, workspace=attn_ws)
+            else:
+                kv = (_ptr(st["kc"][li]), _ptr(st["vc"][li]))
+                rope_cache = getattr(lib, "vtgb_llm_rope_cache" + ("_parts" if qS > 1 else "") + ("_pos" if padded else ""))
+                L.check(rope_cache(code, *((_ptr(ws), qS) if qS > 1 else (_ptr(qkv),)), _ptr(q), *kv, *rope, B, nq, nkv, hd, tmax, stream))
+                ops.decode_attention(q, st["kc"][li], st["vc"][li], st["pos"], float(hd) ** -0.5, key_valid=key_valid, out=a, workspace=attn_ws,
+                                     split=st["attn"] == "split")
             o, oS = lin_d(a, li, 1, "sk_o")
             norm(o, oS, ln2)
             gu = lin(h, li, 2, "sk_gu")
@@ -585,8 +643,14 @@ class GreedyDecoder(_GraphDecoder):
             ok = (st["ar"][None, :] <= pidx[:, None])[None] & (st["key_valid"][:, None, :] != 0)          # [B, P, Tmax]
             causal = torch.where(ok, 0.0, torch.finfo(dt).min).to(dt)[:, None]
             key_mask = torch.where(valid, 0.0, torch.finfo(torch.float32).min).float().contiguous()      # [B, P] additive, vtgb_attention's
-        if self._use_hip_prefill(x, P):
+        fp8_state = st["attn"] == "split_fp8"
+        # (kv_cache="fp8" without the code caches -- the fallback state -- prefills on the torch path, which writes dequantised K/V)
+        if self._use_hip_prefill(x, P) and (self.kv_cache == "bf16" or fp8_state):
             last = self._prefill_hip(st, x, P, pos_ids, key_mask)
+        elif fp8_state:      # a prompt past the prefill kernels' bound into an fp8 state: quantised on the torch path
+            for li, w in enumerate(self.layers):
+                x = self._layer(x, w, cos, sin, None, None, pidx, causal, codes=(st["kc8"][li], st["vc8"][li], st["ks"][li], st["vs"][li]))
+            last = x[:, -1]
         else:
             for li, w in enumerate(self.layers):
                 x = self._layer(x, w, cos, sin, st["kc"][li], st["vc"][li], pidx, causal)
@@ -614,13 +678,15 @@ class T5GreedyDecoder(_GraphDecoder):
     self-attention and of every decoder layer's cross-attention, as HF's extended mask does."""
     _ACT_KIND = {"silu": 0, "swish": 0, "gelu_new": 1, "relu": 2, "gelu": 3}
 
-    def __init__(self, lm, fused: bool = True, weights: str = "bf16"):
+    def __init__(self, lm, fused: bool = True, weights: str = "bf16", kv_cache: str = "bf16"):
         cfg = lm.config
         if getattr(cfg, "model_type", "") != "t5":
             raise NotImplementedError("T5GreedyDecoder handles T5ForConditionalGeneration")
         if check_decode_weights(weights) != "bf16":
             raise NotImplementedError("decode_weights='fp8' is implemented for the Llama decoder only")
-        super().__init__(lm, fused, weights)
+        if check_kv_cache(kv_cache) != "bf16":
+            raise NotImplementedError("kv_cache='fp8' is implemented for the Llama decoder only")
+        super().__init__(lm, fused, weights, kv_cache)
         self.H, self.dk, self.D = cfg.num_heads, cfg.d_kv, cfg.d_model
         self.eps = cfg.layer_norm_epsilon
         self.start = cfg.decoder_start_token_id if cfg.decoder_start_token_id is not None else cfg.pad_token_id
@@ -871,12 +937,12 @@ def keyword_stop_plan(criteria) -> dict:
     return dict(stop_ids=[[int(v) for v in t.tolist()] for c in crit for t in c.keyword_ids], text_stop=text_stop)
 
 
-def make_decoder(lm, weights: str = "bf16"):
+def make_decoder(lm, weights: str = "bf16", kv_cache: str = "bf16"):
     """The graph decoder for a language model: Llama-architecture causal LMs and T5 seq2seq LMs; NotImplementedError otherwise.
-    ``weights``: "bf16", or "fp8" (Llama only: GreedyDecoder)."""
+    ``weights`` / ``kv_cache``: "bf16", or "fp8" (Llama only: GreedyDecoder)."""
     if getattr(lm.config, "model_type", "") == "t5":
-        return T5GreedyDecoder(lm, weights=weights)
-    return GreedyDecoder(lm, weights=weights)
+        return T5GreedyDecoder(lm, weights=weights, kv_cache=kv_cache)
+    return GreedyDecoder(lm, weights=weights, kv_cache=kv_cache)
 
 
 def prompt_padding(attention_mask: Tensor) -> Tuple[Optional[bool], Tensor]:
@@ -891,12 +957,16 @@ def prompt_padding(attention_mask: Tensor) -> Tuple[Optional[bool], Tensor]:
 
 def decoder_for(owner, lm):
     """The graph decoder for ``lm``, cached on ``owner`` (attribute ``_decoder``): the cached one when it was built for this ``lm`` and the
-    weights it re-packed are still the model's (``weights_key``) and in the owner's mode (attribute ``decode_weights``, "bf16" when it has
-    none), else a new one (``make_decoder``)."""
+    weights it re-packed are still the model's (``weights_key``) and in the owner's modes (attributes ``decode_weights`` and ``kv_cache``,
+    "bf16" when it has none), else a new one (``make_decoder``)."""
     mode = check_decode_weights(getattr(owner, "decode_weights", "bf16"))
+    kv = check_kv_cache(getattr(owner, "kv_cache", "bf16"))
     dec = getattr(owner, "_decoder", None)
-    if dec is None or dec.lm is not lm or dec.key != weights_key(lm) or getattr(dec, "weights", "bf16") != mode:
-        dec = owner._decoder = make_decoder(lm) if mode == "bf16" else make_decoder(lm, weights=mode)
+    if (dec is None or dec.lm is not lm or dec.key != weights_key(lm) or getattr(dec, "weights", "bf16") != mode
+            or getattr(dec, "kv_cache", "bf16") != kv):
+        kw = ({} if mode == "bf16" else dict(weights=mode))
+        kw.update({} if kv == "bf16" else dict(kv_cache=kv))
+        dec = owner._decoder = make_decoder(lm, **kw)      # (the default modes: the positional lm alone)
     return dec
 
 

@@ -439,7 +439,8 @@ class _LSTPBase(nn.Module):
     MAP = "A"
 
     def __init__(self, base_model_path, device="cuda", lora: bool = False, language_model: Optional[nn.Module] = None,
-                 compute_dtype="bf16", raft_dtype=None, lm_dtype=None, tgb_cfg: Optional[synth.TgbCfg] = None, decode_weights: str = "bf16"):
+                 compute_dtype="bf16", raft_dtype=None, lm_dtype=None, tgb_cfg: Optional[synth.TgbCfg] = None, decode_weights: str = "bf16",
+                 kv_cache: str = "bf16"):
         """Reference signature (eval/utils/model.py:21-45, :240-264): ``LSTP(base_model_path, device, lora=False)`` -- the
         HF config in ``base_model_path`` sizes the vision tower, Q-Former and language model (random init, the checkpoint
         fills them), the TGB is BERT-base with fusion_layer 6, RAFT is RAFT-large.  ``base_model_path`` may also be a
@@ -449,10 +450,13 @@ class _LSTPBase(nn.Module):
         same accuracy class, 1.2 x slower); "bf16" = the fast REDUCED-PRECISION RAFT; "f32" = the fp32 FMA chain), ``lm_dtype`` of the built LLM
         (default: bf16 with compute_dtype "bf16", else fp32), ``tgb_cfg`` to size the TGB differently from BERT-base (tests), ``decode_weights``
         ("bf16"; "fp8" = opt-in: the graph decoder streams the Llama projections and lm_head as per-row e4m3 codes -- half the weight bytes per
-        token, and the ids are those of the quantised model, not the reference's; see decode.GreedyDecoder)."""
+        token, and the ids are those of the quantised model, not the reference's; see decode.GreedyDecoder), ``kv_cache`` ("bf16"; "fp8" =
+        opt-in: the graph decoder keeps the Llama K/V cache as per-row e4m3 codes -- half the cache bytes per token and per state; the ids are
+        those of the model whose K/V are rounded that way, not the reference's; see decode.GreedyDecoder)."""
         super().__init__()
-        from .decode import check_decode_weights
+        from .decode import check_decode_weights, check_kv_cache
         self.decode_weights = check_decode_weights(decode_weights)      # (decode.decoder_for reads it from its owner)
+        self.kv_cache = check_kv_cache(kv_cache)                        # (likewise)
         hf_config = None
         if isinstance(base_model_path, synth.PathCfg):
             cfg = base_model_path
@@ -467,6 +471,8 @@ class _LSTPBase(nn.Module):
                 language_model = build_language_model(hf_config, lm_dtype)
         if self.decode_weights == "fp8" and getattr(getattr(language_model, "config", None), "model_type", "") == "t5":
             raise NotImplementedError("decode_weights='fp8' is implemented for the Llama decoder only")
+        if self.kv_cache == "fp8" and getattr(getattr(language_model, "config", None), "model_type", "") == "t5":
+            raise NotImplementedError("kv_cache='fp8' is implemented for the Llama decoder only")
         self.cfg = cfg
         self.model = PathModel(cfg, language_model, compute_dtype, hf_config=hf_config)
         self.temporal_encoder = TemporalEncoder(cfg.tgb, compute_dtype)
@@ -492,8 +498,8 @@ class _LSTPBase(nn.Module):
 
     @classmethod
     def from_cfg(cls, cfg: synth.PathCfg, device="cuda", language_model: Optional[nn.Module] = None, compute_dtype="bf16", raft_dtype=None,
-                 decode_weights: str = "bf16"):
-        return cls(cfg, device, False, language_model, compute_dtype, raft_dtype, decode_weights=decode_weights)
+                 decode_weights: str = "bf16", kv_cache: str = "bf16"):
+        return cls(cfg, device, False, language_model, compute_dtype, raft_dtype, decode_weights=decode_weights, kv_cache=kv_cache)
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         """Accepts a reference (Lightning) checkpoint's ``state_dict`` as is: peft's ``language_model.base_model.model.``

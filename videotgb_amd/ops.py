@@ -408,6 +408,69 @@ def decode_attention(q: Tensor, kc: Tensor, vc: Tensor, pos: Tensor, scale: floa
     return out
 
 
+# ---- fp8 K/V cache (opt-in: kv_cache="fp8").  A cache row -- one token of one K/V head -- is e4m3 codes and one power-of-two scale.
+KV_FP8_MIN_EXP = -100      # the scale's exponent is clamped here, so that code * scale stays a normal bf16 number (the smallest code is 2^-9)
+
+
+def quantize_fp8_kv(x: Tensor) -> Tuple[Tensor, Tensor]:
+    """x [..., hd] -> (codes [..., hd] torch.float8_e4m3fn, scale [...] fp32): THE definition of the fp8 K/V cache format (kv_cache="fp8";
+    vtgb_llm_rope_cache_fp8 / _prefill_fp8 compute the same on the device, bit for bit).  ``quantize_fp8_rows``' rule on the last dimension:
+    e = the smallest integer with amax * 2^-e <= 448 (from the binary exponent: exact; 0 for a zero row), clamped below at -100,
+    scale = 2^e, codes = x * 2^-e rounded to nearest even.  codes * scale is exactly representable in bf16: the mode is an ordinary bf16
+    model whose K and V pass through ``dequantize_fp8_kv(*quantize_fp8_kv(.))`` as they are produced.  Runs on any device (no host
+    synchronisation: it may be captured); non-finite values are outside the contract, as they are for the bf16 cache."""
+    xf = x.detach().float()
+    amax = xf.abs().amax(dim=-1)
+    m, ex = torch.frexp(amax)                                    # amax = m * 2^ex with 0.5 <= m < 1; 448 = 0.875 * 2^9
+    e = torch.where(amax > 0, ex - 9 + (m > 0.875).to(ex.dtype), torch.zeros_like(ex)).clamp(min=KV_FP8_MIN_EXP)
+    q = (xf * _pow2(-e)[..., None]).to(torch.float8_e4m3fn)
+    return q, _pow2(e)
+
+
+def _pow2(e: Tensor) -> Tensor:
+    """2^e as fp32 for integer e in [-126, 127], built on the bits: exact on every device (a pow-based ldexp need not be)."""
+    return ((e.to(torch.int32) + 127) << 23).view(torch.float32)
+
+
+def dequantize_fp8_kv(q: Tensor, scale: Tensor, dtype: torch.dtype = torch.bfloat16) -> Tensor:
+    """codes * scale [..., hd]: exact in bf16 (and so in fp32) for the pairs ``quantize_fp8_kv`` returns."""
+    return (q.float() * scale.float()[..., None]).to(dtype)
+
+
+def fp8_kv_round(x: Tensor) -> Tensor:
+    """x [..., hd] as the fp8 K/V cache holds it: dequantize_fp8_kv(*quantize_fp8_kv(x)) in x's dtype."""
+    return dequantize_fp8_kv(*quantize_fp8_kv(x), dtype=x.dtype)
+
+
+def decode_attention_fp8_ok(tmax: int, hd: int) -> bool:
+    """Whether vtgb_llm_decode_attention_split_fp8 takes a cache of ``tmax`` slots and head_dim ``hd`` (the split kernel's limits)."""
+    return hd in (64, 128) and tmax > 0 and tmax % 64 == 0 and tmax <= DECODE_SPLIT_MAX_KEYS
+
+
+def decode_attention_fp8(q: Tensor, kc8: Tensor, vc8: Tensor, ks: Tensor, vs: Tensor, pos: Tensor, scale: float, key_valid: Optional[Tensor] = None,
+                         out: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
+    """``decode_attention`` over an fp8 K/V cache: q [B, nq*hd] bf16, kc8 / vc8 [B, nkv, tmax, hd] uint8 (or float8_e4m3fn) codes, ks / vs
+    [B, nkv, tmax] fp32 row scales (``quantize_fp8_kv``) -> out [B, nq*hd] bf16.  Always the split-KV kernel (vtgb_llm_decode_attention_split_fp8,
+    caches from 64 slots up); the result is ``decode_attention(q, dq(kc8, ks), dq(vc8, vs), ..., split=True)``, bit for bit.  ``workspace``:
+    ``decode_attention_workspace_bytes``, allocated here when None."""
+    _need_cuda(q, kc8, vc8, ks, vs, pos)
+    B, nkv, tmax, hd = kc8.shape
+    nq = q.numel() // (B * hd)
+    assert kc8.element_size() == 1 and vc8.element_size() == 1 and kc8.is_contiguous() and vc8.is_contiguous() and vc8.shape == kc8.shape
+    assert ks.dtype == vs.dtype == torch.float32 and ks.shape == vs.shape == (B, nkv, tmax) and ks.is_contiguous() and vs.is_contiguous()
+    assert q.is_contiguous() and pos.dtype == torch.int64
+    assert key_valid is None or (key_valid.dtype == torch.uint8 and key_valid.shape == (B, tmax) and key_valid.is_contiguous())
+    if out is None:
+        out = torch.empty(B, nq * hd, dtype=q.dtype, device=q.device)
+    need = decode_attention_workspace_bytes(B, nq, hd, tmax)
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)
+    assert workspace.numel() * workspace.element_size() >= need, "decode_attention_fp8: workspace too small"
+    L.check(L.lib().vtgb_llm_decode_attention_split_fp8(dtype_code(q.dtype), _ptr(q), _ptr(kc8), _ptr(vc8), _ptr(ks), _ptr(vs), _ptr(out), _ptr(pos),
+                                                        _ptr(key_valid), _ptr(workspace), B, nq, nkv, hd, tmax, float(scale), _stream()))
+    return out
+
+
 def layernorm(x: Tensor, gamma: Tensor, beta: Tensor, eps: float, out_dtype=torch.float32) -> Tensor:
     _need_cuda(x, gamma, beta)
     x = x.contiguous().float()
