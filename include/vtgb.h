@@ -496,6 +496,25 @@ typedef struct {
 } vtgb_pair_conv_ex_args;
 int vtgb_pair_conv_ex(const vtgb_pair_conv_ex_args* a, vtgb_stream_t stream);
 
+/* Unit-level surface of vtgb_raft_update's fused f16c8 launch "correlation lookup + convc1" (corr.py:29-50, update.py:88: cor = relu(convc1(corr)),
+ * 1x1, 324 -> 256): for every pixel the 4 x 81 bilinear taps of the pyramid around (pixel + flow), as f16c8 operands (csrc/pair_h8.h) against the
+ * table's convc1 weights (ops.h8_conv_pack of the [256, 1, 1, 384] zero-padded weight; scale = device int32: the E8M0 byte), + bias, ReLU -> c1 as
+ * f16c8 pair rows.  variant 1: the split-K tile vtgb_raft_update launches (two workgroups per CU); variant 0: the whole-K tile it replaced (one
+ * workgroup per CU) -- the in-process baseline.  `occupancy` (host, optional) receives hipOccupancyMaxActiveBlocksPerMultiprocessor of the launched
+ * instantiation at its launch configuration.  What tests/test_gpu_lookup_split.py checks against fp64. */
+typedef struct {
+    int32_t n_pairs, H8, W8;    /* M = n_pairs * H8 * W8 pixels; H8, W8 >= 8 */
+    int32_t variant;            /* 0 or 1 */
+    const float* corr[4];       /* pyramid level l: [M, H8>>l, W8>>l] fp32 */
+    const float* flow;          /* [M, 2] fp32 (x, y) */
+    const void* weights;        /* [256, 768] 16-bit units */
+    const int32_t* scale;       /* device: E8M0 byte of 2^-11 / sw */
+    const float* bias;          /* [256] */
+    void* out;                  /* [M, 512] 16-bit units: fp16 x 256 | correction bytes x 512 */
+    int32_t* occupancy;         /* host, optional */
+} vtgb_raft_lookup_convc1_args;
+int vtgb_raft_lookup_convc1(const vtgb_raft_lookup_convc1_args* a, vtgb_stream_t stream);
+
 /* CorrBlock.__init__ (raft_utils/corr.py:12-27; the all-pairs product :52-60): for every pair the correlation of each
  * pixel of image 1 with every pixel of image 2 over the `dim` = 256 features, divided by sqrt(dim), and its three
  * avg_pool2d(2, stride 2) -- one kernel, the four levels are its only output.  Pair n uses the feature maps of images

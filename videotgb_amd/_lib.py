@@ -45,6 +45,7 @@ EXPORTS = [
     "vtgb_pair_pack", "vtgb_pair_conv", "vtgb_pair_conv_ex", "vtgb_attention_tiled",
     "vtgb_llm_decode_attention_split_workspace_bytes", "vtgb_llm_decode_attention_split",
     "vtgb_llm_decode_attention_split_fp8", "vtgb_llm_rope_cache_fp8", "vtgb_llm_rope_cache_prefill_fp8",
+    "vtgb_raft_lookup_convc1",
 ]
 COMM_ID_BYTES = 128
 
@@ -150,6 +151,11 @@ class PairConvExArgs(C.Structure):
     _fields_ = [("conv", PairConvArgs), ("resid", vp), ("ld_resid", i32), ("tail_w", vp), ("tail_out", vp), ("out_f32", vp), ("ld_f32", i32)]
 
 
+class RaftLookupConvc1Args(C.Structure):
+    _fields_ = [("n_pairs", i32), ("H8", i32), ("W8", i32), ("variant", i32), ("corr", vp * 4), ("flow", vp), ("weights", vp), ("scale", vp), ("bias", vp),
+                ("out", vp), ("occupancy", C.POINTER(i32))]
+
+
 class RaftCorrArgs(C.Structure):
     _fields_ = [("dtype", i32), ("n_pairs", i32), ("H8", i32), ("W8", i32), ("dim", i32), ("pairs_per_clip", i32), ("frames_per_clip", i32),
                 ("first_off", i32), ("second_off", i32), ("n_images", i32), ("scale", f32), ("fmap", vp), ("levels", vp * 4),
@@ -241,6 +247,8 @@ def lib() -> C.CDLL:
     L.vtgb_pair_conv.restype = C.c_int
     L.vtgb_pair_conv_ex.argtypes = [C.POINTER(PairConvExArgs), vp]
     L.vtgb_pair_conv_ex.restype = C.c_int
+    L.vtgb_raft_lookup_convc1.argtypes = [C.POINTER(RaftLookupConvc1Args), vp]
+    L.vtgb_raft_lookup_convc1.restype = C.c_int
     L.vtgb_raft_update.argtypes = [C.POINTER(RaftUpdateArgs), vp]
     L.vtgb_raft_update.restype = C.c_int
     L.vtgb_raft_update_workspace_bytes.argtypes = [C.POINTER(RaftUpdateArgs)]

@@ -431,223 +431,293 @@ __global__ __launch_bounds__(512, 2) void raft_lookup_convc1_kernel(const CorrPy
 }
 
 // ---------------------------------------------------------------------------------------
-// The same fusion at VTGB_F16C8 (round 6; raft_x3.hip): lookup -> the operand tile as f16c8 pair rows in LDS ([64][392] fp16 values + [64][784 B]
-// correction bytes: taps 4g .. 4g+3 as (xl' x 4, xh8 x 4), csrc/pair_h8.h) -> wave w multiplies it with its 32 channels' weights -- 11 fp16 k-steps of 32
-// (v_mfma_f32_16x16x32_f16) and 6 fp8 k-tiles of 128 bytes (v_mfma_scale_f32_16x16x128_f8f6f4, K = 324 zero-padded to 384), both streamed from L2 in
-// MFMA fragment order (packed once per call from the table's [256][fp16 x 384 | correction bytes x 768]) -> bias, ReLU -> the f16c8 pair rows of c1 leave
-// through LDS as whole 1 KiB rows.  The tile is 113 KB: ONE workgroup per CU (the bf16 form runs two, one's lookup beside the other's MFMAs); what is saved
-// is the 1.5 KB-per-pixel tap tensor's write + read and a launch.
+// The same fusion at VTGB_F16C8 (round 6; raft_x3.hip): lookup -> the operand tile as f16c8 pair rows in LDS (fp16 values + correction bytes: taps
+// 4g .. 4g+3 as (xl' x 4, xh8 x 4), csrc/pair_h8.h) -> wave w multiplies it with its 32 channels' weights -- fp16 k-steps of 32
+// (v_mfma_f32_16x16x32_f16) and fp8 k-tiles of 128 bytes (v_mfma_scale_f32_16x16x128_f8f6f4), both streamed from L2 in MFMA fragment order (packed
+// once per call from the table's [256][fp16 x 384 | correction bytes x 768]) -> bias, ReLU -> the f16c8 pair rows of c1 leave through LDS as whole
+// 1 KiB rows.  What is saved is the 1.5 KB-per-pixel tap tensor's write + read and a launch.
+//
+// One template, two tiles (LhCfg):
+//   SPLIT = 1 (what vtgb_raft_update launches): the tile's K in two halves at the level boundary.  Half A holds the taps of levels 0 and 1, half B those
+//     of levels 2 and 3: 162 real taps each, zero-padded to 192 = 6 fp16 k-steps + 3 fp8 k-tiles (one fp16 k-step more than the whole K needs; no
+//     level's window is fetched twice).  Per tile: lookup A -> k-steps / k-tiles of A -> lookup B into the same [64][192] region -> those of B, the
+//     accumulators staying in registers.  The operand region is 51 200 B + 6 656 B of windows; the [64][1040 B] output tile that reuses it sets the
+//     allocation: 66 560 B, TWO workgroups per CU -- one's gathers run beside the other's MFMAs, as in the bf16 kernel above.  With half the loads per
+//     pixel, all 8 of a wave's pixels are in flight at once in the same 32 registers.
+//   SPLIT = 0 (the round-6 tile; vtgb_raft_lookup_convc1 variant 0 and the debug hook only -- the A/B baseline and the tests' yardstick): the whole K,
+//     [64][392] fp16 + [64][784 B], 113 664 B: ONE workgroup per CU, whose three phases add up.
+// A pixel's sum is bias + (A: fp16 k-steps, fp8 k-tiles) + (B: ...) in that order whatever the tile, wave or batch it falls in.
 // ---------------------------------------------------------------------------------------
-constexpr int LH_KS16 = 11, LH_KT8 = 6, LH_LDA8 = 784, LH_LDO = 1040;      // fp16 k-steps, fp8 k-tiles, correction-row pitch (bytes), output-row pitch (bytes)
-constexpr int LH_A16_BYTES = LC_PX * LC_LDA * 2, LH_A8_BYTES = LC_PX * LH_LDA8;
-constexpr int LH_LDS = LH_A16_BYTES + LH_A8_BYTES + LC_WAVES * 4 * 104 * 4;
-constexpr size_t LH_WPK_BYTES = (size_t)LC_WAVES * (LH_KS16 * 2 * 1024 + LH_KT8 * 2 * 2048);
-static_assert(LC_PX * LH_LDO <= LH_A16_BYTES + LH_A8_BYTES, "the output tile reuses the operand tile");
+constexpr int LH_LDO = 1040;      // output-row pitch (bytes)
+#ifndef LH_SPLIT_DEPTH
+#define LH_SPLIT_DEPTH 8      // pixels whose window loads are in flight per wave on the split-K tile (all of LC_WPX: 4 loads each; -DLH_SPLIT_DEPTH=4 not measured)
+#endif
+template <int SPLIT>
+struct LhCfg {
+    static constexpr int NH = SPLIT ? 2 : 1;                 // K halves
+    static constexpr int LPH = 4 / NH;                       // pyramid levels per half
+    static constexpr int REAL = 81 * LPH;                    // real taps per half
+    static constexpr int KK = SPLIT ? 3 : 6;                 // deposit rounds of 64 taps per half
+    static constexpr int KS16 = SPLIT ? 6 : 11;              // fp16 k-steps per half
+    static constexpr int KT8 = SPLIT ? 3 : 6;                // fp8 k-tiles per half
+    static constexpr int LDA = SPLIT ? 200 : LC_LDA;         // fp16-row pitch (values)
+    static constexpr int LDA8 = SPLIT ? 400 : 784;           // correction-row pitch (bytes)
+    static constexpr int DEPTH = SPLIT ? LH_SPLIT_DEPTH : 4;              // pixels whose window loads are in flight per wave (of LC_WPX = 8)
+    static constexpr int A16_BYTES = LC_PX * LDA * 2, A8_BYTES = LC_PX * LDA8;
+    static constexpr int OPERAND = A16_BYTES + A8_BYTES + LC_WAVES * LPH * 104 * 4;
+    static constexpr int LDS = OPERAND > LC_PX * LH_LDO ? OPERAND : LC_PX * LH_LDO;      // the output tile reuses the operand tile (and the windows)
+    static constexpr int PER_HALF = KS16 * 2 * 64 + KT8 * 2 * 2 * 64;                    // 16-byte units per wave and half
+    static constexpr int PER_WAVE = NH * PER_HALF;
+    static constexpr size_t WPK_BYTES = (size_t)LC_WAVES * PER_WAVE * 16;
+};
+static_assert(LhCfg<0>::LDS == 113664 && LhCfg<1>::LDS == 66560 && 2 * LhCfg<1>::LDS <= 160 * 1024, "one / two workgroups per CU");
 typedef int lh_i32x4 __attribute__((ext_vector_type(4)));
 typedef int lh_i32x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 lh_f16x8 __attribute__((ext_vector_type(8)));
 
 // w: [256][768 16-bit units] = per output channel fp16 values of the 384 taps, then 768 correction bytes (ops.h8_conv_pack of a 1x1 convolution).
-// packed (16-byte units): wave w: [ks < 11][i < 2][lane] fp16 fragments (taps ks * 32 + (lane >> 4) * 8 ..), then [t < 6][i < 2][half < 2][lane] the
-// two 16-byte pieces of the fp8 fragment (bytes t * 128 + half * 64 + (lane >> 4) * 16 ..) of channel w * 32 + i * 16 + (lane & 15)
+// packed (16-byte units): wave w, half hf: [ks < KS16][i < 2][lane] fp16 fragments (the half's taps ks * 32 + (lane >> 4) * 8 ..), then
+// [t < KT8][i < 2][half < 2][lane] the two 16-byte pieces of the fp8 fragment (the half's bytes t * 128 + half * 64 + (lane >> 4) * 16 ..) of channel
+// w * 32 + i * 16 + (lane & 15).  Tap kl of half hf is the table's tap hf * REAL + kl; SPLIT: taps kl >= REAL are zeros.
+template <int SPLIT>
 __global__ __launch_bounds__(256) void raft_lkc1_h8_pack_w_kernel(const bf16_t* __restrict__ w, lh_i32x4* __restrict__ packed) {
+    typedef LhCfg<SPLIT> C;
     const int idx = blockIdx.x * 256 + threadIdx.x;
-    constexpr int PER_WAVE = LH_KS16 * 2 * 64 + LH_KT8 * 2 * 2 * 64;
-    if (idx >= LC_WAVES * PER_WAVE) return;
-    const int wv = idx / PER_WAVE, r = idx - wv * PER_WAVE, lane = r & 63;
-    const char* row;
-    int off;
-    if (r < LH_KS16 * 2 * 64) {
+    if (idx >= LC_WAVES * C::PER_WAVE) return;
+    const int wv = idx / C::PER_WAVE, rw = idx - wv * C::PER_WAVE, hf = rw / C::PER_HALF, r = rw - hf * C::PER_HALF, lane = r & 63;
+    if (r < C::KS16 * 2 * 64) {
         const int i = (r >> 6) & 1, ks = r >> 7;
-        row = reinterpret_cast<const char*>(w + (int64_t)(wv * 32 + i * 16 + (lane & 15)) * 768);
-        off = (ks * 32 + (lane >> 4) * 8) * 2;
+        const unsigned short* row = reinterpret_cast<const unsigned short*>(w + (int64_t)(wv * 32 + i * 16 + (lane & 15)) * 768);
+        unsigned short v[8];
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            const int kl = ks * 32 + (lane >> 4) * 8 + e;
+            v[e] = (!SPLIT || kl < C::REAL) ? row[hf * C::REAL + kl] : (unsigned short)0;
+        }
+        lh_i32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; e++) o[e] = (int)((unsigned)v[2 * e] | ((unsigned)v[2 * e + 1] << 16));
+        packed[idx] = o;
     } else {
-        const int q = (r - LH_KS16 * 2 * 64) >> 6, half = q & 1, i = (q >> 1) & 1, t = q >> 2;
-        row = reinterpret_cast<const char*>(w + (int64_t)(wv * 32 + i * 16 + (lane & 15)) * 768) + 768;
-        off = t * 128 + half * 64 + (lane >> 4) * 16;
+        const int q = (r - C::KS16 * 2 * 64) >> 6, half = q & 1, i = (q >> 1) & 1, t = q >> 2;
+        const unsigned char* row = reinterpret_cast<const unsigned char*>(w + (int64_t)(wv * 32 + i * 16 + (lane & 15)) * 768) + 768;
+        const int ob = t * 128 + half * 64 + (lane >> 4) * 16;
+        lh_i32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            unsigned u = 0;
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const int p = ob + e * 4 + b, kl = (p >> 3) * 4 + (p & 3), which = (p >> 2) & 1, ksrc = hf * C::REAL + kl;      // byte p of the half's row
+                const unsigned byte = (!SPLIT || kl < C::REAL) ? row[(ksrc >> 2) * 8 + (ksrc & 3) + which * 4] : 0u;
+                u |= byte << (8 * b);
+            }
+            o[e] = (int)u;
+        }
+        packed[idx] = o;
     }
-    packed[idx] = *reinterpret_cast<const lh_i32x4*>(row + off);
 }
 
-template <typename CT>
-__global__ __launch_bounds__(512, 2) void raft_lookup_convc1_h8_kernel(const CorrPyr pyr, const float* __restrict__ flow, const lh_i32x4* __restrict__ wpk,
+#ifndef LH_ABL
+#define LH_ABL 0        // timing-only ablation builds (tools/exp/build_variant.sh NAME raft.hip -DLH_ABL=n): 1 no lookup phase, 2 no MFMA loops, 4 no output.
+#endif                  // SPLIT = 0 measured (2.62 ms whole): no lookup 0.99, no MFMA loops 1.84, no output 2.42, neither lookup nor MFMA 0.40 -- the phases ADD (one
+                        // workgroup per CU); the lookup phase is 1.6 ms there against 0.87 in the bf16 kernel, whose second workgroup hides the gathers' latency.
+                        // A vector form of the deposit (fp32 staging row, one four-value split and two 8-byte writes per group) changed nothing (2.71 vs 2.62 ms),
+                        // nor did 8 instead of 4 pixels in flight per wave at 8 loads each (2.83 vs 2.60 ms).  SPLIT = 1: DESIGN.md section 4.
+template <typename CT, int SPLIT>
+__global__ __launch_bounds__(512, SPLIT ? 4 : 2) void raft_lookup_convc1_h8_kernel(const CorrPyr pyr, const float* __restrict__ flow, const lh_i32x4* __restrict__ wpk,
                                                                        const int* __restrict__ scale, const float* __restrict__ bias, bf16_t* __restrict__ c1, int64_t M,
                                                                        int H8, int W8) {
+    typedef LhCfg<SPLIT> C;
+    constexpr int NH = C::NH, LPH = C::LPH, KK = C::KK, KS16 = C::KS16, KT8 = C::KT8, LDA = C::LDA, LDA8 = C::LDA8, DEPTH = C::DEPTH;
     extern __shared__ __attribute__((aligned(16))) char lc_smem[];
-    unsigned short* const At = reinterpret_cast<unsigned short*>(lc_smem);                 // fp16 values [64][LC_LDA]
-    unsigned char* const A8 = reinterpret_cast<unsigned char*>(lc_smem + LH_A16_BYTES);   // correction bytes [64][LH_LDA8]
+    unsigned short* const At = reinterpret_cast<unsigned short*>(lc_smem);                  // fp16 values [64][LDA]
+    unsigned char* const A8 = reinterpret_cast<unsigned char*>(lc_smem + C::A16_BYTES);    // correction bytes [64][LDA8]
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float* const wv = reinterpret_cast<float*>(lc_smem + LH_A16_BYTES + LH_A8_BYTES) + wave * (4 * 104);
+    float* const wv = reinterpret_cast<float*>(lc_smem + C::A16_BYTES + C::A8_BYTES) + wave * (LPH * 104);
     const int fr = lane & 15, fg = lane >> 4;
     const int sc_w = *scale;
-    // this wave's fp16 weight fragments of the first three k-steps: in flight during the whole lookup phase
-    const lh_i32x4* wp = wpk + (int64_t)wave * (LH_KS16 * 2 * 64 + LH_KT8 * 2 * 2 * 64) + lane;
+    const lh_i32x4* wp = wpk + (int64_t)wave * C::PER_WAVE + lane;
     lh_i32x4 wf[4][2];
-#pragma unroll
-    for (int k = 0; k < 3; k++)
-#pragma unroll
-        for (int i = 0; i < 2; i++) wf[k][i] = wp[(k * 2 + i) * 64];
-    const int wy0 = lane / 10, wx0 = lane - wy0 * 10;
-    const int e1 = lane < 36 ? lane + 64 : 99;
-    const int wy1 = e1 / 10, wx1 = e1 - wy1 * 10;
-    int la[4], lb[4];
-#pragma unroll
-    for (int l = 0; l < 4; l++) {
-        la[l] = (wy0 * pyr.w[l] + wx0) * (int)sizeof(CT);
-        lb[l] = (wy1 * pyr.w[l] + wx1) * (int)sizeof(CT);
-    }
-    int tap_off[6], frac_off[6];
-#pragma unroll
-    for (int kk = 0; kk < 6; kk++) {
-        const int k = kk * 64 + lane;
-        const int l = k / 81, t = k - l * 81, i = t / 9, j = t - i * 9;
-        tap_off[kk] = k < 324 ? l * 104 + j * 10 + i : 0;
-        frac_off[kk] = (k < 324 ? l : 0) * 104 + 100;
-    }
     const int HW = H8 * W8;
     const int64_t m_tile = (int64_t)blockIdx.x * LC_PX, m_first = m_tile + wave * LC_WPX;
     const int npx = (int)(M - m_first < LC_WPX ? (M - m_first > 0 ? M - m_first : 0) : LC_WPX);
-#ifndef LH_ABL
-#define LH_ABL 0        // timing-only ablation builds (tools/exp/build_variant.sh NAME raft.hip -DLH_ABL=n): 1 no lookup phase, 2 no MFMA loops, 4 no output.
-#endif                  // Measured (2.62 ms whole): no lookup 0.99, no MFMA loops 1.84, no output 2.42, neither lookup nor MFMA 0.40 -- the phases ADD (one workgroup
-                        // per CU: 113 KB of LDS); the lookup phase is 1.6 ms here against 0.87 in the bf16 kernel, whose second workgroup hides the gathers'
-                        // latency.  A vector form of the deposit (fp32 staging row, one four-value split and two 8-byte writes per group) changed nothing
-                        // (2.71 vs 2.62 ms): the deposit is not what the phase waits for.
-    if (npx > 0 && !(LH_ABL & 1)) {
-        const int p_first = (int)(m_first % HW);
-        int sx0, sbase;
-        float sqx, sqy;
-        {
-            const int spi = (lane >> 2) < npx ? (lane >> 2) : npx - 1, sl = lane & 3;
-            int p = p_first + spi;
-            p = p >= HW ? p - HW : p;
-            const float2 f = *reinterpret_cast<const float2*>(flow + (m_first + spi) * 2);
-            const float cx = (float)(p % W8) + f.x, cy = (float)(p / W8) + f.y;
-            const float sc = 1.0f / (float)(1 << sl);
-            const float xs = cx * sc, ys = cy * sc, x0f = floorf(xs), y0f = floorf(ys);
-            const int x0 = (int)fminf(fmaxf(x0f, -32768.f), 32768.f) - 4, y0 = (int)fminf(fmaxf(y0f, -32768.f), 32768.f) - 4;
-            const int wl = sl == 0 ? pyr.w[0] : sl == 1 ? pyr.w[1] : sl == 2 ? pyr.w[2] : pyr.w[3];
-            sx0 = x0;
-            sbase = (y0 * wl + x0) * (int)sizeof(CT);
-            sqx = xs - x0f; sqy = ys - y0f;
-        }
-#ifndef LH_DEPTH
-#define LH_DEPTH 4      // pixels whose window loads are in flight per wave (of LC_WPX = 8).  -DLH_DEPTH=8 (all of them up front) measured SLOWER: 2.83 vs 2.60 ms, same box
-#endif
-        CT r[LH_DEPTH][8];
-        const CT* lvl0[4];
+    f32x4 acc[2][4];
 #pragma unroll
-        for (int l = 0; l < 4; l++) lvl0[l] = reinterpret_cast<const CT*>(pyr.lvl[l]) + m_first * (int64_t)(pyr.h[l] * pyr.w[l]);
+    for (int hf = 0; hf < NH; hf++) {
+        const lh_i32x4* wph = wp + hf * C::PER_HALF;
+        // this wave's fp16 weight fragments of the half's first three k-steps: in flight during the whole lookup phase of the first half; requested after
+        // the deposit of a later one, whose lookup holds the accumulators beside its window registers (128 VGPRs: four waves per SIMD)
+        if (hf == 0) {
+#pragma unroll
+            for (int k = 0; k < 3; k++)
+#pragma unroll
+                for (int i = 0; i < 2; i++) wf[k][i] = wph[(k * 2 + i) * 64];
+        }
+        if (npx > 0 && !(LH_ABL & 1)) {
+            // the lookup's lane constants, per half from a copy of the lane number the compiler cannot see through: derived from `lane` itself they
+            // would stay in registers across the MFMA phase of the half before (a dozen VGPRs the four-waves-per-SIMD budget does not have)
+            int ln = lane;
+            if (NH > 1) asm volatile("" : "+v"(ln));
+            const int wy0 = ln / 10, wx0 = ln - wy0 * 10;
+            const int e1 = ln < 36 ? ln + 64 : 99;
+            const int wy1 = e1 / 10, wx1 = e1 - wy1 * 10;
+            int tap_off[KK], frac_off[KK];      // tap kl of a half: level kl / 81 of the half's LPH
+#pragma unroll
+            for (int kk = 0; kk < KK; kk++) {
+                const int k = kk * 64 + ln;
+                const int l = k / 81, t = k - l * 81, i = t / 9, j = t - i * 9;
+                tap_off[kk] = k < C::REAL ? l * 104 + j * 10 + i : 0;
+                frac_off[kk] = (k < C::REAL ? l : 0) * 104 + 100;
+            }
+            // the wave's pixels' window origins and fractions: lane 4 p + l holds pixel p, level l
+            int sx0, sbase;
+            float sqx, sqy;
+            {
+                const int p_first = (int)(m_first % HW);
+                const int spi = (ln >> 2) < npx ? (ln >> 2) : npx - 1, sl = ln & 3;
+                int p = p_first + spi;
+                p = p >= HW ? p - HW : p;
+                const float2 f = *reinterpret_cast<const float2*>(flow + (m_first + spi) * 2);
+                const float cx = (float)(p % W8) + f.x, cy = (float)(p / W8) + f.y;
+                const float sc = 1.0f / (float)(1 << sl);
+                const float xs = cx * sc, ys = cy * sc, x0f = floorf(xs), y0f = floorf(ys);
+                const int x0 = (int)fminf(fmaxf(x0f, -32768.f), 32768.f) - 4, y0 = (int)fminf(fmaxf(y0f, -32768.f), 32768.f) - 4;
+                const int wl = sl == 0 ? pyr.w[0] : sl == 1 ? pyr.w[1] : sl == 2 ? pyr.w[2] : pyr.w[3];
+                sx0 = x0;
+                sbase = (y0 * wl + x0) * (int)sizeof(CT);
+                sqx = xs - x0f; sqy = ys - y0f;
+            }
+            CT r[DEPTH][2 * LPH];
+            const CT* lvl0[LPH];
+            int la[LPH], lb[LPH];
+#pragma unroll
+            for (int ll = 0; ll < LPH; ll++) {
+                la[ll] = (wy0 * pyr.w[hf * LPH + ll] + wx0) * (int)sizeof(CT);
+                lb[ll] = (wy1 * pyr.w[hf * LPH + ll] + wx1) * (int)sizeof(CT);
+            }
+#pragma unroll
+            for (int ll = 0; ll < LPH; ll++) lvl0[ll] = reinterpret_cast<const CT*>(pyr.lvl[hf * LPH + ll]) + m_first * (int64_t)(pyr.h[hf * LPH + ll] * pyr.w[hf * LPH + ll]);
 #define LH_FETCH(pi, d)                                                                                 \
     {                                                                                                   \
-        _Pragma("unroll") for (int l = 0; l < 4; l++) {                                                 \
+        _Pragma("unroll") for (int ll = 0; ll < LPH; ll++) {                                            \
+            const int l = hf * LPH + ll;                                                                \
             const int hw = pyr.h[l] * pyr.w[l];                                                         \
-            const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<CT*>(lvl0[l] + (unsigned)((pi) * hw)), 0, \
+            const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<CT*>(lvl0[ll] + (unsigned)((pi) * hw)), 0, \
                                                               hw * (int)sizeof(CT), 0x00020000);        \
             const int x0 = __builtin_amdgcn_readlane(sx0, (pi) * 4 + l), b0 = __builtin_amdgcn_readlane(sbase, (pi) * 4 + l); \
-            const unsigned oa = (unsigned)(x0 + wx0) < (unsigned)pyr.w[l] ? (unsigned)(b0 + la[l]) : 0xFFFFFFF0u; \
-            const unsigned ob = (unsigned)(x0 + wx1) < (unsigned)pyr.w[l] ? (unsigned)(b0 + lb[l]) : 0xFFFFFFF0u; \
-            r[d][2 * l] = lk_load<CT>(rs, oa);                                                          \
-            r[d][2 * l + 1] = lk_load<CT>(rs, ob);                                                      \
+            const unsigned oa = (unsigned)(x0 + wx0) < (unsigned)pyr.w[l] ? (unsigned)(b0 + la[ll]) : 0xFFFFFFF0u; \
+            const unsigned ob = (unsigned)(x0 + wx1) < (unsigned)pyr.w[l] ? (unsigned)(b0 + lb[ll]) : 0xFFFFFFF0u; \
+            r[d][2 * ll] = lk_load<CT>(rs, oa);                                                         \
+            r[d][2 * ll + 1] = lk_load<CT>(rs, ob);                                                     \
         }                                                                                               \
     }
 #pragma unroll
-        for (int d = 0; d < LH_DEPTH; d++) {
-            const int pf = d < npx ? d : npx - 1;
-            LH_FETCH(pf, d)
+            for (int d = 0; d < DEPTH; d++) {
+                const int pf = d < npx ? d : npx - 1;
+                LH_FETCH(pf, d)
+            }
+            // branch-free over all the wave's rows: rows past the wave's last pixel -- only in the launch's last tile -- repeat that pixel and are never stored
+            for (int pb = 0; pb < LC_WPX; pb += DEPTH) {
+#pragma unroll
+                for (int d = 0; d < DEPTH; d++) {
+                    const int pi = pb + d;
+#pragma unroll
+                    for (int ll = 0; ll < LPH; ll++) {
+                        wv[ll * 104 + lane] = (float)r[d][2 * ll];
+                        if (lane < 36) wv[ll * 104 + lane + 64] = (float)r[d][2 * ll + 1];
+                    }
+                    if ((lane >> 2) == (pi < npx ? pi : npx - 1) && (lane & 3) / LPH == hf) { wv[((lane & 3) - hf * LPH) * 104 + 100] = sqx; wv[((lane & 3) - hf * LPH) * 104 + 101] = sqy; }
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                    if (DEPTH < LC_WPX) {
+                        const int pf = pi + DEPTH < npx ? pi + DEPTH : npx - 1;
+                        LH_FETCH(pf, d)
+                    }
+                    const int prow = wave * LC_WPX + pi;
+#pragma unroll
+                    for (int kk = 0; kk < KK; kk++) {
+                        const float wx = wv[frac_off[kk]], wy = wv[frac_off[kk] + 1];
+                        const float* q = wv + tap_off[kk];
+                        const lk_f32x2 top = {q[0], q[1]}, bot = {q[10], q[11]};
+                        const lk_f32x2 c = top + wy * (bot - top);
+                        float v = c[0] + wx * (c[1] - c[0]);
+                        if (kk == KK - 1) v = lane < C::REAL - (KK - 1) * 64 ? v : 0.f;      // the zero padding of the half's K
+                        unsigned short h16; unsigned char lr, lv;
+                        h8_split1(v, h16, lr, lv);
+                        const int k = kk * 64 + lane;
+                        At[prow * LDA + k] = h16;
+                        unsigned char* lo8 = A8 + prow * LDA8 + h8_lo_off(k);
+                        lo8[0] = lr; lo8[4] = lv;
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                }
+            }
+#undef LH_FETCH
         }
-        for (int pb = 0; pb < LC_WPX; pb += LH_DEPTH) {
+        if (hf > 0) {
 #pragma unroll
-            for (int d = 0; d < LH_DEPTH; d++) {
-                const int pi = pb + d;
+            for (int k = 0; k < 3; k++)
 #pragma unroll
-                for (int l = 0; l < 4; l++) {
-                    wv[l * 104 + lane] = (float)r[d][2 * l];
-                    if (lane < 36) wv[l * 104 + lane + 64] = (float)r[d][2 * l + 1];
-                }
-                if ((lane >> 2) == (pi < npx ? pi : npx - 1)) { wv[(lane & 3) * 104 + 100] = sqx; wv[(lane & 3) * 104 + 101] = sqy; }
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                if (LH_DEPTH < LC_WPX) {
-                    const int pf = pi + LH_DEPTH < npx ? pi + LH_DEPTH : npx - 1;
-                    LH_FETCH(pf, d)
-                }
-                const int prow = wave * LC_WPX + pi;
+                for (int i = 0; i < 2; i++) wf[k][i] = wph[(k * 2 + i) * 64];
+        }
+        __syncthreads();
+        // ---- [64 pixels][the half's taps] x this wave's [32 channels]^T: KS16 fp16 k-steps, then KT8 fp8 k-tiles (their fragments follow the fp16 ones in the stream)
+        if (hf == 0) {
 #pragma unroll
-                for (int kk = 0; kk < 6; kk++) {
-                    const float wx = wv[frac_off[kk]], wy = wv[frac_off[kk] + 1];
-                    const float* q = wv + tap_off[kk];
-                    const lk_f32x2 top = {q[0], q[1]}, bot = {q[10], q[11]};
-                    const lk_f32x2 c = top + wy * (bot - top);
-                    float v = c[0] + wx * (c[1] - c[0]);
-                    if (kk == 5) v = lane < 4 ? v : 0.f;
-                    unsigned short h16; unsigned char lr, lv;
-                    h8_split1(v, h16, lr, lv);
-                    const int k = kk * 64 + lane;
-                    At[prow * LC_LDA + k] = h16;
-                    unsigned char* lo8 = A8 + prow * LH_LDA8 + h8_lo_off(k);
-                    lo8[0] = lr; lo8[4] = lv;
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            for (int i = 0; i < 2; i++) {
+                const f32x4 b = *reinterpret_cast<const f32x4*>(bias + wave * 32 + i * 16 + fg * 4);
+#pragma unroll
+                for (int j = 0; j < 4; j++) acc[i][j] = b;
             }
         }
-#undef LH_FETCH
-    }
-    __syncthreads();
-    // ---- [64 pixels][384 taps] x this wave's [32 channels]^T: 11 fp16 k-steps, then 6 fp8 k-tiles (their fragments follow the fp16 ones in the stream)
-    f32x4 acc[2][4];
+        const lh_i32x4* wp8 = wph + KS16 * 2 * 64;
+        lh_i32x4 w8[2][2][2];      // ring of two fp8 k-tiles: [slot][i][half]
 #pragma unroll
-    for (int i = 0; i < 2; i++) {
-        const f32x4 b = *reinterpret_cast<const f32x4*>(bias + wave * 32 + i * 16 + fg * 4);
+        for (int ks = 0; ks < ((LH_ABL & 2) ? 0 : KS16); ks++) {
+            if (ks + 3 < KS16) {
 #pragma unroll
-        for (int j = 0; j < 4; j++) acc[i][j] = b;
-    }
-    const lh_i32x4* wp8 = wp + LH_KS16 * 2 * 64;
-    lh_i32x4 w8[2][2][2];      // ring of two fp8 k-tiles: [slot][i][half]
+                for (int i = 0; i < 2; i++) wf[(ks + 3) & 3][i] = wph[((ks + 3) * 2 + i) * 64];
+            } else if (ks + 3 - KS16 < 2) {      // the first two fp8 k-tiles, requested under the last fp16 k-steps
+                const int t = ks + 3 - KS16;
 #pragma unroll
-    for (int ks = 0; ks < ((LH_ABL & 2) ? 0 : LH_KS16); ks++) {
-        if (ks + 3 < LH_KS16) {
+                for (int i = 0; i < 2; i++)
 #pragma unroll
-            for (int i = 0; i < 2; i++) wf[(ks + 3) & 3][i] = wp[((ks + 3) * 2 + i) * 64];
-        } else if (ks + 3 - LH_KS16 < 2) {      // the first two fp8 k-tiles, requested under the last fp16 k-steps
-            const int t = ks + 3 - LH_KS16;
+                    for (int h = 0; h < 2; h++) w8[t][i][h] = wp8[((t * 2 + i) * 2 + h) * 64];
+            }
+            lh_i32x4 af[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) af[j] = *reinterpret_cast<const lh_i32x4*>(At + (j * 16 + fr) * LDA + ks * 32 + fg * 8);
 #pragma unroll
             for (int i = 0; i < 2; i++)
 #pragma unroll
-                for (int h = 0; h < 2; h++) w8[t][i][h] = wp8[((t * 2 + i) * 2 + h) * 64];
+                for (int j = 0; j < 4; j++)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(lh_f16x8, wf[ks & 3][i]), __builtin_bit_cast(lh_f16x8, af[j]), acc[i][j], 0, 0, 0);
         }
-        lh_i32x4 af[4];
 #pragma unroll
-        for (int j = 0; j < 4; j++) af[j] = *reinterpret_cast<const lh_i32x4*>(At + (j * 16 + fr) * LC_LDA + ks * 32 + fg * 8);
+        for (int t = 0; t < ((LH_ABL & 2) ? 0 : KT8); t++) {
+            lh_i32x8 a8[4];
 #pragma unroll
-        for (int i = 0; i < 2; i++)
+            for (int j = 0; j < 4; j++) {
+                const unsigned char* rp = A8 + (j * 16 + fr) * LDA8 + t * 128 + fg * 16;
+                const lh_i32x4 lo = *reinterpret_cast<const lh_i32x4*>(rp), hi = *reinterpret_cast<const lh_i32x4*>(rp + 64);
+                a8[j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+            }
+            lh_i32x8 wv8[2];
 #pragma unroll
-            for (int j = 0; j < 4; j++)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(lh_f16x8, wf[ks & 3][i]), __builtin_bit_cast(lh_f16x8, af[j]), acc[i][j], 0, 0, 0);
-    }
-#pragma unroll
-    for (int t = 0; t < ((LH_ABL & 2) ? 0 : LH_KT8); t++) {
-        lh_i32x8 a8[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const unsigned char* rp = A8 + (j * 16 + fr) * LH_LDA8 + t * 128 + fg * 16;
-            const lh_i32x4 lo = *reinterpret_cast<const lh_i32x4*>(rp), hi = *reinterpret_cast<const lh_i32x4*>(rp + 64);
-            a8[j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        }
-        lh_i32x8 wv8[2];
-#pragma unroll
-        for (int i = 0; i < 2; i++) wv8[i] = __builtin_shufflevector(w8[t & 1][i][0], w8[t & 1][i][1], 0, 1, 2, 3, 4, 5, 6, 7);
-#pragma unroll
-        for (int i = 0; i < 2; i++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wv8[i], a8[j], acc[i][j], 0, 1, 0, sc_w, 0, 127);
-        if (t + 2 < LH_KT8) {
+            for (int i = 0; i < 2; i++) wv8[i] = __builtin_shufflevector(w8[t & 1][i][0], w8[t & 1][i][1], 0, 1, 2, 3, 4, 5, 6, 7);
 #pragma unroll
             for (int i = 0; i < 2; i++)
 #pragma unroll
-                for (int h = 0; h < 2; h++) w8[t & 1][i][h] = wp8[(((t + 2) * 2 + i) * 2 + h) * 64];
+                for (int j = 0; j < 4; j++) acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wv8[i], a8[j], acc[i][j], 0, 1, 0, sc_w, 0, 127);
+            if (t + 2 < KT8) {
+#pragma unroll
+                for (int i = 0; i < 2; i++)
+#pragma unroll
+                    for (int h = 0; h < 2; h++) w8[t & 1][i][h] = wp8[(((t + 2) * 2 + i) * 2 + h) * 64];
+            }
         }
+        __syncthreads();      // every wave has read the half's operand tile: the next half's taps, or the output tile, take its place
     }
-    __syncthreads();                                                  // every wave has read the operand tile: it becomes the output tile
     char* const Ot = lc_smem;                                          // [64][LH_LDO]: fp16 x 256 | correction bytes x 512
 #pragma unroll
     for (int j = 0; j < 4; j++)
@@ -672,21 +742,36 @@ __global__ __launch_bounds__(512, 2) void raft_lookup_convc1_h8_kernel(const Cor
     }
 }
 
-int raft_lkc1_h8_pack(const void* w, void* packed, hipStream_t s) {
-    const int n = LC_WAVES * (LH_KS16 * 2 * 64 + LH_KT8 * 2 * 2 * 64);
-    hipLaunchKernelGGL(raft_lkc1_h8_pack_w_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const bf16_t*)w, (lh_i32x4*)packed);
+static int g_lk_split = 1;      // the tile vtgb_raft_update launches (1: the split-K tile, two workgroups per CU)
+#ifdef VTGB_DEBUG_HOOKS
+extern "C" void vtgb_debug_set_lk_split(int v) { g_lk_split = v ? 1 : 0; }      // 0: the round-6 one-workgroup tile (same-process A/B)
+#endif
+int raft_lkc1_h8_variant() { return g_lk_split; }
+size_t raft_lkc1_h8_pack_bytes() { return LhCfg<1>::WPK_BYTES > LhCfg<0>::WPK_BYTES ? LhCfg<1>::WPK_BYTES : LhCfg<0>::WPK_BYTES; }
+template <int SPLIT>
+static int lkc1_h8_pack_t(const void* w, void* packed, hipStream_t s) {
+    const int n = LC_WAVES * LhCfg<SPLIT>::PER_WAVE;
+    hipLaunchKernelGGL(raft_lkc1_h8_pack_w_kernel<SPLIT>, dim3((n + 255) / 256), dim3(256), 0, s, (const bf16_t*)w, (lh_i32x4*)packed);
     VTGB_HIP(hipGetLastError());
     return VTGB_OK;
 }
-size_t raft_lkc1_h8_pack_bytes() { return LH_WPK_BYTES; }
-int raft_launch_lookup_convc1_h8(const CorrPyr& pyr, const float* flow, const void* wpk, const int* scale, const float* bias, void* c1, int64_t M, int H8, int W8,
-                                 hipStream_t s) {
+int raft_lkc1_h8_pack(const void* w, void* packed, int variant, hipStream_t s) { return variant ? lkc1_h8_pack_t<1>(w, packed, s) : lkc1_h8_pack_t<0>(w, packed, s); }
+template <int SPLIT>
+static int lkc1_h8_launch_t(const CorrPyr& pyr, const float* flow, const void* wpk, const int* scale, const float* bias, void* c1, int64_t M, int H8, int W8, int* occupancy,
+                            hipStream_t s) {
     static DeviceOnce attr;
-    VTGB_FUNC_LDS_ONCE(attr, raft_lookup_convc1_h8_kernel<float>, LH_LDS);
-    hipLaunchKernelGGL(raft_lookup_convc1_h8_kernel<float>, dim3((unsigned)((M + LC_PX - 1) / LC_PX)), dim3(512), LH_LDS, s, pyr, flow, (const lh_i32x4*)wpk, scale, bias,
-                       (bf16_t*)c1, M, H8, W8);
+    VTGB_FUNC_LDS_ONCE(attr, (raft_lookup_convc1_h8_kernel<float, SPLIT>), LhCfg<SPLIT>::LDS);
+    if (occupancy)      // resident workgroups per CU of THIS instantiation at its launch configuration
+        VTGB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, reinterpret_cast<const void*>(raft_lookup_convc1_h8_kernel<float, SPLIT>), 512, LhCfg<SPLIT>::LDS));
+    hipLaunchKernelGGL((raft_lookup_convc1_h8_kernel<float, SPLIT>), dim3((unsigned)((M + LC_PX - 1) / LC_PX)), dim3(512), LhCfg<SPLIT>::LDS, s, pyr, flow,
+                       (const lh_i32x4*)wpk, scale, bias, (bf16_t*)c1, M, H8, W8);
     VTGB_HIP(hipGetLastError());
     return VTGB_OK;
+}
+int raft_launch_lookup_convc1_h8(const CorrPyr& pyr, const float* flow, const void* wpk, const int* scale, const float* bias, void* c1, int64_t M, int H8, int W8,
+                                 int variant, int* occupancy, hipStream_t s) {
+    return variant ? lkc1_h8_launch_t<1>(pyr, flow, wpk, scale, bias, c1, M, H8, W8, occupancy, s)
+                   : lkc1_h8_launch_t<0>(pyr, flow, wpk, scale, bias, c1, M, H8, W8, occupancy, s);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -21,10 +21,12 @@
 // the buffers h, r h, motion | flow, corr taps, c1, [cor | flo], convf1's output; inp and the flow / mask heads' hidden maps stay bf16 pairs.
 int raft_launch_lookup_pair(const CorrPyr& pyr, const float* flow, void* out_pair, int64_t M, int H8, int W8, int h8, hipStream_t s);
 // f16c8: lookup + convc1 as one launch (raft.hip: the taps of a pixel never leave the CU)
-int raft_lkc1_h8_pack(const void* w, void* packed, hipStream_t s);
+// (variant: 1 = the split-K tile, two workgroups per CU -- what raft_lkc1_h8_variant() returns in production; 0 = the round-6 one-workgroup tile)
+int raft_lkc1_h8_variant();
+int raft_lkc1_h8_pack(const void* w, void* packed, int variant, hipStream_t s);
 size_t raft_lkc1_h8_pack_bytes();
 int raft_launch_lookup_convc1_h8(const CorrPyr& pyr, const float* flow, const void* wpk, const int* scale, const float* bias, void* c1, int64_t M, int H8, int W8,
-                                 hipStream_t s);
+                                 int variant, int* occupancy, hipStream_t s);
 int raft_launch_flow_head2(const float* P2, const float* bias, float* flow, int n_pairs, int H8, int W8, hipStream_t s);
 int raft_launch_upsample(const float* flow, const float* mask, float* flow_up, int n_pairs, int H8, int W8, hipStream_t s);
 
@@ -340,7 +342,7 @@ int raft_x3_impl(const vtgb_raft_update_args* a, Workspace& ws, hipStream_t s) {
     float* mask = (float*)ws.take(M * 576 * 4);
     float* P2 = mask;   // [M, 32] per-tap partial products of FlowHead.conv2 (the mask buffer is idle until the last iteration)
     void* zero = ws.take(256);
-    void* w1pk = ws.take(raft_lkc1_h8_pack_bytes());      // f16c8: convc1's weights in the fused lookup kernel's fragment order
+    void* w1pk = h8 ? ws.take(raft_lkc1_h8_pack_bytes()) : nullptr;      // f16c8: convc1's weights in the fused lookup kernel's fragment order
     if (ws.dry) return VTGB_OK;
     VTGB_REQUIRE(ws.ok(), VTGB_EWORKSPACE, "raft_update: workspace %zu < %zu bytes", ws.size, ws.used);
     VTGB_REQUIRE(((a->net && a->inp) || a->cnet_nhwc) && a->weights && a->flow_up, VTGB_EINVAL, "raft_update: NULL operand");
@@ -378,11 +380,12 @@ int raft_x3_impl(const vtgb_raft_update_args* a, Workspace& ws, hipStream_t s) {
         VTGB_TRY(launch_conv_gemm(mz, s));
         VTGB_TRY(launch_conv_gemm(mq, s));
     }
-    if (h8) VTGB_TRY(raft_lkc1_h8_pack(w[0], w1pk, s));
+    const int lk_variant = raft_lkc1_h8_variant();
+    if (h8) VTGB_TRY(raft_lkc1_h8_pack(w[0], w1pk, lk_variant, s));
     for (int it = 0; it < a->iters; it++) {
         // ---- BasicMotionEncoder (update.py:88-97)
         if (h8) {      // lookup + convc1 (1x1, 324 -> 256, ReLU) as one launch: the 1.5 KB-per-pixel tap tensor is never written
-            VTGB_TRY(raft_launch_lookup_convc1_h8(pyr, flow, w1pk, hs, F(w[1]), c1, M, H8, W8, s));
+            VTGB_TRY(raft_launch_lookup_convc1_h8(pyr, flow, w1pk, hs, F(w[1]), c1, M, H8, W8, lk_variant, nullptr, s));
         } else {
             VTGB_TRY(raft_launch_lookup_pair(pyr, flow, corrf, M, H8, W8, h8, s));
             VTGB_TRY(run(conv(256, 1, 1, corrf, 384, nullptr, 0, 0, 0, F(w[1]), VTGB_EPI_SPLIT, 1, c1, 512, 256)));
@@ -429,6 +432,31 @@ int raft_x3_impl(const vtgb_raft_update_args* a, Workspace& ws, hipStream_t s) {
     VTGB_TRY(launch_conv_gemm(x3_conv(Mi, 576, H8, W8, 1, 1, FH, 256, nullptr, 0, w[24], F(w[25]), VTGB_EPI_STORE_F32, 0, mask, 576, 0, zero), s));
     VTGB_TRY(raft_launch_upsample(flow, mask, a->flow_up, a->n_pairs, H8, W8, s));
     VTGB_HIP(hipGetLastError());
+    return VTGB_OK;
+}
+
+// ---- unit-level entry point of the fused f16c8 lookup + convc1 launch (include/vtgb.h: vtgb_raft_lookup_convc1)
+extern "C" int vtgb_raft_lookup_convc1(const vtgb_raft_lookup_convc1_args* a, vtgb_stream_t stream) {
+    VTGB_REQUIRE(a, VTGB_EINVAL, "raft_lookup_convc1: NULL args");
+    VTGB_REQUIRE(a->corr[0] && a->corr[1] && a->corr[2] && a->corr[3] && a->flow && a->weights && a->scale && a->bias && a->out, VTGB_EINVAL,
+                 "raft_lookup_convc1: NULL operand");
+    VTGB_REQUIRE(a->n_pairs > 0 && a->H8 >= 8 && a->W8 >= 8 && (a->variant == 0 || a->variant == 1), VTGB_EINVAL,
+                 "raft_lookup_convc1: bad dims n=%d H8=%d W8=%d variant=%d", a->n_pairs, a->H8, a->W8, a->variant);
+    const int64_t M = (int64_t)a->n_pairs * a->H8 * a->W8;
+    VTGB_REQUIRE(M < (1ll << 28), VTGB_EUNSUPPORTED, "raft_lookup_convc1: too many pixels (the flow field is addressed through one 32-bit buffer range)");
+    static void* w1pk = nullptr;      // the weights in fragment order (allocated once per process; repacked by every call)
+    if (!w1pk) VTGB_HIP(hipMalloc(&w1pk, raft_lkc1_h8_pack_bytes()));
+    CorrPyr pyr;
+    int hl = a->H8, wl = a->W8;
+    for (int l = 0; l < 4; l++) {
+        pyr.lvl[l] = a->corr[l]; pyr.h[l] = hl; pyr.w[l] = wl;
+        hl /= 2; wl /= 2;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    VTGB_TRY(raft_lkc1_h8_pack(a->weights, w1pk, a->variant, s));
+    int occ = 0;
+    VTGB_TRY(raft_launch_lookup_convc1_h8(pyr, a->flow, w1pk, a->scale, a->bias, a->out, M, a->H8, a->W8, a->variant, a->occupancy ? &occ : nullptr, s));
+    if (a->occupancy) *a->occupancy = occ;
     return VTGB_OK;
 }
 

@@ -942,6 +942,32 @@ def pair_conv(a: Tensor, w: Tensor, sw: float, H: int, W: int, a2: Optional[Tens
     return tail_out if tail_w is not None else f32 if out_f32 else out
 
 
+def raft_lookup_convc1(pyramid: Sequence[Tensor], flow: Tensor, w: Tensor, bias: Tensor, H8: int, W8: int, variant: int = 1,
+                       want_occupancy: bool = False):
+    """vtgb_raft_update's fused f16c8 launch alone (include/vtgb.h vtgb_raft_lookup_convc1): pyramid = 4 fp32 levels [M, H8 >> l, W8 >> l], flow [M, 2]
+    fp32, w [256, 324] fp32 (convc1), bias [256] -> c1 as f16c8 pair rows [M, 512] int16 (pair_unpack(., 256) gives the values).  variant 1: the
+    split-K tile of the product; 0: the whole-K tile it replaced.  want_occupancy: returns (rows, resident workgroups per CU of that instantiation)."""
+    _need_cuda(flow, *pyramid)
+    M = flow.shape[0]
+    assert M % (H8 * W8) == 0 and flow.shape == (M, 2) and w.shape == (256, 324) and len(pyramid) == 4
+    lv = [p.contiguous().float() for p in pyramid]
+    for l, p in enumerate(lv):
+        assert p.numel() == M * (H8 >> l) * (W8 >> l)
+    wk = torch.zeros(256, 1, 1, 384, dtype=torch.float32, device=flow.device)
+    wk[:, 0, 0, :324] = w.to(flow.device).float()
+    sw, byte = h8_weight_scale(wk)
+    packed = h8_conv_pack(wk, sw)
+    scale = torch.tensor([byte], dtype=torch.int32, device=flow.device)
+    fl, bias_t = flow.contiguous().float(), bias.to(flow.device).contiguous().float()
+    out = torch.zeros(M, 512, dtype=torch.int16, device=flow.device)
+    occ = L.i32(0)
+    args = L.RaftLookupConvc1Args(M // (H8 * W8), H8, W8, variant, (L.vp * 4)(*[p.data_ptr() for p in lv]), fl.data_ptr(), packed.data_ptr(), scale.data_ptr(),
+                                  bias_t.data_ptr(), out.data_ptr(), C.pointer(occ) if want_occupancy else None)
+    L.check(L.lib().vtgb_raft_lookup_convc1(C.byref(args), _stream()))
+    torch.cuda.current_stream().synchronize()      # (packed / scale are temporaries of this call)
+    return (out, occ.value) if want_occupancy else out
+
+
 class RaftWeights(_WeightTable):
     """of_extractor.update_block.* -> the packed table of vtgb_raft_update ([C_out, KH, KW, C_in] in the compute dtype)."""
 
