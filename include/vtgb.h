@@ -515,6 +515,39 @@ typedef struct {
 } vtgb_raft_lookup_convc1_args;
 int vtgb_raft_lookup_convc1(const vtgb_raft_lookup_convc1_args* a, vtgb_stream_t stream);
 
+/* Unit-level surface of vtgb_raft_update's SepConvGRU gate launches at VTGB_F16C8 / VTGB_BF16X3 (update.py:39-65): ONE half-step (half 0: the horizontal
+ * 1x5 convolutions, half 1: the vertical 5x1 ones), launched by the function the refinement loop itself calls (csrc/raft_x3.hip x3_gru_half), on the
+ * caller's buffers.  Pair rows are [M, 256 16-bit units] of 128 channels in the format `fmt` (vtgb_pair_pack), M = n_images * H8 * W8.
+ *   stage 0 -- the z | r launch: pre = conv([h | x], w_zr) + start_zr (256 in, 256 out); z = sigmoid(pre[:, :128]) -> `z` fp32 [M, 128];
+ *              sigmoid(pre[:, 128:]) * h -> `rh` as a pair row, h = the value its pair decodes to.  `h` and `x` are only read.
+ *   stage 1 -- the q launch: pre = conv([rh | x], w_q) + start_q (256 in, 128 out); h' = (1 - z) h + z tanh(pre), read from and written IN PLACE to the
+ *              pair `h_q` (which may be `h`).  `rh`, `z` and `x` are only read.
+ *   stage 2 -- both, in that order.
+ * x = [motion(126) | flow(2)]; the start maps are the loop-invariant `inp` third of the convolutions plus their bias, fp32.  w_zr / w_q are packed exactly
+ * as vtgb_raft_update's table entries [10 + 4 half] / [12 + 4 half]; scale_zr / scale_q (VTGB_F16C8 only, ignored otherwise) are DEVICE int32: the E8M0
+ * byte of 2^-11 / sw of that convolution.  Operands of a launch the stage does not run may be NULL.  The zero page of the out-of-image taps is the
+ * library's own (allocated once per process), as in vtgb_pair_conv.  VTGB_EINVAL on the host, before any launch, for NULL args, a NULL operand of a
+ * launch that runs, a bad fmt / half / stage, n_images < 1 or H8, W8 < 8, a missing scale at VTGB_F16C8.  What tests/test_gpu_gru_half.py checks
+ * against fp64 (tests/gru_ref.py). */
+typedef struct {
+    int32_t fmt;                /* VTGB_F16C8 or VTGB_BF16X3 */
+    int32_t n_images, H8, W8;   /* M = n_images * H8 * W8 pixels; H8, W8 >= 8 */
+    int32_t half;               /* 0: 1x5, 1: 5x1 */
+    int32_t stage;              /* 0: z | r launch, 1: q launch, 2: both */
+    const void* h;              /* pair rows [M, 256]: read by stage 0 */
+    void* h_q;                  /* pair rows [M, 256]: read and updated in place by stage 1 */
+    const void* x;              /* pair rows [M, 256] */
+    void* rh;                   /* pair rows [M, 256]: written by stage 0, read by stage 1 */
+    float* z;                   /* [M, 128]: written by stage 0, read by stage 1 */
+    const float* start_zr;      /* [M, 256] */
+    const float* start_q;       /* [M, 128] */
+    const void* w_zr;           /* [256, K] 16-bit units */
+    const void* w_q;            /* [128, K] 16-bit units */
+    const int32_t* scale_zr;    /* device */
+    const int32_t* scale_q;     /* device */
+} vtgb_raft_gru_half_args;
+int vtgb_raft_gru_half(const vtgb_raft_gru_half_args* a, vtgb_stream_t stream);
+
 /* CorrBlock.__init__ (raft_utils/corr.py:12-27; the all-pairs product :52-60): for every pair the correlation of each
  * pixel of image 1 with every pixel of image 2 over the `dim` = 256 features, divided by sqrt(dim), and its three
  * avg_pool2d(2, stride 2) -- one kernel, the four levels are its only output.  Pair n uses the feature maps of images

@@ -45,7 +45,7 @@ EXPORTS = [
     "vtgb_pair_pack", "vtgb_pair_conv", "vtgb_pair_conv_ex", "vtgb_attention_tiled",
     "vtgb_llm_decode_attention_split_workspace_bytes", "vtgb_llm_decode_attention_split",
     "vtgb_llm_decode_attention_split_fp8", "vtgb_llm_rope_cache_fp8", "vtgb_llm_rope_cache_prefill_fp8",
-    "vtgb_raft_lookup_convc1",
+    "vtgb_raft_lookup_convc1", "vtgb_raft_gru_half",
 ]
 COMM_ID_BYTES = 128
 
@@ -156,6 +156,12 @@ class RaftLookupConvc1Args(C.Structure):
                 ("out", vp), ("occupancy", C.POINTER(i32))]
 
 
+class RaftGruHalfArgs(C.Structure):
+    """vtgb_raft_gru_half_args: one SepConvGRU half-step's gate launches on the caller's buffers."""
+    _fields_ = [("fmt", i32), ("n_images", i32), ("H8", i32), ("W8", i32), ("half", i32), ("stage", i32), ("h", vp), ("h_q", vp), ("x", vp), ("rh", vp), ("z", vp),
+                ("start_zr", vp), ("start_q", vp), ("w_zr", vp), ("w_q", vp), ("scale_zr", vp), ("scale_q", vp)]
+
+
 class RaftCorrArgs(C.Structure):
     _fields_ = [("dtype", i32), ("n_pairs", i32), ("H8", i32), ("W8", i32), ("dim", i32), ("pairs_per_clip", i32), ("frames_per_clip", i32),
                 ("first_off", i32), ("second_off", i32), ("n_images", i32), ("scale", f32), ("fmap", vp), ("levels", vp * 4),
@@ -249,6 +255,8 @@ def lib() -> C.CDLL:
     L.vtgb_pair_conv_ex.restype = C.c_int
     L.vtgb_raft_lookup_convc1.argtypes = [C.POINTER(RaftLookupConvc1Args), vp]
     L.vtgb_raft_lookup_convc1.restype = C.c_int
+    L.vtgb_raft_gru_half.argtypes = [C.POINTER(RaftGruHalfArgs), vp]
+    L.vtgb_raft_gru_half.restype = C.c_int
     L.vtgb_raft_update.argtypes = [C.POINTER(RaftUpdateArgs), vp]
     L.vtgb_raft_update.restype = C.c_int
     L.vtgb_raft_update_workspace_bytes.argtypes = [C.POINTER(RaftUpdateArgs)]

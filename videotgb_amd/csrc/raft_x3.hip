@@ -317,6 +317,41 @@ static GemmDesc h8_conv(int M, int N, int H, int W, int KH, int KW, const void* 
     return d;
 }
 
+// ---- one SepConvGRU half-step (update.py:50-65; half 0: horizontal 1x5, half 1: vertical 5x1) as the refinement loop launches it -- the ONE place that
+// builds these launches (raft_x3_impl's loop and the unit entry vtgb_raft_gru_half).  Input channels [h(128) | motion(126) | flow(2)], the inp third comes
+// from the start maps.  stage 0: the z | r convolution with the gates in its epilogue: z = sigmoid(. + start map) -> z [M, 128] fp32, r * h -> rh pair;
+// stage 1: the q convolution over [r h | motion | flow] with the update h' = (1 - z) h + z tanh(. + start map) in ITS epilogue, in place on the pair hq
+// (the loop: hq == h); stage 2: both in order.
+struct GruHalf {
+    int M, H8, W8, half, h8;
+    const void* h; void* hq; const void* X; void* RH; float* Z;
+    const float* start_zr; const float* start_q;      // fp32 [M, 256], [M, 128]
+    const void* w_zr; const void* w_q;                // the table's entries [10 + 4 half], [12 + 4 half]
+    const int* s_zr; const int* s_q;                  // f16c8: their scale bytes
+    const void* zero;
+};
+static int x3_gru_half(const GruHalf& g, int stage, hipStream_t s) {
+    const int kh = g.half == 0 ? 1 : 5, kw = g.half == 0 ? 5 : 1;
+    auto conv = [&](int N, const void* A, const void* Wt, const int* scale, int epi, void* out, int64_t ldo) {
+        return g.h8 ? h8_conv(g.M, N, g.H8, g.W8, kh, kw, A, 128, g.X, 128, Wt, nullptr, epi, 0, out, ldo, 128, g.zero, scale)
+                    : x3_conv(g.M, N, g.H8, g.W8, kh, kw, A, 128, g.X, 128, Wt, nullptr, epi, 0, out, ldo, 128, g.zero);
+    };
+    auto run = [&](const GemmDesc& d) { return g.h8 ? launch_conv_h8(d, s) : launch_conv_gemm(d, s); };
+    if (stage != 1) {
+        GemmDesc zr = conv(256, g.h, g.w_zr, g.s_zr, VTGB_EPI_X3ZR, g.Z, 128);
+        zr.resid = g.start_zr; zr.ldr = 256; zr.aux = g.h; zr.ldaux = 256; zr.out2 = g.RH; zr.ldo2 = 256;
+        zr.algo_flops = 2.0 * g.M * 256.0 * (5 * 384);
+        VTGB_TRY(run(zr));
+    }
+    if (stage != 0) {
+        GemmDesc q = conv(128, g.RH, g.w_q, g.s_q, VTGB_EPI_X3Q, g.hq, 256);
+        q.resid = g.start_q; q.ldr = 128; q.aux = g.Z; q.ldaux = 128;
+        q.algo_flops = 2.0 * g.M * 128.0 * (5 * 384);
+        VTGB_TRY(run(q));
+    }
+    return VTGB_OK;
+}
+
 int raft_x3_impl(const vtgb_raft_update_args* a, Workspace& ws, hipStream_t s) {
     VTGB_REQUIRE(a->n_pairs > 0 && a->H8 >= 8 && a->W8 >= 8 && a->iters > 0, VTGB_EINVAL, "raft_update: bad dims n=%d H8=%d W8=%d iters=%d", a->n_pairs, a->H8,
                  a->W8, a->iters);
@@ -404,17 +439,9 @@ int raft_x3_impl(const vtgb_raft_update_args* a, Workspace& ws, hipStream_t s) {
         VTGB_TRY(run(conv(126, 3, 3, CF, 256, nullptr, 0, 8, 2, F(w[9]), VTGB_EPI_SPLIT, 1, X, 256, 128)));
         // ---- SepConvGRU (update.py:50-65): horizontal (1x5) then vertical (5x1); input channels [h(128) | motion(126) | flow(2)], the inp third comes from the start maps
         for (int half = 0; half < 2; half++) {
-            const int kh = half == 0 ? 1 : 5, kw = half == 0 ? 5 : 1, wi = 10 + 4 * half;
-            // z | r convolution with the gates in its epilogue: z = sigmoid(. + start map) -> ZR [M, 128] fp32, r * h -> RH pair; then the q
-            // convolution over [r h | motion | flow] with the update h' = (1 - z) h + z tanh(. + start map) in ITS epilogue, in place on the h pair
-            GemmDesc zr = conv(256, kh, kw, hb, 128, X, 128, wi, 3 + 2 * half, nullptr, VTGB_EPI_X3ZR, 0, ZR, 128, 128);
-            zr.resid = ZRI[half]; zr.ldr = 256; zr.aux = hb; zr.ldaux = 256; zr.out2 = RH; zr.ldo2 = 256;
-            zr.algo_flops = 2.0 * Mi * 256.0 * (5 * 384);
-            VTGB_TRY(run(zr));
-            GemmDesc q = conv(128, kh, kw, RH, 128, X, 128, wi + 2, 4 + 2 * half, nullptr, VTGB_EPI_X3Q, 0, hb, 256, 128);
-            q.resid = QI[half]; q.ldr = 128; q.aux = ZR; q.ldaux = 128;
-            q.algo_flops = 2.0 * Mi * 128.0 * (5 * 384);
-            VTGB_TRY(run(q));
+            const int wi = 10 + 4 * half, si = 3 + 2 * half;
+            const GruHalf g{Mi, H8, W8, half, h8, hb, hb, X, RH, ZR, ZRI[half], QI[half], w[wi], w[wi + 2], h8 ? hs + si : nullptr, h8 ? hs + si + 1 : nullptr, zero};
+            VTGB_TRY(x3_gru_half(g, 2, s));
         }
         // ---- FlowHead (update.py:10-18) and coords1 += delta_flow (xraft.py:145); the hidden map leaves as a bf16 pair in both modes (conv2 is a bf16x3 launch)
         if (h8) {      // conv1 with conv2's 18 per-tap products formed in its epilogue (gemm_h8.hip EPI_FTAIL: exact fp32, the hidden map is never stored)
@@ -458,6 +485,28 @@ extern "C" int vtgb_raft_lookup_convc1(const vtgb_raft_lookup_convc1_args* a, vt
     VTGB_TRY(raft_launch_lookup_convc1_h8(pyr, a->flow, w1pk, a->scale, a->bias, a->out, M, a->H8, a->W8, a->variant, a->occupancy ? &occ : nullptr, s));
     if (a->occupancy) *a->occupancy = occ;
     return VTGB_OK;
+}
+
+// ---- unit-level entry point of the SepConvGRU gate launches (include/vtgb.h: vtgb_raft_gru_half): x3_gru_half on the caller's buffers
+extern "C" int vtgb_raft_gru_half(const vtgb_raft_gru_half_args* a, vtgb_stream_t stream) {
+    VTGB_REQUIRE(a, VTGB_EINVAL, "raft_gru_half: NULL args");
+    VTGB_REQUIRE(a->fmt == VTGB_F16C8 || a->fmt == VTGB_BF16X3, VTGB_EINVAL, "raft_gru_half: bad fmt %d (VTGB_F16C8 or VTGB_BF16X3)", a->fmt);
+    VTGB_REQUIRE((a->half == 0 || a->half == 1) && a->stage >= 0 && a->stage <= 2, VTGB_EINVAL, "raft_gru_half: bad half=%d stage=%d", a->half, a->stage);
+    VTGB_REQUIRE(a->n_images > 0 && a->H8 >= 8 && a->W8 >= 8, VTGB_EINVAL, "raft_gru_half: bad dims n=%d H8=%d W8=%d", a->n_images, a->H8, a->W8);
+    const int64_t M = (int64_t)a->n_images * a->H8 * a->W8;
+    VTGB_REQUIRE(M < (1ll << 28), VTGB_EUNSUPPORTED, "raft_gru_half: too many pixels (n_images * H8 * W8 < 2^28 as in vtgb_raft_update)");
+    const int h8 = a->fmt == VTGB_F16C8, zr = a->stage != 1, q = a->stage != 0;
+    VTGB_REQUIRE(a->x && a->rh && a->z, VTGB_EINVAL, "raft_gru_half: NULL operand (x, rh and z belong to both launches)");
+    VTGB_REQUIRE(!zr || (a->h && a->start_zr && a->w_zr), VTGB_EINVAL, "raft_gru_half: NULL operand of the z | r launch (h, start_zr, w_zr)");
+    VTGB_REQUIRE(!q || (a->h_q && a->start_q && a->w_q), VTGB_EINVAL, "raft_gru_half: NULL operand of the q launch (h_q, start_q, w_q)");
+    VTGB_REQUIRE(!h8 || ((!zr || a->scale_zr) && (!q || a->scale_q)), VTGB_EINVAL, "raft_gru_half: VTGB_F16C8 needs the scale byte of every launch it runs");
+    static void* zero = nullptr;      // 256 bytes of zeros for the out-of-image taps (allocated once per process)
+    if (!zero) {
+        VTGB_HIP(hipMalloc(&zero, 256));
+        VTGB_HIP(hipMemset(zero, 0, 256));
+    }
+    const GruHalf g{(int)M, a->H8, a->W8, a->half, h8, a->h, a->h_q, a->x, a->rh, a->z, a->start_zr, a->start_q, a->w_zr, a->w_q, a->scale_zr, a->scale_q, zero};
+    return x3_gru_half(g, a->stage, (hipStream_t)stream);
 }
 
 // ---- unit-level entry points of the pair formats (include/vtgb.h: vtgb_pair_pack, vtgb_pair_conv)

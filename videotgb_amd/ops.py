@@ -968,6 +968,48 @@ def raft_lookup_convc1(pyramid: Sequence[Tensor], flow: Tensor, w: Tensor, bias:
     return (out, occ.value) if want_occupancy else out
 
 
+def raft_gru_half(fmt: int, h: Tensor, x: Tensor, start_zr: Optional[Tensor], start_q: Optional[Tensor], w_zr: Optional[Tensor], w_q: Optional[Tensor],
+                  H8: int, W8: int, half: int, stage: int = 2, rh: Optional[Tensor] = None, z: Optional[Tensor] = None, h_q: Optional[Tensor] = None):
+    """One SepConvGRU half-step of vtgb_raft_update's refinement loop alone (include/vtgb.h vtgb_raft_gru_half; fmt F16C8 or BF16X3): h, x = [motion | flow]
+    pair rows [M, 256] int16 (pair_pack), start maps fp32 [M, 256] / [M, 128], w_zr [256, kh, kw, 256] / w_q [128, kh, kw, 256] fp32 over the input
+    channels [h | x] with (kh, kw) = (1, 5) for half 0, (5, 1) for half 1 -- packed here the way RaftWeights packs the table.  stage 0: the z | r launch
+    writes z (fp32 [M, 128]) and rh (pair rows); stage 1: the q launch reads them and updates h_q IN PLACE (default: h itself, as the loop does);
+    stage 2: both.  Returns (z, rh, h_q); operands of a launch that does not run may be None."""
+    _need_cuda(h, x)
+    M, dev = h.shape[0], h.device
+    assert M % (H8 * W8) == 0 and h.shape == (M, 256) and x.shape == (M, 256) and h.dtype == torch.int16 and x.dtype == torch.int16
+    assert h.is_contiguous() and x.is_contiguous()
+    kh, kw = (1, 5) if half == 0 else (5, 1)
+    keep = []
+
+    def pack(w, co):
+        if w is None:
+            return None, None
+        assert tuple(w.shape) == (co, kh, kw, 256)
+        w = w.to(dev).float()
+        if fmt == F16C8:
+            sw, byte = h8_weight_scale(w)
+            keep.append(torch.tensor([byte], dtype=torch.int32, device=dev))
+            keep.append(h8_conv_pack(w, sw, [128, 128]))
+            return keep[-1], keep[-2]
+        keep.append(_bf16_exact(conv_k_order(split3(w, [128, 128]))))
+        return keep[-1], None
+
+    pzr, szr = pack(w_zr, 256)
+    pq, sq = pack(w_q, 128)
+    rh = torch.zeros(M, 256, dtype=torch.int16, device=dev) if rh is None else rh
+    z = torch.zeros(M, 128, dtype=torch.float32, device=dev) if z is None else z
+    h_q = h if h_q is None else h_q
+    for t, shape, dt in ((rh, (M, 256), torch.int16), (z, (M, 128), torch.float32), (h_q, (M, 256), torch.int16), (start_zr, (M, 256), torch.float32),
+                         (start_q, (M, 128), torch.float32)):
+        assert t is None or (tuple(t.shape) == shape and t.dtype == dt and t.is_contiguous() and t.device == dev)
+    args = L.RaftGruHalfArgs(fmt, M // (H8 * W8), H8, W8, half, stage, h.data_ptr(), h_q.data_ptr(), x.data_ptr(), rh.data_ptr(), z.data_ptr(), _ptr(start_zr),
+                             _ptr(start_q), _ptr(pzr), _ptr(pq), _ptr(szr), _ptr(sq))
+    L.check(L.lib().vtgb_raft_gru_half(C.byref(args), _stream()))
+    torch.cuda.current_stream().synchronize()      # (the packed weights / scales are temporaries of this call)
+    return z, rh, h_q
+
+
 class RaftWeights(_WeightTable):
     """of_extractor.update_block.* -> the packed table of vtgb_raft_update ([C_out, KH, KW, C_in] in the compute dtype)."""
 
