@@ -761,6 +761,40 @@ int vtgb_llm_decode_attention_split_fp8(int dtype, const void* q, const uint8_t*
                                         const int64_t* pos, const uint8_t* key_valid /* NULL: none */, void* workspace, int32_t B, int32_t nq,
                                         int32_t nkv, int32_t hd, int32_t tmax, float scale, vtgb_stream_t stream);
 
+/* ---- LoRA adapters on the language model's q / k / v projections (lora.hip; added at version 601 without a bump).  An in-place low-rank
+ *   update of a projection's output -- videotgb_amd.train.LoraLinear.forward in eval mode (peft 0.4.0 tuners.lora.Linear, unmerged, fp32
+ *   adapters), rounding for rounding:
+ *     for each segment s, row m, column j in [0, n_s):
+ *       t[m, i] = sum_k A_s[i, k] * float(x[m, k])              fp32 accumulation, i < r_s
+ *       u       = sum_i B_s[j, i] * t[m, i]                      fp32
+ *       d       = rnd(u * scaling_s)                             fp32 product, ONE rounding to `dtype`
+ *       y[m, col0_s + j] = rnd(y[m, col0_s + j] + d)
+ *   x [rows, K] (row stride ldx) and y [rows, n_cols] (row stride ldy) are `dtype` (VTGB_F32 or VTGB_BF16, both the same); A_s [r_s, K] and
+ *   B_s [n_s, r_s] fp32 row-major; 1 <= r_s <= VTGB_LORA_MAX_RANK; 1 .. VTGB_LORA_MAX_SEGMENTS segments, disjoint column ranges of y.
+ *   Columns outside every segment keep their bits.  Any rows > 0 (the decode step's <= 128, the prefill's B * P).  The order of every sum
+ *   is fixed by (K, r_s): a row's bits do not depend on rows, on its neighbours or on the launch grid.  No atomics, no workspace.
+ *   Checked on the host before any launch -- VTGB_EINVAL: NULL args / x / y / A / B, a dtype other than the two, n_seg outside 1 ..
+ *   VTGB_LORA_MAX_SEGMENTS, r outside 1 .. VTGB_LORA_MAX_RANK, non-positive rows / K / n_cols / n, ldx < K, ldy < n_cols, a segment past
+ *   n_cols, overlapping segments; VTGB_EUNSUPPORTED: K or ldx not a multiple of 4, x not aligned to four elements, y not to one, A not
+ *   16-byte or B not 4-byte aligned. */
+#define VTGB_LORA_MAX_SEGMENTS 4
+#define VTGB_LORA_MAX_RANK 64
+typedef struct {
+    const float* A;                      /* [r, K]                    */
+    const float* B;                      /* [n, r]                    */
+    int32_t r, n, col0;                  /* y columns [col0, col0 + n) */
+    float scaling;                       /* lora_alpha / r            */
+} vtgb_llm_lora_seg;
+typedef struct {
+    int32_t dtype;                       /* of x and y */
+    int32_t K, n_cols, n_seg;
+    int64_t rows, ldx, ldy;              /* row strides in elements */
+    const void* x;
+    void* y;
+    vtgb_llm_lora_seg seg[VTGB_LORA_MAX_SEGMENTS];
+} vtgb_llm_lora_args;
+int vtgb_llm_lora(const vtgb_llm_lora_args* a, vtgb_stream_t stream);
+
 size_t vtgb_pack_skinny_weight_bytes(int32_t N, int32_t K);
 int vtgb_pack_skinny_weight(const void* w, int64_t ldw, int32_t N, int32_t K, void* dst, vtgb_stream_t stream);
 size_t vtgb_gemm_skinny_workspace_bytes(const vtgb_gemm_skinny_args* a);

@@ -45,7 +45,7 @@ EXPORTS = [
     "vtgb_pair_pack", "vtgb_pair_conv", "vtgb_pair_conv_ex", "vtgb_attention_tiled",
     "vtgb_llm_decode_attention_split_workspace_bytes", "vtgb_llm_decode_attention_split",
     "vtgb_llm_decode_attention_split_fp8", "vtgb_llm_rope_cache_fp8", "vtgb_llm_rope_cache_prefill_fp8",
-    "vtgb_raft_lookup_convc1", "vtgb_raft_gru_half",
+    "vtgb_raft_lookup_convc1", "vtgb_raft_gru_half", "vtgb_llm_lora",
 ]
 COMM_ID_BYTES = 128
 
@@ -178,6 +178,20 @@ class GemmSkinnyArgs(C.Structure):
                 ("out_dtype", i32), ("w_tiled", i32), ("workspace", vp), ("workspace_bytes", sz), ("defer_reduce", i32)]
 
 
+class LlmLoraSeg(C.Structure):
+    """vtgb_llm_lora_seg: one adapter -- fp32 A [r, K], B [n, r] -- on y's columns [col0, col0 + n)."""
+    _fields_ = [("A", vp), ("B", vp), ("r", i32), ("n", i32), ("col0", i32), ("scaling", f32)]
+
+
+LORA_MAX_SEGMENTS, LORA_MAX_RANK = 4, 64
+
+
+class LlmLoraArgs(C.Structure):
+    """vtgb_llm_lora_args: the in-place low-rank update of a projection's output (unmerged LoRA adapters)."""
+    _fields_ = [("dtype", i32), ("K", i32), ("n_cols", i32), ("n_seg", i32), ("rows", i64), ("ldx", i64), ("ldy", i64), ("x", vp), ("y", vp),
+                ("seg", LlmLoraSeg * LORA_MAX_SEGMENTS)]
+
+
 class LlmRopeCacheFp8Args(C.Structure):
     """vtgb_llm_rope_cache_fp8_args: the decode step's rotary + append into the fp8 K/V cache (exactly one of qkv / part)."""
     _fields_ = [("dtype", i32), ("B", i32), ("nq", i32), ("nkv", i32), ("hd", i32), ("tmax", i32), ("n_splits", i32), ("qkv", vp), ("part", vp),
@@ -298,6 +312,8 @@ def lib() -> C.CDLL:
     L.vtgb_llm_decode_attention_split_fp8.restype = C.c_int
     L.vtgb_llm_rope_cache_fp8.argtypes = [C.POINTER(LlmRopeCacheFp8Args), vp]
     L.vtgb_llm_rope_cache_fp8.restype = C.c_int
+    L.vtgb_llm_lora.argtypes = [C.POINTER(LlmLoraArgs), vp]
+    L.vtgb_llm_lora.restype = C.c_int
     L.vtgb_llm_rope_cache_prefill_fp8.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     L.vtgb_llm_rope_cache_prefill_fp8.restype = C.c_int
     L.vtgb_gemm_skinny_splits.argtypes = [C.POINTER(GemmSkinnyArgs)]

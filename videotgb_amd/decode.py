@@ -83,6 +83,58 @@ def weights_key(lm):
     return tuple((p._version, p.data_ptr()) for p in lm.parameters())
 
 
+_LORA_PROJECTIONS = ("q_proj", "k_proj", "v_proj")
+
+
+def _lora_modules(lm):
+    """(name, module) of every module that carries adapters (``lora_A`` / ``lora_B`` children, peft's layout; an object that is no
+    nn.Module has no modules)."""
+    if not isinstance(lm, torch.nn.Module):
+        return []
+    return [(n, m) for n, m in lm.named_modules() if hasattr(m, "lora_A") or hasattr(m, "lora_B")]
+
+
+def lora_state(lm) -> Optional[str]:
+    """None: ``lm`` has no LoRA adapters; "ok": the graph decoders serve its adapters (train.LoraLinear on q_proj / k_proj / v_proj of a
+    Llama's attention layers: fp32 "default" adapters, no bias, no active dropout), unmerged, as LoraLinear.forward computes them; any other
+    string: why they do not -- the decoders raise NotImplementedError with it and ``plan_decode`` hands the request to HF generate, which runs
+    the modules' own forward.  Never "decoded as the base model"."""
+    mods = _lora_modules(lm)
+    if not mods:
+        return None
+    from .train import LoraLinear
+    if getattr(lm.config, "model_type", "") == "t5":
+        return f"LoRA adapters on a T5 language model ({mods[0][0]}): the T5 graph decoder does not apply adapters"
+    layers = getattr(getattr(lm, "model", None), "layers", None) or ()
+    served = {id(getattr(l.self_attn, p, None)) for l in layers if hasattr(l, "self_attn") for p in _LORA_PROJECTIONS}
+    for name, m in mods:
+        if not isinstance(m, LoraLinear):
+            return f"{name}: adapters on a {type(m).__name__}, not a videotgb_amd.train.LoraLinear"
+        if id(m) not in served:
+            return f"{name}: adapters outside q_proj / k_proj / v_proj of the attention layers"
+        if "default" not in m.lora_A or "default" not in m.lora_B:
+            return f"{name}: no \"default\" adapter"
+        A, B = m.lora_A["default"].weight, m.lora_B["default"].weight
+        if A.dtype != torch.float32 or B.dtype != torch.float32:
+            return f"{name}: adapters are {A.dtype} / {B.dtype}, not fp32"
+        if m.bias is not None or m.lora_A["default"].bias is not None or m.lora_B["default"].bias is not None:
+            return f"{name}: a LoraLinear with a bias"
+        p = float(getattr(m.lora_dropout["default"], "p", 0.0)) if "default" in m.lora_dropout else 0.0
+        if (lm.training or m.training) and p > 0.0:
+            return f"{name}: training mode with lora_dropout={p} (HF generate applies the dropout; call .eval())"
+        if not 1 <= A.shape[0] <= L.LORA_MAX_RANK:
+            return f"{name}: rank {A.shape[0]} outside 1..{L.LORA_MAX_RANK}"
+    return "ok"
+
+
+def _lora_servable(lm) -> bool:
+    """NotImplementedError(reason) for adapters the decoders do not serve; whether there are adapters to apply."""
+    state = lora_state(lm)
+    if state not in (None, "ok"):
+        raise NotImplementedError(f"LoRA adapters outside the graph decoder's envelope -- {state}")
+    return state == "ok"
+
+
 def _padding(attention_mask: Optional[Tensor], B: int, P: int) -> Optional[Tensor]:
     """The decoders' view of a prompt mask: None when there is none or it is all ones (the unpadded path, unchanged), else the mask.
     Rejects what HF would not decode the same way here: a shape other than [B, P], values other than 0 / 1, a row without a token."""
@@ -279,6 +331,7 @@ class GreedyDecoder(_GraphDecoder):
         cfg = lm.config
         if "llama" not in cfg.model_type:
             raise NotImplementedError("GreedyDecoder handles Llama-architecture models; use HF generate otherwise")
+        has_lora = _lora_servable(lm)
         super().__init__(lm, fused, weights, kv_cache)
         wdt = lm.lm_head.weight.dtype
         if self.kv_cache == "fp8" and wdt != torch.bfloat16 and (fused or wdt != torch.float32):
@@ -305,6 +358,14 @@ class GreedyDecoder(_GraphDecoder):
                                 prep(m.down_proj.weight)))
         self.head_w = prep(lm.lm_head.weight)
         self.inter = cfg.intermediate_size
+        # LoRA adapters (train.LoraLinear on q / k / v), UNMERGED: per layer the (col0, A, B, scaling) segments of the fused q|k|v output that
+        # ops.lora_update (vtgb_llm_lora) and ``_layer`` add after the base projection -- references to the model's own fp32 parameters, so the
+        # base stream stays the packed weights above (bf16, or fp8's q * scale).  None: no adapters, nothing below changes.
+        self.lora = None
+        if has_lora:
+            col0 = dict(q_proj=0, k_proj=self.nh * self.hd, v_proj=(self.nh + self.nkv) * self.hd)
+            self.lora = [[(col0[p], m.lora_A["default"].weight.detach(), m.lora_B["default"].weight.detach(), float(m.scaling))
+                          for p in _LORA_PROJECTIONS for m in (getattr(l.self_attn, p),) if hasattr(m, "lora_A")] for l in lm.model.layers]
         self._skinny = None           # per layer (wqkv, wo, wgu, wd) + lm_head in vtgb_gemm_skinny's tiled layout, built on first use
 
     # Projections of the decode step through libvtgb.so's own weight-streaming GEMM (vtgb_gemm_skinny, tiled weights), at every batch
@@ -322,6 +383,9 @@ class GreedyDecoder(_GraphDecoder):
             self._skinny.append(pack(self.head_w))
         return self._skinny
 
+    def _lora_of(self, li: int):
+        return self.lora[li] if self.lora is not None else ()
+
     def _use_skinny(self, B: int, dtype) -> bool:
         H, I = self.cfg.hidden_size, self.inter
         return self.fused and dtype == torch.bfloat16 and B <= self.SKINNY_MAX_BATCH and H % 64 == 0 and I % 64 == 0 and (self.nh * self.hd) % 64 == 0
@@ -332,16 +396,22 @@ class GreedyDecoder(_GraphDecoder):
         emb = torch.cat((fr, fr), dim=-1)
         return emb.cos().to(dtype), emb.sin().to(dtype)
 
-    def _layer(self, x, w, cos, sin, kc, vc, pos_idx, mask, codes=None):
+    def _layer(self, x, w, cos, sin, kc, vc, pos_idx, mask, codes=None, lora=()):
         """x [B, S, H]; cos/sin [S, hd] (padded batches: [B, 1, S, hd], per-row positions); kc/vc [B, nkv, Tmax, hd]; pos_idx [S] cache rows
         to write; mask additive, broadcast to [B, 1, S, Tmax].  kv_cache="fp8": k and v pass through dq(q(.)) before the cache write and
         the attention -- the kernel-independent statement of the model.  ``codes`` = (kc8, vc8, ks, vs) of an fp8 state (prefill only,
-        pos_idx = 0 .. S-1; kc / vc None): codes and scales go to the cache and the attention runs over the prompt's own dequantised K/V."""
+        pos_idx = 0 .. S-1; kc / vc None): codes and scales go to the cache and the attention runs over the prompt's own dequantised K/V.
+        ``lora``: the layer's adapter segments (``self.lora[li]``), added to q|k|v as train.LoraLinear.forward adds them."""
         ln1, wqkv, wo, ln2, wgu, wd = w
         B, S, _ = x.shape
         nq, nkv, hd = self.nh, self.nkv, self.hd
         h = _rms(x, ln1, self.eps)
-        qkv = F.linear(h, wqkv).view(B, S, nq + 2 * nkv, hd).transpose(1, 2)      # [B, heads, S, hd]
+        qkv = F.linear(h, wqkv)
+        for c0, la, lb, scaling in lora:      # result + (lora_B(lora_A(x.float())) * scaling).to(result.dtype), per adapted projection
+            n = lb.shape[0]
+            qkv = torch.cat((qkv[..., :c0], qkv[..., c0: c0 + n] + (F.linear(F.linear(h.to(la.dtype), la), lb) * scaling).to(qkv.dtype),
+                             qkv[..., c0 + n:]), dim=-1)
+        qkv = qkv.view(B, S, nq + 2 * nkv, hd).transpose(1, 2)      # [B, heads, S, hd]
         qk = qkv[:, : nq + nkv]
         qk = qk * cos + _rot_half(qk) * sin                                        # rotary on q and k together
         q, k, v = qk[:, :nq], qk[:, nq:], qkv[:, nq + nkv:]
@@ -411,7 +481,10 @@ class GreedyDecoder(_GraphDecoder):
         delta = None
         for li, (ln1, wqkv, wo, ln2, wgu, wd) in enumerate(self.layers):
             L.check(lib.vtgb_llm_rmsnorm(code, _ptr(x), _ptr(delta), _ptr(ln1), _ptr(h), M, H, self.eps, stream))
-            qkv = ops.gemm(h, wqkv).view(B, P, nh + 2 * nkv, hd)
+            qkv = ops.gemm(h, wqkv)
+            if self.lora is not None and self.lora[li]:      # the adapters act on q|k|v before rotary and before K/V are quantised, as in the model
+                ops.lora_update(h, qkv, self.lora[li])
+            qkv = qkv.view(B, P, nh + 2 * nkv, hd)
             # rotary on q and k in place + k / v into the cache rows 0 .. P-1: one launch (HF's roundings in the model's dtype)
             if st["attn"] == "split_fp8":      # codes + scales into the cache, the dequantised k / v back into qkv for the attention below
                 L.check(lib.vtgb_llm_rope_cache_prefill_fp8(code, _ptr(qkv), _ptr(st["kc8"][li]), _ptr(st["vc8"][li]), _ptr(st["ks"][li]),
@@ -548,7 +621,10 @@ class GreedyDecoder(_GraphDecoder):
         delta, dS = None, 1
         for li, (ln1, wqkv, wo, ln2, wgu, wd) in enumerate(self.layers):
             norm(delta, dS, ln1)
-            qkv, qS = lin_d(h, li, 0, "sk_qkv")
+            if self.lora is not None and self.lora[li]:      # adapters: q|k|v materialised (this one projection is not deferred), updated in place
+                qkv, qS = ops.lora_update(h, lin(h, li, 0, "sk_qkv"), self.lora[li]), 1
+            else:
+                qkv, qS = lin_d(h, li, 0, "sk_qkv")
             if fp8_kv:
                 kv8 = (st["kc8"][li], st["vc8"][li], st["ks"][li], st["vs"][li])
                 ra = L.LlmRopeCacheFp8Args(code, B, nq, nkv, hd, tmax, qS if qS > 1 else 0, None if qS > 1 else _ptr(qkv), _ptr(ws) if qS > 1 else None,
@@ -591,7 +667,7 @@ class GreedyDecoder(_GraphDecoder):
             cos, sin = st["cos"].index_select(0, pos), st["sin"].index_select(0, pos)
             mask = torch.where(st["ar"][None, None, None, :] <= pos, 0.0, neg).to(x.dtype)
         for li, w in enumerate(self.layers):
-            x = self._layer(x, w, cos, sin, st["kc"][li], st["vc"][li], pos, mask)
+            x = self._layer(x, w, cos, sin, st["kc"][li], st["vc"][li], pos, mask, lora=self._lora_of(li))
         self._emit(st, self._head(x[:, -1]))
 
     @torch.no_grad()
@@ -649,11 +725,12 @@ class GreedyDecoder(_GraphDecoder):
             last = self._prefill_hip(st, x, P, pos_ids, key_mask)
         elif fp8_state:      # a prompt past the prefill kernels' bound into an fp8 state: quantised on the torch path
             for li, w in enumerate(self.layers):
-                x = self._layer(x, w, cos, sin, None, None, pidx, causal, codes=(st["kc8"][li], st["vc8"][li], st["ks"][li], st["vs"][li]))
+                x = self._layer(x, w, cos, sin, None, None, pidx, causal, codes=(st["kc8"][li], st["vc8"][li], st["ks"][li], st["vs"][li]),
+                                lora=self._lora_of(li))
             last = x[:, -1]
         else:
             for li, w in enumerate(self.layers):
-                x = self._layer(x, w, cos, sin, st["kc"][li], st["vc"][li], pidx, causal)
+                x = self._layer(x, w, cos, sin, st["kc"][li], st["vc"][li], pidx, causal, lora=self._lora_of(li))
             last = x[:, -1]
         self._reset(st, ending, P)
         first = self._pick(st, self._head(last), 0)      # the first token comes from the prefill, eagerly; the loop replays the other N - 1
@@ -686,6 +763,7 @@ class T5GreedyDecoder(_GraphDecoder):
             raise NotImplementedError("decode_weights='fp8' is implemented for the Llama decoder only")
         if check_kv_cache(kv_cache) != "bf16":
             raise NotImplementedError("kv_cache='fp8' is implemented for the Llama decoder only")
+        _lora_servable(lm)      # (a T5 with adapters is never servable: NotImplementedError)
         super().__init__(lm, fused, weights, kv_cache)
         self.H, self.dk, self.D = cfg.num_heads, cfg.d_kv, cfg.d_model
         self.eps = cfg.layer_norm_epsilon
@@ -1000,6 +1078,8 @@ def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: E
     if not inputs_embeds.is_cuda or not ("llama" in mt or mt == "t5"):
         return None
     if set(request) - env.keys or (env.need_max_new and "max_new_tokens" not in request):
+        return None
+    if lora_state(lm) not in (None, "ok"):      # adapters the decoders do not apply: HF generate runs the modules' own forward
         return None
     if any(k in request and request[k] not in ok for k, ok in env.neutral.items()):
         return None

@@ -471,6 +471,23 @@ def decode_attention_fp8(q: Tensor, kc8: Tensor, vc8: Tensor, ks: Tensor, vs: Te
     return out
 
 
+def lora_update(x: Tensor, y: Tensor, segments) -> Tensor:
+    """Unmerged LoRA adapters on a projection's output, in place (vtgb_llm_lora): for every ``(col0, A, B, scaling)`` of ``segments`` (1 .. 4,
+    disjoint column ranges), ``y[:, col0 : col0 + n] += ((x.float() @ A.T) @ B.T * scaling).to(y.dtype)`` -- train.LoraLinear.forward in eval
+    mode, rounding for rounding.  x [rows, K] and y [rows, n_cols] bf16 or fp32 (the same), unit column stride, any row stride; A [r, K] and
+    B [n, r] fp32 contiguous.  Returns ``y``.  The library checks the rest (include/vtgb.h) and raises through ``_lib.check``."""
+    _need_cuda(x, y, *(t for _, A, B, _ in segments for t in (A, B)))
+    assert x.dim() == 2 and y.dim() == 2 and x.shape[0] == y.shape[0] and x.dtype == y.dtype, "lora_update: x [rows, K] and y [rows, n_cols] of one dtype"
+    assert x.stride(1) == 1 and y.stride(1) == 1, "lora_update: unit column stride"
+    a = L.LlmLoraArgs(dtype_code(y.dtype), x.shape[1], y.shape[1], len(segments), x.shape[0], x.stride(0), y.stride(0), _ptr(x), _ptr(y))
+    for s, (col0, A, B, scaling) in enumerate(segments[:L.LORA_MAX_SEGMENTS]):
+        assert A.dtype == B.dtype == torch.float32 and A.is_contiguous() and B.is_contiguous(), "lora_update: fp32 contiguous adapters"
+        assert A.dim() == 2 and B.dim() == 2 and A.shape[1] == x.shape[1] and B.shape[1] == A.shape[0], "lora_update: A [r, K], B [n, r]"
+        a.seg[s] = L.LlmLoraSeg(_ptr(A), _ptr(B), A.shape[0], B.shape[0], int(col0), float(scaling))
+    L.check(L.lib().vtgb_llm_lora(C.byref(a), _stream()))
+    return y
+
+
 def layernorm(x: Tensor, gamma: Tensor, beta: Tensor, eps: float, out_dtype=torch.float32) -> Tensor:
     _need_cuda(x, gamma, beta)
     x = x.contiguous().float()
