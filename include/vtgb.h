@@ -391,7 +391,8 @@ int vtgb_layernorm(const vtgb_layernorm_args* a, vtgb_stream_t stream);
  * three: VTGB_BF16 = bf16 MFMA implicit-GEMM convolutions over NHWC bf16 activations, fp32 accumulation, fp32
  * hidden state / flow / norms, IEEE-half correlation pyramid (a reduced-precision mode the reference does not have);
  * VTGB_F32 = fp32 operands and FMAs everywhere, k summed in order -- the exactness mode, which is how the reference
- * runs RAFT (xraft.py:118-119; since version 500 on the fp32-input matrix instruction, the same fmaf chain bit for bit).
+ * runs RAFT (xraft.py:118-119; since version 500 on the fp32-input matrix instruction, the same fmaf chain bit for bit; the convolutions sum k in
+ * four interleaved in-order chains, added in a fixed order: a quarter of one chain's rounding error, csrc/conv_f32.hip).
  * VTGB_BF16X3 (version 500) = the reference's fp32 ACCURACY on the bf16 matrix cores: every convolution operand is a bf16 pair
  * (hi = bf16(x), lo = bf16(x - hi): 16 significant bits), x . w ~ hi . Wh + lo . Wh + hi . Wl with fp32 accumulation; activations
  * are stored as rows [hi(C) | lo(C)], gates / flow / correlation pyramid / lookup stay fp32 (the pyramid from split-bf16 products).
@@ -547,6 +548,62 @@ typedef struct {
     const int32_t* scale_q;     /* device */
 } vtgb_raft_gru_half_args;
 int vtgb_raft_gru_half(const vtgb_raft_gru_half_args* a, vtgb_stream_t stream);
+
+/* Unit-level surface of RAFT's implicit-GEMM convolution launches at VTGB_BF16X3, VTGB_BF16 and VTGB_F32 (every RAFT convolution that is not an f16c8
+ * launch): ONE launch_conv_gemm on the caller's buffers, its descriptor built by the helpers the production callers use (csrc/conv_descs.h: enc_conv /
+ * enc_stem_conv of vtgb_raft_encoder for site 0, x3_conv / conv_desc of vtgb_raft_update for site 1), plus the moments finish when `moments` is given.
+ *   out[m][n] = act(sum over taps (ty, tx) and channels c of x[img][oy * stride + ty - KH/2][ox * stride + tx - KW/2][c] * w[n][ty][tx][c] + bias[n])
+ * over NHWC rows, m = (img * H + oy) * W + ox on the H x W OUTPUT grid; the input grid is Hi x Wi (0 = the output grid), out-of-image taps read zeros
+ * (the library's own zero page, allocated once per process, as in vtgb_pair_conv).  Even kernels pad KH/2 before and KH/2 - 1 behind (the 4 x 1 stem GEMM
+ * over the packed rows: taps oy - 2 .. oy + 1).  x = C1 channels from `a` (+ C2 more from `a2`: a virtual concatenation), contiguous rows:
+ *   VTGB_BF16X3: bf16 pair rows [hi(C) | lo(C)] (vtgb_pair_pack), weights [N, taps, 3 (C1 + C2)] bf16 with the blocks [Wh | Wh | Wl] per source;
+ *   VTGB_BF16: bf16 rows [C], weights [N, taps, C1 + C2] bf16;   VTGB_F32: fp32 rows, fp32 weights -- all in the kernels' K order (64-channel chunk
+ *   major, tap minor), as the production tables pack them.
+ * site 0 (encoders): K x K or the 4 x 1 stem, one source, stride 1 or 2.  site 1 (update block): KH x KW, one or two sources, stride 1; at VTGB_BF16 /
+ * VTGB_F32 a 1 x 1 convolution is the plain GEMM the update block launches (out_scale applies there: mask.2's 0.25).
+ * out_kind: VTGB_CONV_OUT_F32 fp32 rows [M, ld_out]; VTGB_CONV_OUT_PAIR_BF16 / _PAIR_F16C8 (VTGB_BF16X3 only): pair rows [M, 2 ld_out] 16-bit units, the
+ * lo half at unit ld_out; VTGB_CONV_OUT_BF16 (VTGB_BF16 only): bf16 rows [M, ld_out], optionally out = [relu](act(.) + resid) (a ResidualBlock's tail,
+ * resid bf16 rows [M, ld_resid]) or, with tail_w ([32, 256] bf16, N == 256), tail_out [M, 32] fp32 = act(.) as bf16 times tail_w^T instead of `out`.
+ * moments (site 0, fp32 rows, H * W >= 256, N <= 128): [n_images, N, 2] fp32 = per image and channel the (sum, sum of squares) of the stored values, by the
+ * epilogue's per-tile slots and launch_stats_finish_tiles as the encoders chain them; stats_part: scratch of >= (M / 256 + 2) * 128 * 4 floats (the
+ * encoders' sizing), stats_part_floats its size.
+ * Not expressible here: the gate epilogues (EPI_X3ZR / EPI_X3Q: vtgb_raft_gru_half), the unfused bf16 GRU (EPI_GRU, gate_from, frag_out / init_frag: reachable
+ * only with the fused GRU kernel switched off by a debug hook) and raft_stem_pack_kernel (the caller provides the packed rows).
+ * VTGB_EINVAL on the host, before any launch, for NULL args, a NULL operand, a bad dtype / out_kind / site / act / stride, non-positive sizes, C1 or C2
+ * not a multiple of 64, a geometry the site does not have, an out_kind the dtype does not have, resid / tail_w / out_scale outside their out_kind,
+ * moments with H * W < 256, a non-fp32 output, site 1 or a short stats_part.  What launch_conv_gemm refuses keeps its own code and message.  What
+ * tests/test_gpu_conv_launch.py checks against fp64 (tests/conv_ref.py). */
+#define VTGB_CONV_OUT_F32 0
+#define VTGB_CONV_OUT_PAIR_BF16 1
+#define VTGB_CONV_OUT_PAIR_F16C8 2
+#define VTGB_CONV_OUT_BF16 3
+typedef struct {
+    int32_t dtype;              /* VTGB_F32, VTGB_BF16 or VTGB_BF16X3 */
+    int32_t out_kind;           /* VTGB_CONV_OUT_* */
+    int32_t site;               /* 0: encoder builders, 1: update-block builders */
+    int32_t n_images, H, W;     /* output grid: M = n_images * H * W rows */
+    int32_t KH, KW, stride;     /* stride 1 or 2 */
+    int32_t Hi, Wi;             /* input grid; 0 = H, W */
+    int32_t C1, C2;             /* channels per source (multiples of 64; C2 = 0: one source) */
+    int32_t N;                  /* output channels */
+    int32_t act;                /* 0 none, 1 relu, 2 sigmoid */
+    int32_t post_relu;          /* with resid */
+    float out_scale;            /* 0 = 1 */
+    const void* a;
+    const void* a2;
+    const void* weights;
+    const float* bias;          /* [N] or NULL */
+    void* out;
+    int64_t ld_out;             /* >= N; pair rows: 16-bit units per half */
+    float* moments;             /* [n_images, N, 2] or NULL */
+    float* stats_part;
+    int64_t stats_part_floats;
+    const void* resid;          /* VTGB_CONV_OUT_BF16: bf16 rows [M, ld_resid] or NULL */
+    int64_t ld_resid;
+    const void* tail_w;         /* VTGB_CONV_OUT_BF16: [32, 256] bf16 or NULL */
+    float* tail_out;            /* [M, 32] */
+} vtgb_conv_launch_args;
+int vtgb_conv_launch(const vtgb_conv_launch_args* a, vtgb_stream_t stream);
 
 /* CorrBlock.__init__ (raft_utils/corr.py:12-27; the all-pairs product :52-60): for every pair the correlation of each
  * pixel of image 1 with every pixel of image 2 over the `dim` = 256 features, divided by sqrt(dim), and its three

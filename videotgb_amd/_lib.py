@@ -45,7 +45,7 @@ EXPORTS = [
     "vtgb_pair_pack", "vtgb_pair_conv", "vtgb_pair_conv_ex", "vtgb_attention_tiled",
     "vtgb_llm_decode_attention_split_workspace_bytes", "vtgb_llm_decode_attention_split",
     "vtgb_llm_decode_attention_split_fp8", "vtgb_llm_rope_cache_fp8", "vtgb_llm_rope_cache_prefill_fp8",
-    "vtgb_raft_lookup_convc1", "vtgb_raft_gru_half", "vtgb_llm_lora",
+    "vtgb_raft_lookup_convc1", "vtgb_raft_gru_half", "vtgb_llm_lora", "vtgb_conv_launch",
 ]
 COMM_ID_BYTES = 128
 
@@ -162,6 +162,18 @@ class RaftGruHalfArgs(C.Structure):
                 ("start_zr", vp), ("start_q", vp), ("w_zr", vp), ("w_q", vp), ("scale_zr", vp), ("scale_q", vp)]
 
 
+CONV_OUT_F32, CONV_OUT_PAIR_BF16, CONV_OUT_PAIR_F16C8, CONV_OUT_BF16 = 0, 1, 2, 3
+CONV_SITE_ENCODER, CONV_SITE_UPDATE = 0, 1
+
+
+class ConvLaunchArgs(C.Structure):
+    """vtgb_conv_launch_args: one implicit-GEMM convolution launch (bf16x3 / bf16 / fp32) on the caller's buffers."""
+    _fields_ = [("dtype", i32), ("out_kind", i32), ("site", i32), ("n_images", i32), ("H", i32), ("W", i32), ("KH", i32), ("KW", i32), ("stride", i32),
+                ("Hi", i32), ("Wi", i32), ("C1", i32), ("C2", i32), ("N", i32), ("act", i32), ("post_relu", i32), ("out_scale", f32), ("a", vp), ("a2", vp),
+                ("weights", vp), ("bias", vp), ("out", vp), ("ld_out", i64), ("moments", vp), ("stats_part", vp), ("stats_part_floats", i64), ("resid", vp),
+                ("ld_resid", i64), ("tail_w", vp), ("tail_out", vp)]
+
+
 class RaftCorrArgs(C.Structure):
     _fields_ = [("dtype", i32), ("n_pairs", i32), ("H8", i32), ("W8", i32), ("dim", i32), ("pairs_per_clip", i32), ("frames_per_clip", i32),
                 ("first_off", i32), ("second_off", i32), ("n_images", i32), ("scale", f32), ("fmap", vp), ("levels", vp * 4),
@@ -271,6 +283,8 @@ def lib() -> C.CDLL:
     L.vtgb_raft_lookup_convc1.restype = C.c_int
     L.vtgb_raft_gru_half.argtypes = [C.POINTER(RaftGruHalfArgs), vp]
     L.vtgb_raft_gru_half.restype = C.c_int
+    L.vtgb_conv_launch.argtypes = [C.POINTER(ConvLaunchArgs), vp]
+    L.vtgb_conv_launch.restype = C.c_int
     L.vtgb_raft_update.argtypes = [C.POINTER(RaftUpdateArgs), vp]
     L.vtgb_raft_update.restype = C.c_int
     L.vtgb_raft_update_workspace_bytes.argtypes = [C.POINTER(RaftUpdateArgs)]

@@ -1,5 +1,5 @@
 // conv_f32.hip -- exactness mode (VTGB_F32) of launch_conv_gemm: the implicit-GEMM convolution / plain GEMM
-// that RAFT's encoders and update block run on, with fp32 operands, fp32 FMAs and k summed in order
+// that RAFT's encoders and update block run on, with fp32 operands and fp32 FMAs, k summed in four interleaved in-order chains
 // (the reference runs RAFT in fp32: src/models/components/xraft.py:118-119).  Same GemmDesc, same NHWC
 // activation layout, same K order (64-channel chunk major, tap minor) and the same epilogues as the bf16
 // MFMA kernel of gemm.hip, so raft.hip / raft_enc.hip drive both modes with one launch sequence; every
@@ -17,17 +17,23 @@ __device__ __forceinline__ float f32_act(float v, int act) {
     return v;
 }
 
-// r5: the products run on the fp32-input matrix instruction v_mfma_f32_32x32x2_f32 -- bit for bit a k-ordered fmaf chain (one rounding per
+// r5: the products run on the fp32-input matrix instruction v_mfma_f32_32x32x2_f32 -- bit for bit k-ordered fmaf chains (one rounding per
 // product, no wider accumulation: cdna_hip_programming.md, "FP32-input MFMA"), i.e. the SAME numbers as the scalar-FMA loop of rounds 2-4, at
 // the packed-FMA rate instead of the plain-FMA rate that loop was pinned to (78 TFLOP/s: RAFT's exactness mode ran at 81).
 // Workgroup tile 128 pixels x 64 channels, 16-deep k-slabs through LDS (k-major), four waves of 64 x 32: the weight slab is the A operand
 // (rows = output channels), the activation slab the B operand, so a lane ends up with four runs of four consecutive channels of ONE pixel;
 // the next slab's global loads are in flight while the current one is multiplied.
+// Summation order: CF_CHAINS = 4 accumulator sets; the instruction for k = k0 + 2 kk + {0, 1} of a 16-deep slab adds to set kk & 3, so an output is four
+// k-ordered fmaf chains of K / 4 terms each, added as (c0 + c1) + (c2 + c3) in the epilogue -- the same for every output, whatever the tile or batch.
+// One chain over all of K (rounds 2-5) left 4.0e-7 - 6.5e-7 of sum |x| |w| on RAFT's multi-tap convolutions (K = 576 - 2304), up to 1.9 x beyond four times
+// the error of a blocked fp32 convolution on the same operands (tests/test_gpu_conv_launch.py): a chain's rounding error grows with the partial sum it
+// carries, and four chains carry a quarter each.  The eight independent accumulators per wave also keep the matrix pipe from waiting on its own result.
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+constexpr int CF_CHAINS = 4;
 constexpr int CF_BM = 128, CF_BN = 64;
 
 template <bool CONV, bool GRU>
-__global__ __launch_bounds__(256) void conv_f32_kernel(const GemmDesc p) {
+__global__ __launch_bounds__(256, 2) void conv_f32_kernel(const GemmDesc p) {
     __shared__ float As[16][CF_BM + 4];
     __shared__ float Ws[16][CF_BN + 4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -84,11 +90,13 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(const GemmDesc p) {
             }
         }
     };
-    f32x16 acc[2];
+    f32x16 acc[CF_CHAINS][2];
 #pragma unroll
-    for (int j = 0; j < 2; j++)
+    for (int q = 0; q < CF_CHAINS; q++)
 #pragma unroll
-        for (int e = 0; e < 16; e++) acc[j][e] = 0.f;
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int e = 0; e < 16; e++) acc[q][j][e] = 0.f;
     float4 av[2], wv;
     fetch(0, av, wv);
     const int l31 = lane & 31, kh = lane >> 5;
@@ -101,10 +109,11 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(const GemmDesc p) {
         __syncthreads();
         if (k0 + 16 < p.K) fetch(k0 + 16, av, wv);                // the next slab's loads fly under this slab's products
 #pragma unroll
-        for (int kk = 0; kk < 8; kk++) {                           // k = k0 + 2 kk + {0, 1}: ascending inside the instruction and across them
+        for (int kk = 0; kk < 8; kk++) {                           // k = k0 + 2 kk + {0, 1}: ascending inside the instruction and along each chain kk & 3
             const float wf = Ws[2 * kk + kh][wn * 32 + l31];
 #pragma unroll
-            for (int j = 0; j < 2; j++) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf, As[2 * kk + kh][wm * 64 + j * 32 + l31], acc[j], 0, 0, 0);
+            for (int j = 0; j < 2; j++)
+                acc[kk & (CF_CHAINS - 1)][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf, As[2 * kk + kh][wm * 64 + j * 32 + l31], acc[kk & (CF_CHAINS - 1)][j], 0, 0, 0);
         }
         __syncthreads();
     }
@@ -119,7 +128,7 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(const GemmDesc p) {
         for (int reg = 0; reg < 16; reg++) {
             const int n = n0 + wn * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kh;
             if (n >= p.N) continue;
-            float v = acc[j][reg] + (p.bias ? p.bias[n] : 0.f);
+            float v = ((acc[0][j][reg] + acc[1][j][reg]) + (acc[2][j][reg] + acc[3][j][reg])) + (p.bias ? p.bias[n] : 0.f);
             if constexpr (GRU) {
                 // h' = (1 - z) h + z tanh(acc + bias) (update.py:57-58, :64-65)
                 const float h = p.resid[map_row(p.r_map, m) * p.ldr + n];

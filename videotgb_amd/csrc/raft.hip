@@ -15,6 +15,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "conv_descs.h"
 #include "pair_h8.h"
 
 // ---------------------------------------------------------------------------------------
@@ -1012,15 +1013,7 @@ __global__ void raft_upsample_kernel(const float* __restrict__ flow, const float
 // ---------------------------------------------------------------------------------------
 // host orchestration
 // ---------------------------------------------------------------------------------------
-static GemmDesc conv_desc(int dt, int M, int N, int H, int W, int KH, int KW, int Cin, int split, const void* A, int64_t lda, const void* A2,
-                          int64_t lda2, const void* Wt, const float* bias, int epi, int act, void* out, int64_t ldo, const void* zero) {
-    GemmDesc d;
-    memset(&d, 0, sizeof(d));
-    d.dtype = dt; d.M = M; d.N = N; d.K = KH * KW * Cin; d.epi = epi; d.act = act;
-    d.A = A; d.lda = lda; d.A2 = A2; d.lda2 = lda2; d.W = Wt; d.ldw = d.K; d.bias = bias; d.out = out; d.ldo = ldo;
-    d.conv_H = H; d.conv_W = W; d.conv_KH = KH; d.conv_KW = KW; d.conv_Cin = Cin; d.conv_split = split; d.zero_page = zero;
-    return d;
-}
+// (conv_desc, the builder of this file's convolution launches: conv_descs.h)
 
 // gru_fused.hip: one launch per SepConvGRU half-step (bf16 mode with the hoisted `inp` third)
 bool gru_fused_supported(int n_img, int H, int W);

@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "conv_descs.h"
 
 // ---- stem: conv 7x7 stride 2 pad 3, 3 -> 64, on 2*(x/255)-1 (xraft.py:105-106), as an implicit GEMM.
 // Space-to-depth: the image is repacked (NHWC at half resolution) so that pixel (Y, X) carries the 4 x 2 x 2 x 3
@@ -218,21 +219,7 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const float* __restrict
     }
 }
 
-// VTGB_BF16X3: the input is a pair row [hi(Cin) | lo(Cin)] contracted as [hi | lo | hi] against weights packed [Wh | Wh | Wl] (raft_x3.hip)
-static GemmDesc enc_conv(int dt, int Mo, int N, int Ho, int Wo, int K, int Cin, int stride, int Hi, int Wi, const void* A, const void* Wt, const float* bias,
-                         float* out, int ldo, const void* zero, float* col_stats) {
-    GemmDesc d;
-    memset(&d, 0, sizeof(d));
-    const bool x3 = dt == VTGB_BF16X3;
-    const int Ce = x3 ? 3 * Cin : Cin;
-    d.dtype = x3 ? VTGB_BF16 : dt; d.M = Mo; d.N = N; d.K = K * K * Ce; d.epi = VTGB_EPI_STORE_F32;
-    d.A = A; d.lda = x3 ? 2 * Cin : Cin; d.W = Wt; d.ldw = d.K; d.bias = bias; d.out = out; d.ldo = ldo;
-    d.conv_H = Ho; d.conv_W = Wo; d.conv_KH = K; d.conv_KW = K; d.conv_Cin = Ce; d.conv_split = Ce; d.conv_wrap = x3 ? 2 * Cin : 0;
-    d.conv_stride = stride; d.conv_Hi = Hi; d.conv_Wi = Wi; d.zero_page = zero;
-    d.col_stats = col_stats; d.stats_rows = Ho * Wo;
-    if (x3) d.algo_flops = 2.0 * Mo * (double)N * (K * K * Cin);
-    return d;
-}
+// (enc_conv / enc_stem_conv, the builders of this file's convolution launches: conv_descs.h)
 int launch_x3_pair_pass(const float* x, int64_t ldx, const float* stats, int HW, const void* resid, int64_t ldr, int r_lo, void* out, int64_t ldo, int o_lo,
                         int C, int Cpad, int relu_in, int relu_out, int64_t M, hipStream_t s, int h8 = 0, int resid_h8 = 0);   // raft_x3.hip
 
@@ -333,8 +320,7 @@ static int enc_impl(const vtgb_raft_encoder_args* a, Workspace& ws, hipStream_t 
         {
             float* sf = stats_for(stats, H2 * W2, 64);
             const int cp = dt == VTGB_BF16 ? 128 : 64;            // bf16: hi | lo chunks (raft_stem_pack_kernel); bf16x3: the same image read as a pair of 64
-            GemmDesc d = enc_conv(dt, (int)M2, 64, H2, W2, 1, cp, 1, H2, W2, act1, w[0], F(w[1]), cf, 64, pad_page, sf);
-            d.conv_KH = 4; d.K = 4 * d.conv_Cin; d.ldw = d.K;
+            GemmDesc d = enc_stem_conv(dt, (int)M2, 64, H2, W2, cp, act1, w[0], F(w[1]), cf, 64, pad_page, sf);
             if (x3) d.algo_flops = 2.0 * (double)M2 * 64 * 147;
             if (!inorm && !x3) { d.epi = VTGB_EPI_STORE; d.act = 1; d.out = act0; }        // relu(bn1(conv1(x))) straight to bf16
             VTGB_TRY(conv_stats(d, stats));

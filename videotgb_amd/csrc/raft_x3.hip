@@ -13,6 +13,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "conv_descs.h"
 #include "pair_h8.h"
 
 // VTGB_F16C8 (round 6): the same orchestration with the update block's large convolutions over f16c8 pairs (pair_h8.h, gemm_h8.hip: fp16 main
@@ -288,19 +289,7 @@ __global__ __launch_bounds__(256) void x3_convf1_kernel(const float* __restrict_
     }
 }
 
-// a convolution over pair operands: C1 channels from A (row [hi(C1) | lo(C1)]), optionally C2 more from A2; K = taps * 3 (C1 + C2)
-static GemmDesc x3_conv(int M, int N, int H, int W, int KH, int KW, const void* A, int C1, const void* A2, int C2, const void* Wt, const float* bias, int epi,
-                        int act, void* out, int64_t ldo, int split_lo, const void* zero) {
-    GemmDesc d;
-    memset(&d, 0, sizeof(d));
-    const int Cin = 3 * (C1 + C2);
-    d.dtype = VTGB_BF16; d.M = M; d.N = N; d.K = KH * KW * Cin; d.epi = epi; d.act = act;
-    d.A = A; d.lda = 2 * C1; d.A2 = A2; d.lda2 = 2 * C2; d.W = Wt; d.ldw = d.K; d.bias = bias; d.out = out; d.ldo = ldo; d.split_lo = split_lo;
-    d.conv_H = H; d.conv_W = W; d.conv_KH = KH; d.conv_KW = KW; d.conv_Cin = Cin; d.conv_split = 3 * C1; d.conv_wrap = 2 * C1; d.conv_wrap2 = 2 * C2;
-    d.zero_page = zero;
-    d.algo_flops = 2.0 * M * (double)N * (KH * KW * (C1 + C2));      // the fp32 convolution this launch stands for (executed: 3 x)
-    return d;
-}
+// (x3_conv, a convolution over pair operands: conv_descs.h)
 // the same over f16c8 pairs (pair_h8.h; gemm_h8.hip): K = taps * 2 (C1 + C2) 16-bit units, C2 == 0 or C2 == C1; `scale`: device pointer to the layer's
 // E8M0 scale byte (weights[30][...])
 static GemmDesc h8_conv(int M, int N, int H, int W, int KH, int KW, const void* A, int C1, const void* A2, int C2, const void* Wt, const float* bias, int epi,
@@ -546,4 +535,80 @@ static int pair_conv_impl(const vtgb_pair_conv_args* a, const vtgb_pair_conv_ex_
         d.epi = VTGB_EPI_STORE_F32; d.out = x->out_f32; d.ldo = x->ld_f32; d.split_lo = 0;
     }
     return launch_conv_h8(d, (hipStream_t)stream);
+}
+
+// ---- unit-level entry point of the implicit-GEMM convolution launches (include/vtgb.h: vtgb_conv_launch): one launch_conv_gemm, its descriptor from the
+// builders of conv_descs.h exactly as vtgb_raft_encoder (site 0) and vtgb_raft_update (site 1) call them, then the moments finish as raft_enc.hip's conv_stats
+extern "C" int vtgb_conv_launch(const vtgb_conv_launch_args* a, vtgb_stream_t stream) {
+    VTGB_REQUIRE(a, VTGB_EINVAL, "conv_launch: NULL args");
+    const int dt = a->dtype, ok = a->out_kind;
+    VTGB_REQUIRE(dt == VTGB_F32 || dt == VTGB_BF16 || dt == VTGB_BF16X3, VTGB_EINVAL, "conv_launch: bad dtype %d (VTGB_F32, VTGB_BF16 or VTGB_BF16X3)", dt);
+    VTGB_REQUIRE(ok >= VTGB_CONV_OUT_F32 && ok <= VTGB_CONV_OUT_BF16, VTGB_EINVAL, "conv_launch: bad out_kind %d", ok);
+    VTGB_REQUIRE((a->site == 0 || a->site == 1) && a->act >= 0 && a->act <= 2 && (a->stride == 1 || a->stride == 2), VTGB_EINVAL,
+                 "conv_launch: bad site=%d act=%d stride=%d", a->site, a->act, a->stride);
+    VTGB_REQUIRE(a->n_images > 0 && a->H > 0 && a->W > 0 && a->KH > 0 && a->KW > 0 && a->N > 0 && a->Hi >= 0 && a->Wi >= 0 && a->C1 > 0 && a->C2 >= 0, VTGB_EINVAL,
+                 "conv_launch: bad dims n=%d H=%d W=%d KH=%d KW=%d N=%d Hi=%d Wi=%d C1=%d C2=%d", a->n_images, a->H, a->W, a->KH, a->KW, a->N, a->Hi, a->Wi, a->C1, a->C2);
+    VTGB_REQUIRE((a->C1 % 64) == 0 && (a->C2 % 64) == 0, VTGB_EINVAL, "conv_launch: channels per source must be multiples of 64 (C1=%d C2=%d)", a->C1, a->C2);
+    VTGB_REQUIRE(a->a && a->weights && a->out && (a->C2 == 0) == (a->a2 == nullptr), VTGB_EINVAL, "conv_launch: NULL operand (a, weights, out; a2 with C2 > 0 only)");
+    const int64_t M = (int64_t)a->n_images * a->H * a->W;
+    VTGB_REQUIRE(M < (1ll << 31) && a->ld_out >= a->N, VTGB_EINVAL, "conv_launch: n_images * H * W < 2^31 rows and ld_out >= N (ld_out=%lld)", (long long)a->ld_out);
+    const bool stem = a->KH == 4 && a->KW == 1;
+    if (a->site == 0)
+        VTGB_REQUIRE(a->C2 == 0 && (a->KH == a->KW || (stem && a->stride == 1)), VTGB_EINVAL, "conv_launch: the encoder site takes one source and K x K or the 4 x 1 stem (%d x %d)",
+                     a->KH, a->KW);
+    else
+        VTGB_REQUIRE(a->stride == 1 && (a->Hi == 0 || a->Hi == a->H) && (a->Wi == 0 || a->Wi == a->W), VTGB_EINVAL, "conv_launch: the update-block site is stride 1 on one grid");
+    const bool pair = ok == VTGB_CONV_OUT_PAIR_BF16 || ok == VTGB_CONV_OUT_PAIR_F16C8;
+    VTGB_REQUIRE(!pair || dt == VTGB_BF16X3, VTGB_EINVAL, "conv_launch: pair rows are a VTGB_BF16X3 output (dtype %d)", dt);
+    VTGB_REQUIRE(ok != VTGB_CONV_OUT_BF16 || dt == VTGB_BF16, VTGB_EINVAL, "conv_launch: bf16 rows are a VTGB_BF16 output (dtype %d)", dt);
+    VTGB_REQUIRE((!a->resid && !a->tail_w && !a->post_relu) || ok == VTGB_CONV_OUT_BF16, VTGB_EINVAL, "conv_launch: resid / post_relu / tail_w belong to VTGB_CONV_OUT_BF16");
+    VTGB_REQUIRE(!(a->resid && a->tail_w) && (!a->tail_w || a->tail_out) && (!a->resid || a->ld_resid >= a->N) && (!a->post_relu || a->resid), VTGB_EINVAL,
+                 "conv_launch: one of resid (ld_resid >= N) / tail_w (with tail_out); post_relu with resid");
+    const bool gemm1x1 = a->site == 1 && dt != VTGB_BF16X3 && a->KH == 1 && a->KW == 1 && a->C2 == 0;      // the update block's plain GEMMs
+    VTGB_REQUIRE(a->out_scale == 0.f || (gemm1x1 && !pair), VTGB_EINVAL, "conv_launch: out_scale belongs to the update block's 1 x 1 GEMMs at VTGB_BF16 / VTGB_F32");
+    if (a->moments) {
+        VTGB_REQUIRE(ok == VTGB_CONV_OUT_F32, VTGB_EINVAL, "conv_launch: moments need fp32 rows (out_kind %d)", ok);
+        VTGB_REQUIRE(a->H * a->W >= 256, VTGB_EINVAL, "conv_launch: moments need images of >= 256 rows (H * W = %d)", a->H * a->W);
+        VTGB_REQUIRE(a->site == 0 && a->N <= 128 && a->act == 0, VTGB_EINVAL, "conv_launch: moments belong to the encoder site, N <= 128, no activation");
+        VTGB_REQUIRE(a->stats_part && a->stats_part_floats >= (M / 256 + 2) * 128 * 4, VTGB_EINVAL, "conv_launch: stats_part needs (M / 256 + 2) * 128 * 4 = %lld floats",
+                     (long long)((M / 256 + 2) * 128 * 4));
+    }
+    static void* zero = nullptr;      // 256 bytes of zeros for the out-of-image taps (allocated once per process)
+    if (!zero) {
+        VTGB_HIP(hipMalloc(&zero, 256));
+        VTGB_HIP(hipMemset(zero, 0, 256));
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int Mi = (int)M, N = a->N, H = a->H, W = a->W, Hi = a->Hi ? a->Hi : H, Wi = a->Wi ? a->Wi : W, C1 = a->C1, C2 = a->C2;
+    const int ldo = (int)(pair ? 2 * a->ld_out : a->ld_out);
+    GemmDesc d;
+    if (a->site == 0) {
+        float* o32 = ok == VTGB_CONV_OUT_F32 ? (float*)a->out : nullptr;
+        d = stem ? enc_stem_conv(dt, Mi, N, H, W, C1, a->a, a->weights, a->bias, o32, ldo, zero, a->moments ? a->stats_part : nullptr)
+                 : enc_conv(dt, Mi, N, H, W, a->KH, C1, a->stride, Hi, Wi, a->a, a->weights, a->bias, o32, ldo, zero, a->moments ? a->stats_part : nullptr);
+        d.act = a->act;
+        if (pair) {      // raft_enc.hip split_conv
+            d.epi = VTGB_EPI_SPLIT; d.out = a->out; d.split_lo = (int)a->ld_out; d.split_f16c8 = ok == VTGB_CONV_OUT_PAIR_F16C8;
+        } else if (ok == VTGB_CONV_OUT_BF16) {      // raft_enc.hip conv_bn
+            d.epi = VTGB_EPI_STORE; d.out = a->out;
+            d.resid_bf16 = a->resid; d.ldrb = a->ld_resid; d.post_relu = a->post_relu;
+        }
+    } else if (dt == VTGB_BF16X3) {
+        d = x3_conv(Mi, N, H, W, a->KH, a->KW, a->a, C1, a->a2, C2, a->weights, a->bias, pair ? VTGB_EPI_SPLIT : VTGB_EPI_STORE_F32, a->act, a->out, ldo,
+                    pair ? (int)a->ld_out : 0, zero);
+        d.split_f16c8 = ok == VTGB_CONV_OUT_PAIR_F16C8;
+    } else {
+        const int epi = ok == VTGB_CONV_OUT_BF16 ? VTGB_EPI_STORE : VTGB_EPI_STORE_F32;
+        if (gemm1x1) {
+            d = conv_desc(dt, Mi, N, H, W, 0, 0, 0, 0, a->a, C1, nullptr, 0, a->weights, a->bias, epi, a->act, a->out, ldo, zero);
+            d.K = C1; d.ldw = C1; d.out_scale = a->out_scale;
+        } else {
+            d = conv_desc(dt, Mi, N, H, W, a->KH, a->KW, C1 + C2, C1, a->a, C1, a->a2, C2, a->weights, a->bias, epi, a->act, a->out, ldo, zero);
+        }
+        d.resid_bf16 = a->resid; d.ldrb = a->ld_resid; d.post_relu = a->post_relu;
+    }
+    if (a->tail_w) { d.tail_w = a->tail_w; d.tail_out = a->tail_out; d.ldtail = 32; }
+    VTGB_TRY(launch_conv_gemm(d, s));
+    if (d.col_stats) VTGB_TRY(launch_stats_finish_tiles(d.col_stats, a->moments, a->n_images, d.stats_rows, d.N, d.M, s));
+    return VTGB_OK;
 }

@@ -1027,6 +1027,64 @@ def raft_gru_half(fmt: int, h: Tensor, x: Tensor, start_zr: Optional[Tensor], st
     return z, rh, h_q
 
 
+def conv_launch(code: int, a: Tensor, w: Tensor, n_images: int, H: int, W: int, a2: Optional[Tensor] = None, bias: Optional[Tensor] = None, act: int = 0,
+                stride: int = 1, in_hw: Optional[Tuple[int, int]] = None, site: int = L.CONV_SITE_UPDATE, out_kind: int = L.CONV_OUT_F32,
+                ld_out: Optional[int] = None, out: Optional[Tensor] = None, moments: bool = False, resid: Optional[Tensor] = None, post_relu: bool = False,
+                tail_w: Optional[Tensor] = None, out_scale: float = 0.0):
+    """One implicit-GEMM convolution launch of RAFT at ``code`` = BF16X3 / BF16 / F32 alone (include/vtgb.h vtgb_conv_launch), on the H x W output grid of
+    n_images images.  a (and a2, a virtual channel concatenation): contiguous rows of the input grid ``in_hw`` (default the output grid) -- int16 pair rows
+    [M_in, 2 C] (pair_pack(., BF16X3)) at BF16X3, bf16 [M_in, C] at BF16, fp32 at F32.  w [co, kh, kw, ci] fp32, packed here the way the production tables
+    pack it (conv_k_order; split3 per source at BF16X3).  site: L.CONV_SITE_ENCODER / L.CONV_SITE_UPDATE = whose descriptor builder runs.  out_kind
+    CONV_OUT_F32 -> fp32 rows [M, ld_out]; CONV_OUT_PAIR_BF16 / CONV_OUT_PAIR_F16C8 -> int16 pair rows [M, 2 ld_out] (pair_unpack); CONV_OUT_BF16 -> bf16
+    rows.  ``out``: write into this 2-D tensor (unit column stride; its row stride is ld_out) instead of a fresh one.  moments: also returns the
+    [n_images, co, 2] per-image (sum, sum of squares).  resid (bf16 rows) / post_relu: the ResidualBlock tail; tail_w [32, 256] fp32: returns the fused
+    1x1 tail's [M, 32] fp32 instead."""
+    _need_cuda(a, a2)
+    dev = a.device
+    co, kh, kw, ci = w.shape
+    width = {BF16X3: 2, BF16: 1, F32: 1}[code]
+    adt = {BF16X3: torch.int16, BF16: torch.bfloat16, F32: torch.float32}[code]
+    C1 = a.shape[1] // width
+    C2 = 0 if a2 is None else a2.shape[1] // width
+    Hi, Wi = in_hw or (H, W)
+    M = n_images * H * W
+    for t in (a, a2):
+        assert t is None or (t.dtype == adt and t.is_contiguous() and t.shape[0] == n_images * Hi * Wi)
+    assert ci == C1 + C2
+    w = w.to(dev).float()
+    if code == BF16X3:
+        packed = _bf16_exact(conv_k_order(split3(w, [C1, C2] if a2 is not None else None)))
+    else:
+        packed = conv_k_order(w).to(act_dtype(code)).contiguous()
+    bias_t = None if bias is None else bias.to(dev).contiguous().float()
+    pair = out_kind in (L.CONV_OUT_PAIR_BF16, L.CONV_OUT_PAIR_F16C8)
+    if out is None:
+        ld = ld_out or ((co + 7) // 8 * 8)
+        odt = torch.int16 if pair else torch.bfloat16 if out_kind == L.CONV_OUT_BF16 else torch.float32
+        out = torch.zeros(M, (2 if pair else 1) * ld, dtype=odt, device=dev)
+    else:
+        assert out.dim() == 2 and out.shape[0] == M and out.stride(1) == 1 and out.shape[1] >= co and not pair
+        ld = out.stride(0)
+    mom = part = None
+    if moments:
+        mom = torch.zeros(n_images, co, 2, dtype=torch.float32, device=dev)
+        part = torch.zeros((M // 256 + 2) * 128 * 4, dtype=torch.float32, device=dev)
+    tail_p = tail_out = None
+    if tail_w is not None:
+        tail_p = tail_w.to(dev).to(torch.bfloat16).contiguous()
+        assert tuple(tail_p.shape) == (32, 256)
+        tail_out = torch.zeros(M, 32, dtype=torch.float32, device=dev)
+    if resid is not None:
+        assert resid.dtype == torch.bfloat16 and resid.dim() == 2 and resid.shape[0] == M and resid.stride(1) == 1
+    args = L.ConvLaunchArgs(code, out_kind, site, n_images, H, W, kh, kw, stride, Hi, Wi, C1, C2, co, act, 1 if post_relu else 0, out_scale, a.data_ptr(),
+                            _ptr(a2), packed.data_ptr(), _ptr(bias_t), out.data_ptr(), ld, _ptr(mom), _ptr(part), 0 if part is None else part.numel(),
+                            _ptr(resid), 0 if resid is None else resid.stride(0), _ptr(tail_p), _ptr(tail_out))
+    L.check(L.lib().vtgb_conv_launch(C.byref(args), _stream()))
+    torch.cuda.current_stream().synchronize()      # (the packed weights are temporaries of this call)
+    res = tail_out if tail_w is not None else out
+    return (res, mom) if moments else res
+
+
 class RaftWeights(_WeightTable):
     """of_extractor.update_block.* -> the packed table of vtgb_raft_update ([C_out, KH, KW, C_in] in the compute dtype)."""
 
