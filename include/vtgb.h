@@ -373,6 +373,40 @@ typedef struct {
 } vtgb_attention_tiled_args;
 int vtgb_attention_tiled(const vtgb_attention_tiled_args* a, vtgb_stream_t stream);
 
+/* Causal attention of a chunk of queries over the language model's KV cache: the chunked prefill of prompts past the one-shot prefill's
+ * bound (added at version 601 without a version bump).  q [batch, s_q, heads * head_dim] bf16 (token and batch strides below) are the
+ * prompt positions q0 .. q0 + s_q - 1; kc / vc [batch, kv_heads, tmax, head_dim] are the decoder's caches, contiguous: bf16 (ks = vs =
+ * NULL), or uint8 e4m3 codes with ks / vs [batch, kv_heads, tmax] fp32 power-of-two row scales (vtgb_llm_decode_attention_split_fp8's
+ * layout; value = code * scale, exactly a bf16 number).  Query i sees cache rows 0 .. q0 + i; nothing at or past row q0 + s_q is read.
+ * key_valid [batch, tmax] uint8 or NULL (the decode kernels' convention): a key with 0 gets weight exactly 0 and neither its K / V row nor
+ * its codes or scales are read (a pad slot may hold NaN).  A query with no visible key gets an all-zero output row.  out [batch, s_q,
+ * heads * head_dim] bf16.  Query head h reads K/V head h / (heads / kv_heads) in place.
+ * The tile partition and the per-tile arithmetic are vtgb_attention_tiled's, so the output equals vtgb_attention_tiled's with
+ * s_kv = q0 + s_q, causal, on the same K / V values laid out token-major (key_valid 0 <-> a hard key_mask), bit for bit, wherever that
+ * entry takes the call; an fp8 cache gives the bits of the bf16 cache of its dequantised values.  A row's result does not depend on
+ * batch, on tmax, on the other rows or on run order.
+ * Limits: head_dim 64 or 128, heads % kv_heads == 0, q0 >= 0, s_q > 0, q0 + s_q <= tmax <= 16384.
+ * Errors, on the host before any launch: VTGB_EINVAL for a NULL args / q / kc / vc / out, a non-positive size, a negative q0,
+ * heads % kv_heads != 0, or exactly one of ks / vs; VTGB_EUNSUPPORTED for head_dim outside {64, 128}, tmax > 16384, q0 + s_q > tmax,
+ * batch or heads > 65535, strides that break 16-byte alignment (q multiples of 8 elements, out of 4), or base pointers that do:
+ * q / kc / vc 16-byte, out 8-byte, ks / vs 4-byte aligned. */
+typedef struct {
+    int32_t batch, heads, kv_heads, head_dim, s_q;
+    int32_t q0;                            /* cache row of the chunk's first query                        */
+    int32_t tmax;                          /* slots per (batch, K/V head) of the caches                   */
+    float scale;
+    const void* q;
+    const void* kc;                        /* bf16, or e4m3 codes when ks / vs are given                  */
+    const void* vc;
+    const float* ks;                       /* [batch, kv_heads, tmax] fp32 row scales, or NULL (bf16)     */
+    const float* vs;
+    const uint8_t* key_valid;              /* [batch, tmax] or NULL                                       */
+    int64_t q_tok_stride, q_batch_stride;  /* elements                                                    */
+    void* out;                             /* [batch, s_q, heads*head_dim] bf16                           */
+    int64_t out_tok_stride, out_batch_stride;
+} vtgb_attention_cached_args;
+int vtgb_attention_cached(const vtgb_attention_cached_args* a, vtgb_stream_t stream);
+
 /* LayerNorm over the last dim of fp32 rows; writes fp32 and/or `dtype` copies. */
 typedef struct {
     int32_t dtype, M, D;

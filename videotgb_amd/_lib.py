@@ -45,7 +45,7 @@ EXPORTS = [
     "vtgb_pair_pack", "vtgb_pair_conv", "vtgb_pair_conv_ex", "vtgb_attention_tiled",
     "vtgb_llm_decode_attention_split_workspace_bytes", "vtgb_llm_decode_attention_split",
     "vtgb_llm_decode_attention_split_fp8", "vtgb_llm_rope_cache_fp8", "vtgb_llm_rope_cache_prefill_fp8",
-    "vtgb_raft_lookup_convc1", "vtgb_raft_gru_half", "vtgb_llm_lora", "vtgb_conv_launch",
+    "vtgb_raft_lookup_convc1", "vtgb_raft_gru_half", "vtgb_llm_lora", "vtgb_conv_launch", "vtgb_attention_cached",
 ]
 COMM_ID_BYTES = 128
 
@@ -229,6 +229,13 @@ class AttentionTiledArgs(C.Structure):
                 ("out_tok_stride", i64), ("out_batch_stride", i64)]
 
 
+class AttentionCachedArgs(C.Structure):
+    """vtgb_attention_cached_args: a chunk of queries at cache row q0 over the decoder's KV cache (bf16, or fp8 codes + ks / vs)."""
+    _fields_ = [("batch", i32), ("heads", i32), ("kv_heads", i32), ("head_dim", i32), ("s_q", i32), ("q0", i32), ("tmax", i32), ("scale", f32),
+                ("q", vp), ("kc", vp), ("vc", vp), ("ks", vp), ("vs", vp), ("key_valid", vp), ("q_tok_stride", i64), ("q_batch_stride", i64),
+                ("out", vp), ("out_tok_stride", i64), ("out_batch_stride", i64)]
+
+
 class LlmAttnRowsArgs(C.Structure):
     _fields_ = [("dtype", i32), ("rows", i32), ("heads", i32), ("head_dim", i32), ("rows_per_batch", i32), ("n_keys", i32), ("t_pad", i32),
                 ("scale", f32), ("q", vp), ("q_row", i64), ("k", vp), ("v", vp), ("kv_batch", i64), ("kv_head", i64), ("kv_tok", i64),
@@ -260,7 +267,8 @@ def lib() -> C.CDLL:
     for name, st in (("span_select", SpanSelectArgs), ("span_to_frames", SpanToFramesArgs),
                      ("gather_frames", GatherFramesArgs), ("vit_forward", VitArgs), ("qformer_forward", QFormerArgs),
                      ("pool_project", PoolProjectArgs), ("tgb_forward", TgbArgs), ("gemm", GemmArgs),
-                     ("attention", AttentionArgs), ("attention_tiled", AttentionTiledArgs), ("layernorm", LayerNormArgs)):
+                     ("attention", AttentionArgs), ("attention_tiled", AttentionTiledArgs), ("attention_cached", AttentionCachedArgs),
+                     ("layernorm", LayerNormArgs)):
         fn = getattr(L, "vtgb_" + name)
         fn.argtypes = [C.POINTER(st), vp]
         fn.restype = C.c_int

@@ -135,6 +135,13 @@ def _lora_servable(lm) -> bool:
     return state == "ok"
 
 
+def prefill_chunks(P: int, chunk: int):
+    """The chunked prefill's plan: [(q0, n), ...] -- consecutive row ranges [q0, q0 + n) covering 0 .. P-1, every n == chunk but the last."""
+    if P <= 0 or chunk <= 0:
+        raise ValueError(f"prefill_chunks: P={P} and chunk={chunk} must be positive")
+    return [(q0, min(chunk, P - q0)) for q0 in range(0, P, chunk)]
+
+
 def _padding(attention_mask: Optional[Tensor], B: int, P: int) -> Optional[Tensor]:
     """The decoders' view of a prompt mask: None when there is none or it is all ones (the unpadded path, unchanged), else the mask.
     Rejects what HF would not decode the same way here: a shape other than [B, P], values other than 0 / 1, a row without a token."""
@@ -445,7 +452,7 @@ class GreedyDecoder(_GraphDecoder):
     # 128, K / V heads read in place; fp32: the exactness kernel), RMSNorm(+residual), rotary + cache fill and SwiGLU through the
     # vtgb_llm_* kernels of the decode step -- no BLAS library call is left on the f2 path, in either dtype (round 4: the fp32 mode, whose
     # ids are compared token for token with HF generate, runs on libvtgb.so too; there grouped-query models repeat K / V heads).
-    # PREFILL_MAX_TOKENS = 0 forces the torch path.  (The bound is the prefill's alone: the decode step's cache is P + max_new_tokens slots
+    # Longer bf16 prompts are prefilled in chunks over the cache (_prefill_chunked below); PREFILL_MAX_TOKENS = 0 forces the torch path.  (The bound is the prefill's alone: the decode step's cache is P + max_new_tokens slots
     # rounded up to 64, and which attention kernel serves it is decided by DECODE_SPLIT_MIN_KEYS below.)  Activation memory of the bf16 path: B * P x intermediate_size bf16 (+ twice that for
     # gate | up) -- 0.72 GB (+ 1.44 GB) at B = 16, P = 2048 of Vicuna-7B.
     PREFILL_MAX_TOKENS = 2048
@@ -509,6 +516,73 @@ class GreedyDecoder(_GraphDecoder):
             L.check(lib.vtgb_llm_silu_mul(code, _ptr(gu), _ptr(act), M, self.inter, stream))
             delta = ops.gemm(act, wd)
         return x.view(B, P, H)[:, -1] + delta.view(B, P, H)[:, -1]
+
+    # Chunked prefill: a bf16 prompt past PREFILL_MAX_TOKENS goes through the layer stack in chunks of at most PREFILL_CHUNK_TOKENS rows, one
+    # after the other; every chunk appends its K / V to the cache and attends over the cache -- everything before it plus itself
+    # (ops.attention_cached: vtgb_attention_cached, caches up to 16384 slots, bf16 or the fp8 codes).  Activation memory is one chunk's
+    # (B * 2048 rows), whatever P.  Prompts up to PREFILL_MAX_TOKENS keep the one-shot sequence above and its bits.
+    PREFILL_CHUNK_TOKENS = 2048
+
+    def _use_chunked_prefill(self, st, x: Tensor, P: int) -> bool:
+        """Whether ``_prefill_chunked`` takes the prompt: the one-shot prefill refuses it for its length alone, and the state's cache is one
+        vtgb_attention_cached reads (bf16, or the fp8 code caches; up to 16384 slots).  PREFILL_MAX_TOKENS = 0 still forces the torch path."""
+        if not (self.fused and x.is_cuda and x.dtype == torch.bfloat16):
+            return False
+        if not (0 < self.PREFILL_MAX_TOKENS < P and self.PREFILL_CHUNK_TOKENS > 0):
+            return False
+        if not (self.hd in (64, 128) and self.nh % self.nkv == 0 and self.cfg.hidden_size % 64 == 0 and self.inter % 64 == 0):
+            return False
+        if st["tmax"] > ops.ATTENTION_CACHED_MAX_KEYS:
+            return False
+        return st["attn"] == "split_fp8" or (self.kv_cache == "bf16" and "kc" in st)
+
+    def _prefill_chunked(self, st, x: Tensor, P: int, pos_ids: Optional[Tensor] = None) -> Tensor:
+        """``_prefill_hip`` in chunks (``prefill_chunks(P, PREFILL_CHUNK_TOKENS)``): x [B, P, H] bf16 -> hidden state of the last position
+        [B, H]; fills rows 0..P-1 of every layer's KV cache.  Per chunk [q0, q0 + n) and layer the launches are ``_prefill_hip``'s, except
+        that rotary + append write cache rows q0 .. q0+n-1 with the rotary rows q0 + s (padded: ``pos_ids[:, q0:q0+n]``) -- the same
+        entries, which address the cache and the tables only through base pointers and (b, head, row) strides, given pointers advanced by
+        q0 rows -- and that the attention reads K / V from the cache the append just wrote (padded: the state's ``key_valid``)."""
+        lib, stream, code = L.lib(), _stream(), dtype_code(x.dtype)
+        B, _, H = x.shape
+        nh, nkv, hd, tmax = self.nh, self.nkv, self.hd, st["tmax"]
+        fp8 = st["attn"] == "split_fp8"
+        key_valid = st.get("key_valid")
+        scale = float(hd) ** -0.5
+        last = None
+        for q0, n in prefill_chunks(P, self.PREFILL_CHUNK_TOKENS):
+            M = B * n
+            xc = x[:, q0: q0 + n].reshape(M, H).clone()
+            h = torch.empty_like(xc)
+            act = torch.empty(M, self.inter, dtype=x.dtype, device=x.device)
+            pid = None if pos_ids is None else pos_ids[:, q0: q0 + n].contiguous()
+            # (the rotary row is the table's row s without pos_ids -- tables advanced by q0 rows -- and pos_ids[b, s] with them: tables as they are)
+            cos, sin = (st["cos"], st["sin"]) if pid is not None else (st["cos"][q0:], st["sin"][q0:])
+            delta = None
+            for li, (ln1, wqkv, wo, ln2, wgu, wd) in enumerate(self.layers):
+                L.check(lib.vtgb_llm_rmsnorm(code, _ptr(xc), _ptr(delta), _ptr(ln1), _ptr(h), M, H, self.eps, stream))
+                qkv = ops.gemm(h, wqkv)
+                if self.lora is not None and self.lora[li]:
+                    ops.lora_update(h, qkv, self.lora[li])
+                qkv = qkv.view(B, n, (nh + 2 * nkv) * hd)
+                if fp8:      # (the entry also writes the dequantised k / v back into qkv: unused here, K / V have one source, the cache)
+                    kc, vc, sc = st["kc8"][li], st["vc8"][li], (st["ks"][li], st["vs"][li])
+                    L.check(lib.vtgb_llm_rope_cache_prefill_fp8(code, _ptr(qkv), _ptr(kc[:, :, q0:]), _ptr(vc[:, :, q0:]), _ptr(sc[0][:, :, q0:]),
+                                                                _ptr(sc[1][:, :, q0:]), _ptr(cos), _ptr(sin), _ptr(pid), B, n, nh, nkv, hd, tmax, stream))
+                else:
+                    kc, vc, sc = st["kc"][li], st["vc"][li], None
+                    cache = (_ptr(qkv), _ptr(kc[:, :, q0:]), _ptr(vc[:, :, q0:]), _ptr(cos), _ptr(sin))
+                    if pid is None:
+                        L.check(lib.vtgb_llm_rope_cache_prefill(code, *cache, B, n, nh, nkv, hd, tmax, stream))
+                    else:
+                        L.check(lib.vtgb_llm_rope_cache_prefill_pos(code, *cache, _ptr(pid), B, n, nh, nkv, hd, tmax, stream))
+                a = ops.attention_cached(qkv[:, :, : nh * hd], kc, vc, q0, nh, scale, key_valid=key_valid, scales=sc)
+                o = ops.gemm(a.view(M, nh * hd), wo)
+                L.check(lib.vtgb_llm_rmsnorm(code, _ptr(xc), _ptr(o), _ptr(ln2), _ptr(h), M, H, self.eps, stream))
+                gu = ops.gemm(h, wgu)
+                L.check(lib.vtgb_llm_silu_mul(code, _ptr(gu), _ptr(act), M, self.inter, stream))
+                delta = ops.gemm(act, wd)
+            last = xc.view(B, n, H)[:, -1] + delta.view(B, n, H)[:, -1]
+        return last
 
     def _head(self, x):
         h = _rms(x, self.lm.model.norm.weight, self.eps)
@@ -706,8 +780,6 @@ class GreedyDecoder(_GraphDecoder):
         # ---- prefill (eager: a handful of large GEMMs)
         x = inputs_embeds
         pidx = st["ar"][:P]
-        causal = torch.where(st["ar"][None, :] <= pidx[:, None], 0.0, torch.finfo(dt).min).to(dt)[None, None]   # [1,1,P,Tmax]
-        cos, sin = st["cos"][:P], st["sin"][:P]
         pos_ids = key_mask = None
         if pmask is not None:        # (device buffers of the state, written outside any capture)
             valid = pmask.to(dev) != 0
@@ -715,20 +787,29 @@ class GreedyDecoder(_GraphDecoder):
             st["key_valid"][:, :P].copy_(valid)
             st["key_valid"][:, P:].fill_(1)                                                               # generated keys
             st["rope_off"].copy_(pos_ids[:, P - 1] - (P - 1))                                             # _update_model_kwargs_for_generation: last + 1 per step
-            cos, sin = st["cos"][pos_ids][:, None], st["sin"][pos_ids][:, None]                          # [B, 1, P, hd]
-            ok = (st["ar"][None, :] <= pidx[:, None])[None] & (st["key_valid"][:, None, :] != 0)          # [B, P, Tmax]
-            causal = torch.where(ok, 0.0, torch.finfo(dt).min).to(dt)[:, None]
             key_mask = torch.where(valid, 0.0, torch.finfo(torch.float32).min).float().contiguous()      # [B, P] additive, vtgb_attention's
+
+        def torch_operands():      # what ``_layer`` takes -- the additive mask is P x Tmax per row: built on the torch branches alone
+            if pmask is None:
+                causal = torch.where(st["ar"][None, :] <= pidx[:, None], 0.0, torch.finfo(dt).min).to(dt)[None, None]   # [1,1,P,Tmax]
+                return st["cos"][:P], st["sin"][:P], causal
+            ok = (st["ar"][None, :] <= pidx[:, None])[None] & (st["key_valid"][:, None, :] != 0)          # [B, P, Tmax]
+            return (st["cos"][pos_ids][:, None], st["sin"][pos_ids][:, None],                             # [B, 1, P, hd]
+                    torch.where(ok, 0.0, torch.finfo(dt).min).to(dt)[:, None])
         fp8_state = st["attn"] == "split_fp8"
         # (kv_cache="fp8" without the code caches -- the fallback state -- prefills on the torch path, which writes dequantised K/V)
         if self._use_hip_prefill(x, P) and (self.kv_cache == "bf16" or fp8_state):
             last = self._prefill_hip(st, x, P, pos_ids, key_mask)
+        elif self._use_chunked_prefill(st, x, P):      # past the one-shot bound: chunks over the cache
+            last = self._prefill_chunked(st, x, P, pos_ids)
         elif fp8_state:      # a prompt past the prefill kernels' bound into an fp8 state: quantised on the torch path
+            cos, sin, causal = torch_operands()
             for li, w in enumerate(self.layers):
                 x = self._layer(x, w, cos, sin, None, None, pidx, causal, codes=(st["kc8"][li], st["vc8"][li], st["ks"][li], st["vs"][li]),
                                 lora=self._lora_of(li))
             last = x[:, -1]
         else:
+            cos, sin, causal = torch_operands()
             for li, w in enumerate(self.layers):
                 x = self._layer(x, w, cos, sin, st["kc"][li], st["vc"][li], pidx, causal, lora=self._lora_of(li))
             last = x[:, -1]

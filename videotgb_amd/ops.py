@@ -350,6 +350,37 @@ def attention_tiled(q: Tensor, k: Tensor, v: Tensor, heads: int, scale: float, k
     return out
 
 
+ATTENTION_CACHED_MAX_KEYS = 16384
+
+
+def attention_cached(q: Tensor, kc: Tensor, vc: Tensor, q0: int, heads: int, scale: float, key_valid: Optional[Tensor] = None,
+                     scales: Optional[Tuple[Tensor, Tensor]] = None) -> Tensor:
+    """vtgb_attention_cached: a chunk of queries over the decoder's KV cache.  q [B, Sq, heads*hd] bf16 (unit channel stride) are the
+    positions q0 .. q0+Sq-1; kc / vc [B, kv_heads, tmax <= 16384, hd] (hd 64 or 128) contiguous, bf16 -- or, with ``scales`` = (ks, vs)
+    [B, kv_heads, tmax] fp32, uint8 / float8_e4m3fn codes (``quantize_fp8_kv``) -> [B, Sq, heads*hd] bf16.  Query i sees cache rows
+    0 .. q0+i; rows from q0+Sq on are never read.  ``key_valid`` [B, tmax] uint8: keys with 0 get weight exactly 0 and are never read.
+    The bits are ``attention_tiled``'s on the same values with Skv = q0+Sq."""
+    _need_cuda(q, kc, vc)
+    B, Sq, D = q.shape
+    assert kc.dim() == 4 and kc.shape[0] == B and vc.shape == kc.shape and kc.is_contiguous() and vc.is_contiguous()
+    nkv, tmax, hd = kc.shape[1:]
+    assert q.dtype == torch.bfloat16 and q.stride(2) == 1 and D == heads * hd, "attention_cached: q [B, Sq, heads*hd] bf16"
+    ks = vs = None
+    if scales is None:
+        assert kc.dtype == vc.dtype == torch.bfloat16, "attention_cached: bf16 caches, or codes with scales=(ks, vs)"
+    else:
+        ks, vs = scales
+        _need_cuda(ks, vs)
+        assert kc.element_size() == 1 and vc.element_size() == 1, "attention_cached: with scales the caches hold e4m3 codes"
+        assert ks.dtype == vs.dtype == torch.float32 and ks.shape == vs.shape == (B, nkv, tmax) and ks.is_contiguous() and vs.is_contiguous()
+    assert key_valid is None or (key_valid.dtype == torch.uint8 and key_valid.shape == (B, tmax) and key_valid.is_contiguous())
+    out = torch.empty(B, Sq, D, dtype=q.dtype, device=q.device)
+    a = L.AttentionCachedArgs(B, heads, nkv, hd, Sq, int(q0), tmax, float(scale), q.data_ptr(), kc.data_ptr(), vc.data_ptr(), _ptr(ks), _ptr(vs),
+                              _ptr(key_valid), q.stride(1), q.stride(0), out.data_ptr(), out.stride(1), out.stride(0))
+    L.check(L.lib().vtgb_attention_cached(C.byref(a), _stream()))
+    return out
+
+
 # ---- single-query attention of the decode step.  Two kernels: vtgb_llm_decode_attention{,_masked} (one wave per (row, head), every score in
 # LDS: caches up to 2048 slots, any head_dim <= 256) and vtgb_llm_decode_attention_split (256-key chunks over workgroups + a combine launch:
 # caches up to 16384 slots, head_dim 64 / 128, K/V read once per group of query heads).  DECODE_SPLIT_MIN_KEYS: the cache length from which
