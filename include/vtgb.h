@@ -852,6 +852,61 @@ int vtgb_llm_decode_attention_split_fp8(int dtype, const void* q, const uint8_t*
                                         const int64_t* pos, const uint8_t* key_valid /* NULL: none */, void* workspace, int32_t B, int32_t nq,
                                         int32_t nkv, int32_t hd, int32_t tmax, float scale, vtgb_stream_t stream);
 
+/* ---- Beam search on the Llama decode step (opt-in: beam_search = "graph"; attn_decode.hip, beam.hip; added at version 601 without a bump).
+ *   R = B * K beam rows; the beams of batch item b are the rows b K .. b K + K - 1.
+ * vtgb_llm_decode_attention_beam: the split-KV decode attention with two K/V sources, so that re-ordering beams copies no K/V and the prompt's
+ *   K/V exist once per batch item.  kp / vp [B, nkv, tmax_p, hd]: the prompt cache, as the prefill entries write it on B rows.  kg / vg
+ *   [R, nkv, tmax_g, hd]: what the beams generate, row r appending at slot = the step.  src_row [R, tmax_g] int32: the generated-cache row that
+ *   holds beam row r's key of slot s.  Key t of row r is kp[r / K, :, t] for t < *n_prompt, else kg[src_row[r, t - *n_prompt], :, t - *n_prompt];
+ *   it is visible while t <= *pos and (prompt keys, with key_valid [B, tmax_p] uint8) key_valid[r / K, t] != 0.  *n_prompt and *pos are device
+ *   int64 (one captured graph serves every prompt length of a bucket), clamped to [0, tmax_p] and to *n_prompt + tmax_g - 1; a table entry is
+ *   clamped into [0, R) before use: a wrong table gives wrong numbers, never a read outside the caches.
+ *   Chunks, waves, lanes and the order of every sum follow the global key index t as in vtgb_llm_decode_attention_split: the output equals, BIT
+ *   FOR BIT, that entry's on the cache [R, nkv, T, hd] this gather materialises.  Nothing past *pos, no masked slot and no prompt slot
+ *   >= *n_prompt reaches an output, NaN included.  Workspace: vtgb_llm_decode_attention_split_workspace_bytes at (R, nq, hd, tmax_p + tmax_g);
+ *   pass 2 is that entry's.  VTGB_EINVAL: NULL args / operand, a dtype other than VTGB_BF16 / VTGB_F32, a non-positive size, R % K != 0,
+ *   nq % nkv != 0; VTGB_EUNSUPPORTED: hd outside {64, 128}, tmax_p or tmax_g not a multiple of 64, tmax_p + tmax_g > 16384, a misaligned operand
+ *   (16 bytes; src_row 4) -- on the host, before any launch.
+ * vtgb_llm_beam_candidates: one step's logits [R, V] (`dtype`, as the lm_head leaves them) -> per batch item the 2 K best continuations.  Per
+ *   row, in fp32: lp = (x - m) - log(sum exp(x - m)), m = max x; for every DISTINCT id in seq[r, 0 .. *step) (int64 [R, N], *step device int64
+ *   clamped to [0, N], ids outside [0, V) ignored) lp = lp < 0 ? lp * penalty : lp / penalty (HF's RepetitionPenaltyLogitsProcessor on the
+ *   log-probabilities); lp[eos] = -inf while *step < min_new (eos < 0: none); score = lp + running[r].  Per batch item the 2 K largest of its
+ *   K * V scores in descending order: cand_score [B, 2 K] fp32, cand_idx [B, 2 K] int32 = k * V + token; equal scores in ascending index.
+ *   The order of every sum is fixed by V alone: a row's lp bits do not depend on B, K or the row's place.  Workspace: R * V * 4 +
+ *   R * 2 K * 8 bytes.  VTGB_EINVAL: NULL args / operand (seq may be NULL when N == 0), a bad dtype, non-positive R / K / V, R % K != 0,
+ *   N < 0, penalty <= 0; VTGB_EUNSUPPORTED: 2 K > V, K > 16, V > 2^20, a workspace that is too small or not 16-byte aligned. */
+typedef struct {
+    int32_t dtype;                       /* VTGB_BF16 / VTGB_F32: q, the caches, out */
+    int32_t R, K, nq, nkv, hd, tmax_p, tmax_g;
+    float scale;
+    const void* q;                       /* [R, nq * hd] */
+    const void* kp; const void* vp;      /* [R / K, nkv, tmax_p, hd] */
+    const void* kg; const void* vg;      /* [R, nkv, tmax_g, hd] */
+    const int32_t* src_row;              /* [R, tmax_g] */
+    void* out;                           /* [R, nq * hd] */
+    const int64_t* n_prompt;             /* device */
+    const int64_t* pos;                  /* device: the last visible key */
+    const uint8_t* key_valid;            /* [R / K, tmax_p] or NULL */
+    void* workspace;
+} vtgb_llm_decode_attention_beam_args;
+int vtgb_llm_decode_attention_beam(const vtgb_llm_decode_attention_beam_args* a, vtgb_stream_t stream);
+typedef struct {
+    int32_t dtype;                       /* of logits */
+    int32_t R, K, V, N;
+    int32_t eos;                         /* or -1 */
+    int32_t min_new;
+    float penalty;                       /* repetition penalty, > 0 (1: none) */
+    const void* logits;                  /* [R, V] */
+    const int64_t* seq;                  /* [R, N] generated ids */
+    const int64_t* step;                 /* device */
+    const float* running;                /* [R / K, K] */
+    float* cand_score;                   /* [R / K, 2 K] */
+    int32_t* cand_idx;                   /* [R / K, 2 K] */
+    void* workspace;
+    size_t workspace_bytes;
+} vtgb_llm_beam_candidates_args;
+int vtgb_llm_beam_candidates(const vtgb_llm_beam_candidates_args* a, vtgb_stream_t stream);
+
 /* ---- LoRA adapters on the language model's q / k / v projections (lora.hip; added at version 601 without a bump).  An in-place low-rank
  *   update of a projection's output -- videotgb_amd.train.LoraLinear.forward in eval mode (peft 0.4.0 tuners.lora.Linear, unmerged, fp32
  *   adapters), rounding for rounding:

@@ -46,6 +46,7 @@ EXPORTS = [
     "vtgb_llm_decode_attention_split_workspace_bytes", "vtgb_llm_decode_attention_split",
     "vtgb_llm_decode_attention_split_fp8", "vtgb_llm_rope_cache_fp8", "vtgb_llm_rope_cache_prefill_fp8",
     "vtgb_raft_lookup_convc1", "vtgb_raft_gru_half", "vtgb_llm_lora", "vtgb_conv_launch", "vtgb_attention_cached",
+    "vtgb_llm_decode_attention_beam", "vtgb_llm_beam_candidates",
 ]
 COMM_ID_BYTES = 128
 
@@ -210,6 +211,19 @@ class LlmRopeCacheFp8Args(C.Structure):
                 ("q_out", vp), ("kc8", vp), ("vc8", vp), ("ks", vp), ("vs", vp), ("cos_t", vp), ("sin_t", vp), ("pos", vp), ("rope_off", vp)]
 
 
+class LlmDecodeAttentionBeamArgs(C.Structure):
+    """vtgb_llm_decode_attention_beam_args: the split-KV decode attention over a prompt cache per batch item and an ancestry table per beam row."""
+    _fields_ = [("dtype", i32), ("R", i32), ("K", i32), ("nq", i32), ("nkv", i32), ("hd", i32), ("tmax_p", i32), ("tmax_g", i32), ("scale", f32),
+                ("q", vp), ("kp", vp), ("vp", vp), ("kg", vp), ("vg", vp), ("src_row", vp), ("out", vp), ("n_prompt", vp), ("pos", vp),
+                ("key_valid", vp), ("workspace", vp)]
+
+
+class LlmBeamCandidatesArgs(C.Structure):
+    """vtgb_llm_beam_candidates_args: one beam-search step's logits -> the 2 K best continuations of every batch item."""
+    _fields_ = [("dtype", i32), ("R", i32), ("K", i32), ("V", i32), ("N", i32), ("eos", i32), ("min_new", i32), ("penalty", f32), ("logits", vp),
+                ("seq", vp), ("step", vp), ("running", vp), ("cand_score", vp), ("cand_idx", vp), ("workspace", vp), ("workspace_bytes", sz)]
+
+
 class GemmArgs(C.Structure):
     _fields_ = [("dtype", i32), ("M", i32), ("N", i32), ("K", i32), ("epilogue", i32), ("A", vp), ("lda", i64),
                 ("W", vp), ("ldw", i64), ("bias", vp), ("resid", vp), ("out", vp), ("ldo", i64)]
@@ -334,6 +348,10 @@ def lib() -> C.CDLL:
     L.vtgb_llm_decode_attention_split_fp8.restype = C.c_int
     L.vtgb_llm_rope_cache_fp8.argtypes = [C.POINTER(LlmRopeCacheFp8Args), vp]
     L.vtgb_llm_rope_cache_fp8.restype = C.c_int
+    L.vtgb_llm_decode_attention_beam.argtypes = [C.POINTER(LlmDecodeAttentionBeamArgs), vp]
+    L.vtgb_llm_decode_attention_beam.restype = C.c_int
+    L.vtgb_llm_beam_candidates.argtypes = [C.POINTER(LlmBeamCandidatesArgs), vp]
+    L.vtgb_llm_beam_candidates.restype = C.c_int
     L.vtgb_llm_lora.argtypes = [C.POINTER(LlmLoraArgs), vp]
     L.vtgb_llm_lora.restype = C.c_int
     L.vtgb_llm_rope_cache_prefill_fp8.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]

@@ -16,13 +16,15 @@ from . import models, video
 
 
 def load_pretrained_model(ckpt_path, base_model_path, base_sampler_path, device, lora=False, compute_dtype="bf16", load_processors=True,
-                          decode_weights="bf16", kv_cache="bf16", **model_kwargs):
+                          decode_weights="bf16", kv_cache="bf16", beam_search="hf", **model_kwargs):
     """eval/utils/builder_utils.py:169-187.  ``compute_dtype`` / ``load_processors`` / ``decode_weights`` / ``kv_cache`` / ``model_kwargs`` are keyword extensions
     (the processors need tokenizer files next to the config; tests that only have a config.json pass ``load_processors=False``;
-    ``decode_weights="fp8"``: the opt-in fp8 weight stream of the Llama graph decoder, ``kv_cache="fp8"``: its opt-in fp8 K/V cache, models.LSTP)."""
-    from .decode import check_decode_weights, check_kv_cache
+    ``decode_weights="fp8"``: the opt-in fp8 weight stream of the Llama graph decoder, ``kv_cache="fp8"``: its opt-in fp8 K/V cache, ``beam_search="graph"``: its opt-in
+    beam search, models.LSTP)."""
+    from .decode import check_beam_search, check_decode_weights, check_kv_cache
     check_decode_weights(decode_weights)
     check_kv_cache(kv_cache)
+    check_beam_search(beam_search)
     print("start to load model...")
     processor = sampler_processor = None
     if load_processors:
@@ -30,10 +32,11 @@ def load_pretrained_model(ckpt_path, base_model_path, base_sampler_path, device,
         processor = AutoProcessor.from_pretrained(base_model_path)
         sampler_processor = AutoTokenizer.from_pretrained(base_sampler_path)
     if "instructblip" in base_model_path:
-        model = models.LSTP(base_model_path, device, lora, compute_dtype=compute_dtype, decode_weights=decode_weights, kv_cache=kv_cache, **model_kwargs)
+        model = models.LSTP(base_model_path, device, lora, compute_dtype=compute_dtype, decode_weights=decode_weights, kv_cache=kv_cache, beam_search=beam_search,
+                            **model_kwargs)
     elif "blip2" in base_model_path:
         model = models.LSTP_blip2(base_model_path, device, lora, compute_dtype=compute_dtype, decode_weights=decode_weights, kv_cache=kv_cache,
-                                  **model_kwargs)
+                                  beam_search=beam_search, **model_kwargs)
     else:   # the reference leaves `model` unbound here and dies with UnboundLocalError
         raise ValueError(f"base_model_path {base_model_path!r} names neither an instructblip nor a blip2 model")
     state_dict = torch.load(ckpt_path, map_location="cpu")

@@ -452,3 +452,202 @@ extern "C" int vtgb_llm_decode_attention_split_fp8(int dtype, const void* q, con
     return hd == 128 ? launch_split_fp8<128>(q, kc8, vc8, ks, vs, out, pos, key_valid, workspace, B, nq, nkv, tmax, scale, s)
                      : launch_split_fp8<64>(q, kc8, vc8, ks, vs, out, pos, key_valid, workspace, B, nq, nkv, tmax, scale, s);
 }
+
+// ---- beam search (opt-in: beam_search="graph").  llm_decode_attn_split_kernel with two K/V sources and no K/V copies when beams are
+// re-ordered: the R = B * K beam rows of a batch share ONE prompt cache per batch item, kp / vp [B, nkv, tmax_p, hd] (the prefill's, on B
+// rows), and append what they generate to kg / vg [R, nkv, tmax_g, hd] at slot = the step; src_row [R, tmax_g] int32 names, for beam row r,
+// the generated-cache row that holds its key of slot s (its ancestor at that step).  Global key t of row r:
+//   t <  *n_prompt:  kp[r / K, kvh, t]                                        (and key_valid[r / K, t] != 0, MASKED)
+//   t >= *n_prompt:  kg[clamp(src_row[r, t - *n_prompt], 0, R - 1), kvh, t - *n_prompt]
+// visible while t <= *pos (clamped to *n_prompt + tmax_g - 1; *n_prompt to [0, tmax_p]).  A table entry is clamped before use: a wrong
+// table gives wrong numbers, never a read outside the caches.
+// Contract: chunk = t / 256, wave = t / 64 % 4, a lane's keys and the order inside every sum follow the GLOBAL key index t exactly as in
+// llm_decode_attn_split_kernel, so the output equals, bit for bit, vtgb_llm_decode_attention_split on the cache [R, nkv, T, hd] that this
+// gather materialises.  Nothing past *pos, no masked slot and no prompt slot >= *n_prompt reaches a product (an invisible row's load goes
+// to row 0 of the item's prompt cache and is selected away).  Workspace and pass 2 are the split kernel's, with tmax = tmax_p + tmax_g.
+template <typename T, int HD, bool MASKED>
+__global__ __launch_bounds__(256) void llm_decode_attn_beam_kernel(const T* __restrict__ q, const T* __restrict__ kp, const T* __restrict__ vp,
+                                                                   const T* __restrict__ kg, const T* __restrict__ vg,
+                                                                   const int32_t* __restrict__ src_row, float* __restrict__ ws,
+                                                                   const int64_t* __restrict__ np_p, const int64_t* __restrict__ pos_p,
+                                                                   const uint8_t* __restrict__ key_valid, int R, int K, int nq, int nkv, int tmax_p,
+                                                                   int tmax_g, float scale) {
+    constexpr int EPL = 16 / (int)sizeof(T);      // elements per lane: one 16-byte piece of a row
+    constexpr int LPR = HD / EPL;                 // lanes per row
+    constexpr int RPI = 64 / LPR;                 // rows per load instruction
+    constexpr int NI = 64 / RPI;                  // load instructions per wave (== LPR)
+    typedef T TV __attribute__((ext_vector_type(EPL)));
+    __shared__ float qs[DEC_SPLIT_HEADS][HD];
+    __shared__ float sc[DEC_SPLIT_HEADS][DEC_SPLIT_CHUNK];
+    __shared__ __attribute__((aligned(16))) float red[4][DEC_SPLIT_HEADS][HD];
+
+    const int chunk = blockIdx.x, r = blockIdx.z, b = r / K;
+    const int tmax = tmax_p + tmax_g;
+    const int64_t np64 = *np_p, pos64 = *pos_p;
+    const int np = (int)(np64 < 0 ? 0 : np64 > tmax_p ? tmax_p : np64);
+    const int pos_c = (int)(pos64 < -1 ? -1 : pos64 > tmax - 1 ? tmax - 1 : pos64);      // what pass 2 walks: chunks 0 .. pos_c / 256
+    if (chunk * DEC_SPLIT_CHUNK > pos_c) return;
+    const int pos = min(pos_c, np + tmax_g - 1);                                          // the last visible key
+    const int group = nq / nkv, nhb = (group + DEC_SPLIT_HEADS - 1) / DEC_SPLIT_HEADS;
+    const int kvh = blockIdx.y / nhb, hb = blockIdx.y % nhb;
+    const int head0 = kvh * group + hb * DEC_SPLIT_HEADS, nh = min(DEC_SPLIT_HEADS, group - hb * DEC_SPLIT_HEADS);
+    const int nc = (tmax + DEC_SPLIT_CHUNK - 1) / DEC_SPLIT_CHUNK;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c = lane % LPR, rs = lane / LPR;      // this lane's 16-byte piece and row slot
+
+    for (int i = tid; i < nh * HD; i += 256) qs[i / HD][i % HD] = (float)q[((int64_t)r * nq + head0) * HD + i];
+
+    // ---- K: the wave's 64 rows -> registers (row kl0 + i * RPI of instruction i); invisible rows stay zeros
+    const int kl0 = wave * 64 + rs, key0 = chunk * DEC_SPLIT_CHUNK + kl0;
+    const int64_t pbase = ((int64_t)b * nkv + kvh) * tmax_p * HD + c * EPL;      // row 0 of the item's prompt cache (this K/V head, this piece)
+    const uint8_t* kvr = MASKED ? key_valid + (int64_t)b * tmax_p : nullptr;
+    unsigned vis = 0;
+    int64_t off[NI];      // element offset of the row: into kp / vp (key < np or invisible) or kg / vg
+#pragma unroll
+    for (int i = 0; i < NI; i++) {
+        const int key = key0 + i * RPI;
+        bool ok = key <= pos;
+        if (MASKED && ok && key < np) ok = kvr[key] != 0;
+        vis |= ok ? 1u << i : 0u;
+        int64_t o = pbase;
+        if (ok && key < np) {
+            o = pbase + (int64_t)key * HD;
+        } else if (ok) {
+            const int g = key - np;      // < tmax_g: key <= pos <= np + tmax_g - 1
+            int sr = src_row[(int64_t)r * tmax_g + g];
+            sr = sr < 0 ? 0 : sr >= R ? R - 1 : sr;
+            o = (((int64_t)sr * nkv + kvh) * tmax_g + g) * HD + c * EPL;
+        }
+        off[i] = o;
+    }
+    TV zero;
+#pragma unroll
+    for (int e = 0; e < EPL; e++) zero[e] = (T)0.f;
+    auto load_rows = [&](const T* __restrict__ srcp, const T* __restrict__ srcg, TV (&reg)[NI]) {
+#pragma unroll
+        for (int i = 0; i < NI; i++) {
+            const bool ok = vis >> i & 1;
+            const T* p = (ok && key0 + i * RPI >= np) ? srcg : srcp;
+            const TV v = *reinterpret_cast<const TV*>(p + off[i]);
+            reg[i] = ok ? v : zero;
+        }
+    };
+    TV reg[NI];
+    load_rows(kp, kg, reg);
+    __syncthreads();      // qs
+
+    // ---- scores: per head, the lane's piece of every row, then the row's LPR lanes
+    for (int h = 0; h < nh; h++) {
+        float qv[EPL];
+#pragma unroll
+        for (int e = 0; e < EPL; e++) qv[e] = qs[h][c * EPL + e];
+#pragma unroll
+        for (int i = 0; i < NI; i++) {
+            float dot = 0.f;
+#pragma unroll
+            for (int e = 0; e < EPL; e++) dot = fmaf(qv[e], (float)reg[i][e], dot);
+            dot = group_sum<LPR>(dot);
+            if (c == 0) sc[h][kl0 + i * RPI] = (vis >> i & 1) ? dot * scale : -INFINITY;
+        }
+    }
+    // ---- V replaces K in the registers (the loads fly behind the softmax)
+    load_rows(vp, vg, reg);
+    __syncthreads();      // sc
+
+    // ---- softmax statistics of the chunk: wave w takes the heads w, w + 4
+    for (int h = wave; h < nh; h += 4) {
+        float s[4], m = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            s[j] = sc[h][lane + 64 * j];
+            m = fmaxf(m, s[j]);
+        }
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            s[j] = s[j] == -INFINITY ? 0.f : expf(s[j] - m);      // (an invisible key: exactly 0, also when the chunk has no visible key)
+            sc[h][lane + 64 * j] = s[j];
+        }
+        const float l = group_sum<64>((s[0] + s[1]) + (s[2] + s[3]));
+        if (lane == 0) {
+            float* ml = ws + (int64_t)R * nq * nc * HD + (((int64_t)r * nq + head0 + h) * nc + chunk) * 2;
+            ml[0] = m;
+            ml[1] = l;
+        }
+    }
+    __syncthreads();      // sc = weights
+
+    // ---- O: per head, the lane's rows in ascending order, then the wave's row slots, then (below) the four waves
+    for (int h = 0; h < nh; h++) {
+        float acc[EPL];
+#pragma unroll
+        for (int e = 0; e < EPL; e++) acc[e] = 0.f;
+#pragma unroll
+        for (int i = 0; i < NI; i++) {
+            const float p = sc[h][kl0 + i * RPI];
+#pragma unroll
+            for (int e = 0; e < EPL; e++) acc[e] = fmaf(p, (float)reg[i][e], acc[e]);
+        }
+#pragma unroll
+        for (int e = 0; e < EPL; e++) {
+            float v = acc[e];
+            if constexpr (RPI > 1) v += __shfl_xor(v, LPR);
+            if constexpr (RPI > 2) v += __shfl_xor(v, 2 * LPR);
+            if constexpr (RPI > 4) v += __shfl_xor(v, 4 * LPR);
+            acc[e] = v;
+        }
+        if (rs == 0) {
+#pragma unroll
+            for (int e = 0; e < EPL; e += 4)
+                *reinterpret_cast<f32x4*>(&red[wave][h][c * EPL + e]) = f32x4{acc[e], acc[e + 1], acc[e + 2], acc[e + 3]};
+        }
+    }
+    __syncthreads();      // red
+    for (int i = tid; i < nh * HD; i += 256) {
+        const int h = i / HD, d = i % HD;
+        ws[(((int64_t)r * nq + head0 + h) * nc + chunk) * HD + d] = ((red[0][h][d] + red[1][h][d]) + red[2][h][d]) + red[3][h][d];
+    }
+}
+
+template <typename T, int HD>
+static int launch_beam(const vtgb_llm_decode_attention_beam_args* a, hipStream_t s) {
+    const int tmax = a->tmax_p + a->tmax_g;
+    const int group = a->nq / a->nkv, nhb = (group + DEC_SPLIT_HEADS - 1) / DEC_SPLIT_HEADS, nc = (tmax + DEC_SPLIT_CHUNK - 1) / DEC_SPLIT_CHUNK;
+    const dim3 grid(nc, a->nkv * nhb, a->R);
+    float* ws = (float*)a->workspace;
+    if (a->key_valid)
+        hipLaunchKernelGGL((llm_decode_attn_beam_kernel<T, HD, true>), grid, dim3(256), 0, s, (const T*)a->q, (const T*)a->kp, (const T*)a->vp,
+                           (const T*)a->kg, (const T*)a->vg, a->src_row, ws, a->n_prompt, a->pos, a->key_valid, a->R, a->K, a->nq, a->nkv, a->tmax_p,
+                           a->tmax_g, a->scale);
+    else
+        hipLaunchKernelGGL((llm_decode_attn_beam_kernel<T, HD, false>), grid, dim3(256), 0, s, (const T*)a->q, (const T*)a->kp, (const T*)a->vp,
+                           (const T*)a->kg, (const T*)a->vg, a->src_row, ws, a->n_prompt, a->pos, (const uint8_t*)nullptr, a->R, a->K, a->nq, a->nkv,
+                           a->tmax_p, a->tmax_g, a->scale);
+    VTGB_HIP(hipGetLastError());
+    hipLaunchKernelGGL(llm_decode_attn_combine_kernel<T>, dim3((unsigned)((int64_t)a->R * a->nq)), dim3(HD), 0, s, (const float*)ws, (T*)a->out, a->pos,
+                       (int64_t)a->R * a->nq, HD, tmax);
+    VTGB_HIP(hipGetLastError());
+    return VTGB_OK;
+}
+
+extern "C" int vtgb_llm_decode_attention_beam(const vtgb_llm_decode_attention_beam_args* a, vtgb_stream_t stream) {
+    VTGB_REQUIRE(a, VTGB_EINVAL, "llm_decode_attention_beam: NULL args");
+    VTGB_REQUIRE(a->q && a->kp && a->vp && a->kg && a->vg && a->src_row && a->out && a->n_prompt && a->pos && a->workspace, VTGB_EINVAL,
+                 "llm_decode_attention_beam: NULL operand");
+    VTGB_REQUIRE((a->dtype == VTGB_BF16 || a->dtype == VTGB_F32) && a->R > 0 && a->K > 0 && a->nq > 0 && a->nkv > 0 && a->tmax_p > 0 && a->tmax_g > 0,
+                 VTGB_EINVAL, "llm_decode_attention_beam: bad argument");
+    VTGB_REQUIRE(a->R % a->K == 0, VTGB_EINVAL, "llm_decode_attention_beam: R=%d rows are not a multiple of K=%d beams", a->R, a->K);
+    VTGB_REQUIRE(a->nq % a->nkv == 0, VTGB_EINVAL, "llm_decode_attention_beam: nq=%d is not a multiple of nkv=%d", a->nq, a->nkv);
+    VTGB_REQUIRE(a->hd == 64 || a->hd == 128, VTGB_EUNSUPPORTED, "llm_decode_attention_beam: hd=%d, built for 64 and 128", a->hd);
+    VTGB_REQUIRE(a->tmax_p % 64 == 0 && a->tmax_g % 64 == 0 && (int64_t)a->tmax_p + a->tmax_g <= DEC_SPLIT_MAX_T, VTGB_EUNSUPPORTED,
+                 "llm_decode_attention_beam: tmax_p=%d / tmax_g=%d are not multiples of 64 with a sum up to %d", a->tmax_p, a->tmax_g, DEC_SPLIT_MAX_T);
+    const int nhb = (a->nq / a->nkv + DEC_SPLIT_HEADS - 1) / DEC_SPLIT_HEADS;
+    VTGB_REQUIRE(a->R <= 65535 && (int64_t)a->nkv * nhb <= 65535, VTGB_EUNSUPPORTED, "llm_decode_attention_beam: R=%d / nq=%d exceed the grid", a->R, a->nq);
+    const auto misaligned = [](const void* p, uintptr_t al) { return (reinterpret_cast<uintptr_t>(p) & (al - 1)) != 0; };
+    VTGB_REQUIRE(!misaligned(a->q, 16) && !misaligned(a->kp, 16) && !misaligned(a->vp, 16) && !misaligned(a->kg, 16) && !misaligned(a->vg, 16) &&
+                     !misaligned(a->out, 16) && !misaligned(a->workspace, 16) && !misaligned(a->src_row, 4),
+                 VTGB_EUNSUPPORTED, "llm_decode_attention_beam: q / kp / vp / kg / vg / out / workspace need 16-byte, src_row 4-byte alignment");
+    hipStream_t s = (hipStream_t)stream;
+    if (a->dtype == VTGB_BF16) return a->hd == 128 ? launch_beam<bf16_t, 128>(a, s) : launch_beam<bf16_t, 64>(a, s);
+    return a->hd == 128 ? launch_beam<float, 128>(a, s) : launch_beam<float, 64>(a, s);
+}

@@ -20,6 +20,9 @@ the returned ids end at the step where the last row finished.  ``min_new_tokens`
 for the first steps like MinNewTokensLengthLogitsProcessor.  ``eos_token_id=None`` = fixed-length
 decode (the bench's "no EOS stopping, fixed work per clip" mode).
 Greedy ids are checked token-for-token against HF generate at fp32 (tests/test_decode.py, test_gpu_e2e.py).
+Opt-in (an owner's ``beam_search="graph"``): HF's deterministic beam search on the Llama decoder -- ``GreedyDecoder.generate(num_beams=...,
+repetition_penalty=..., length_penalty=...)``; by default such requests go to HF generate as before (tests/test_beam_decode.py,
+test_gpu_beam_decode.py).
 
 Structure: ``_GraphDecoder`` owns everything that is not the model -- the state cache (LRU, MAX_STATES), the emission state (token / position
 feedback, finished flags, lengths, sampling and stopping data), token selection, capture, the replay loop and the truncation of the returned ids;
@@ -74,6 +77,16 @@ def check_kv_cache(kv_cache) -> str:
     if kv_cache not in KV_CACHE:
         raise ValueError(f"kv_cache must be one of {KV_CACHE}, got {kv_cache!r}")
     return kv_cache
+
+
+BEAM_SEARCH = ("hf", "graph")
+
+
+def check_beam_search(beam_search) -> str:
+    """Who runs a beam-search request: "hf" (HF generate, the default) or "graph" (opt-in: the Llama graph decoder); ValueError otherwise."""
+    if beam_search not in BEAM_SEARCH:
+        raise ValueError(f"beam_search must be one of {BEAM_SEARCH}, got {beam_search!r}")
+    return beam_search
 
 
 def weights_key(lm):
@@ -262,10 +275,11 @@ class _GraphDecoder:
 
     def _capture(self, st):
         """One decode step into a graph: a warm-up step on a side stream first (handles, workspaces), the feedback buffers put back after both."""
-        keep = [st[k].clone() for k in self.FEEDBACK]
+        names = st.get("feedback", self.FEEDBACK)      # (a beam state: its bookkeeping as well)
+        keep = [st[k].clone() for k in names]
 
         def restore():
-            for k, v in zip(self.FEEDBACK, keep):
+            for k, v in zip(names, keep):
                 st[k].copy_(v)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -308,6 +322,133 @@ class _GraphDecoder:
             n = int(st["len"].max().item())
             out = out[:, : n if cut is None else min(n, cut)]
         return out
+
+    # ---- beam search: transformers 5.15.0 GenerationMixin._beam_search and its helpers (_get_top_k_continuations,
+    # _get_running_beams_for_next_iteration, _update_finished_beams, _check_early_stop_heuristic, _beam_search_has_unfinished_sequences) with
+    # fixed shapes and the step as device data, capturable like ``_emit``.  The prompt arrives as embeddings, so HF's ``input_ids`` is empty:
+    # cur_len and decoder_prompt_len start at 0, max_length is N, only generated ids feed the repetition penalty.  early_stopping is False.
+    # Per-vocabulary work is ops.beam_candidates (vtgb_llm_beam_candidates) on the fused device path and the torch statement elsewhere; the
+    # [B, 2K]-sized bookkeeping is torch ops inside the captured step.
+    BEAM_BOOK = ("run_seq", "run_scores", "run_bi", "seqs", "beam_scores", "beam_bi", "sent_fin", "unsat", "done")
+
+    def _beam_book(self, B: int, K: int, N: int, device, fill: int) -> dict:
+        """The bookkeeping of one beam search over B items, K beams, N new tokens (``_beam_search``, "3. init running tensors")."""
+        return dict(run_seq=torch.full((B, K, N), fill, dtype=torch.long, device=device), seqs=torch.full((B, K, N), fill, dtype=torch.long, device=device),
+                    run_scores=torch.zeros(B, K, device=device), beam_scores=torch.zeros(B, K, device=device),
+                    run_bi=torch.zeros(B, K, N, dtype=torch.int32, device=device), beam_bi=torch.zeros(B, K, N, dtype=torch.int32, device=device),
+                    sent_fin=torch.zeros(B, K, dtype=torch.bool, device=device), unsat=torch.ones(B, 1, dtype=torch.bool, device=device),
+                    done=torch.zeros(1, dtype=torch.bool, device=device),
+                    top_mask=torch.cat((torch.ones(K, dtype=torch.bool), torch.zeros(K, dtype=torch.bool))).to(device),
+                    item_off=(torch.arange(B, device=device) * K)[:, None], cand_score=torch.zeros(B, 2 * K, device=device),
+                    cand_idx=torch.zeros(B, 2 * K, dtype=torch.int32, device=device))
+
+    def _beam_reset(self, st):
+        fill = st["beam"]["fill"]
+        st["run_seq"].fill_(fill)
+        st["seqs"].fill_(fill)
+        st["run_scores"].fill_(-1e9)
+        st["run_scores"][:, 0] = 0.0      # only the first beam's tokens count at the first step: the K rows are identical
+        st["beam_scores"].fill_(-1e9)
+        st["run_bi"].fill_(-1)
+        st["beam_bi"].fill_(-1)
+        st["sent_fin"].zero_()
+        st["unsat"].fill_(True)
+        st["done"].zero_()
+
+    def _beam_candidates(self, st, logits: Tensor):
+        """(score [B, 2K] fp32, flat index [B, 2K] int64 = k * V + token): log_softmax, the repetition penalty over the ids generated so far,
+        the eos block of min_new_tokens, + the running scores, the 2K best per item."""
+        bm, step = st["beam"], st["step"]
+        B, K, N = st["run_seq"].shape
+        V = logits.shape[-1]
+        if bm["kernel"]:
+            sc, ix = ops.beam_candidates(logits, st["run_seq"].view(B * K, N), step, st["run_scores"], bm["repetition_penalty"], st["eos"],
+                                         st["min_new"], out=(st["cand_score"], st["cand_idx"]), workspace=st["cand_ws"])
+            return sc, ix.long()
+        lp = F.log_softmax(logits.float(), dim=-1)
+        if bm["repetition_penalty"] != 1.0:      # RepetitionPenaltyLogitsProcessor on the log-probabilities; ids behind the step go to a spare column
+            ids = torch.where(st["ar"][None, :N] < step, st["run_seq"].view(B * K, N), torch.full_like(st["run_seq"].view(B * K, N), V))
+            lp = torch.cat((lp, torch.zeros_like(lp[:, :1])), dim=-1)
+            g = lp.gather(1, ids)
+            lp = lp.scatter(1, ids, torch.where(g < 0, g * bm["repetition_penalty"], g / bm["repetition_penalty"]))[:, :V]
+        if st["eos"] is not None and st["min_new"] > 0:
+            lp = lp.clone()
+            lp[:, st["eos"]] = torch.where(step < st["min_new"], torch.full_like(lp[:, st["eos"]], float("-inf")), lp[:, st["eos"]])
+        acc = (lp.view(B, K, V) + st["run_scores"][:, :, None]).reshape(B, K * V)
+        return torch.topk(acc, k=2 * K)
+
+    def _beam_select(self, st, logits: Tensor) -> Tensor:
+        """One ``_beam_search`` iteration behind the logits [B*K, V] at cur_len = *step: the bookkeeping is advanced (frozen once ``done``) and
+        the next tokens go to ``tok``; returns the rows [B*K] the next beams continue (their parents)."""
+        bm, step = st["beam"], st["step"]
+        B, K, N = st["run_seq"].shape
+        V = logits.shape[-1]
+        lpen = bm["length_penalty"]
+
+        def take(t, idx):      # _gather_beams
+            while idx.dim() < t.dim():
+                idx = idx.unsqueeze(-1)
+            return torch.take_along_dim(t, idx, dim=1)
+
+        def over(t, d):        # t / d for a length-penalty denominator: HF divides by a Python scalar (on the device: times its fp32 reciprocal)
+            return t * (1.0 / d) if t.is_cuda else t / d
+        # c. _get_top_k_continuations
+        score, flat = self._beam_candidates(st, logits)
+        beam, token = flat // V, flat % V
+        at = step.view(1, 1, 1).expand(B, 2 * K, 1)
+        top_seq = take(st["run_seq"], beam).scatter(2, at, token[:, :, None])
+        top_bi = take(st["run_bi"], beam).scatter(2, at, (beam + st["item_off"]).to(torch.int32)[:, :, None])
+        # d. stopping criteria: EosTokenCriteria | MaxLengthCriteria
+        hits = (step + 1 >= N).expand(B, 2 * K)
+        if st["eos"] is not None:
+            hits = hits | (token == st["eos"])
+        # e. _get_running_beams_for_next_iteration
+        run_lp = score + hits.to(torch.float32) * -1.0e9
+        nxt = torch.topk(run_lp, k=K)[1]
+        run_seq, run_scores, run_bi = take(top_seq, nxt), take(run_lp, nxt), take(top_bi, nxt)
+        # f. _update_finished_beams (early_stopping False)
+        did = hits & st["top_mask"][None, :]
+        fin_lp = over(score, torch.pow((step + 1).double(), lpen).float())
+        fin_lp = fin_lp + (~st["unsat"]).to(torch.float32) * -1.0e9
+        fin_lp = fin_lp + (~did) * -1.0e9
+        m_scores = torch.cat((st["beam_scores"], fin_lp), dim=1)
+        keep = torch.topk(m_scores, k=K)[1]
+        seqs, beam_scores = take(torch.cat((st["seqs"], top_seq), dim=1), keep), take(m_scores, keep)
+        beam_bi, sent_fin = take(torch.cat((st["beam_bi"], top_bi), dim=1), keep), take(torch.cat((st["sent_fin"], did), dim=1), keep)
+        # g. _check_early_stop_heuristic at cur_len + 1, _beam_search_has_unfinished_sequences
+        best = over(run_scores[:, :1], torch.pow((step + 1).double(), lpen).float())
+        worst = torch.where(sent_fin, torch.min(beam_scores, dim=1, keepdim=True)[0], torch.full_like(beam_scores, -1.0e9))
+        unsat = st["unsat"] & torch.any(best > worst, dim=-1, keepdim=True)
+        more = torch.any(unsat) & ~torch.all(hits)
+        # HF leaves its loop on the step that finishes: from then on nothing changes
+        done = st["done"]
+        for name, new in (("run_seq", run_seq), ("run_scores", run_scores), ("run_bi", run_bi), ("seqs", seqs), ("beam_scores", beam_scores),
+                          ("beam_bi", beam_bi), ("sent_fin", sent_fin), ("unsat", unsat)):
+            st[name].copy_(torch.where(done, st[name], new))
+        done.logical_or_(~more)
+        st["tok"].copy_(take(token, nxt).reshape(B * K))
+        return (take(beam, nxt) + st["item_off"]).reshape(B * K)
+
+    def _beam_result(self, st) -> Tensor:
+        """Per batch item the best finished beam, cropped to the longest generated length (counted from ``beam_indices``, as HF does)."""
+        n = int(((st["beam_bi"][:, 0] + 1).bool()).sum(dim=1).max().item())
+        return st["seqs"][:, 0, :n].clone()
+
+    def _replay_beams(self, st, use_graph: bool) -> Tensor:
+        """Steps 1 .. N-1 (the first selection came from the prefill), one graph replay each; ``done`` is read once per 16 steps."""
+        N = st["run_seq"].shape[2]
+        use_graph = use_graph and st["tok"].is_cuda and st["attn"] == "beam"
+        if N > 1:
+            if use_graph and st["graph"] is None:
+                self._capture(st)
+            for i in range(N - 1):
+                if i % 16 == 0 and i > 0 and bool(st["done"].item()):
+                    break
+                if use_graph:
+                    st["graph"].replay()
+                else:
+                    self._decode_step(st)
+        return self._beam_result(st)
 
     @staticmethod
     def _text_scan(st, text_stop, checked: int, upto: int):
@@ -659,6 +800,11 @@ class GreedyDecoder(_GraphDecoder):
         code = dtype_code(x.dtype)
         nq, nkv, hd, tmax = self.nh, self.nkv, self.hd, st["tmax"]
         padded, skinny = "key_valid" in st, "sk_ws" in st
+        # a beam state (st["attn"] == "beam"): the rows are the B * K beams; a row appends its K/V at slot = the step of the generated caches
+        # kg / vg (rotary row = slot + rope_off[r] of the state's tables) and attends through the ancestry table over the prompt cache of its
+        # batch item (B rows: the key mask is the batch item's) and the generated caches (vtgb_llm_decode_attention_beam)
+        beam = st["attn"] == "beam"
+        row_off = padded or beam
         h, q, a, act = st["h"], st["q"], st["a"], st["act"]
         if skinny:
             sw, ws = self._skinny_weights(), st["sk_ws"]
@@ -689,7 +835,7 @@ class GreedyDecoder(_GraphDecoder):
         # rotary + cache append: vtgb_llm_rope_cache{,_parts}{,_pos} (_parts: q|k|v arrive as split-K fragments; _pos: a padded batch's per-row
         # rotary offsets) take the same pointer lists apart from those extras.  Attention: ops.decode_attention, the kernel fixed by the state
         # (its workspace exists exactly where the split kernel serves it)
-        rope = (_ptr(st["cos"]), _ptr(st["sin"]), _ptr(st["pos"])) + ((_ptr(st["rope_off"]),) if padded else ())
+        rope = (_ptr(st["cos"]), _ptr(st["sin"]), _ptr(st["slot"] if beam else st["pos"])) + ((_ptr(st["rope_off"]),) if row_off else ())
         attn_ws, key_valid = st.get("attn_ws"), st.get("key_valid")
         fp8_kv = st["attn"] == "split_fp8"      # kv_cache="fp8": the append quantises the K / V rows, the attention reads codes and scales
         delta, dS = None, 1
@@ -706,23 +852,29 @@ class GreedyDecoder(_GraphDecoder):
                 L.check(lib.vtgb_llm_rope_cache_fp8(ctypes.byref(ra), stream))
                 ops.decode_attention_fp8(q, *kv8, st["pos"], float(hd) ** -0.5, key_valid=key_valid, out=a, workspace=attn_ws)
             else:
-                kv = (_ptr(st["kc"][li]), _ptr(st["vc"][li]))
-                rope_cache = getattr(lib, "vtgb_llm_rope_cache" + ("_parts" if qS > 1 else "") + ("_pos" if padded else ""))
-                L.check(rope_cache(code, *((_ptr(ws), qS) if qS > 1 else (_ptr(qkv),)), _ptr(q), *kv, *rope, B, nq, nkv, hd, tmax, stream))
-                ops.decode_attention(q, st["kc"][li], st["vc"][li], st["pos"], float(hd) ** -0.5, key_valid=key_valid, out=a, workspace=attn_ws,
-                                     split=st["attn"] == "split")
+                kc, vc = (st["kg"][li], st["vg"][li]) if beam else (st["kc"][li], st["vc"][li])
+                rope_cache = getattr(lib, "vtgb_llm_rope_cache" + ("_parts" if qS > 1 else "") + ("_pos" if row_off else ""))
+                L.check(rope_cache(code, *((_ptr(ws), qS) if qS > 1 else (_ptr(qkv),)), _ptr(q), _ptr(kc), _ptr(vc), *rope, B, nq, nkv, hd,
+                                   st["tmax_g"] if beam else tmax, stream))
+                if beam:
+                    ops.decode_attention_beam(q, st["prompt"]["kc"][li], st["prompt"]["vc"][li], kc, vc, st["src_row"], st["nprompt"], st["pos"],
+                                              float(hd) ** -0.5, key_valid=key_valid, out=a, workspace=attn_ws)
+                else:
+                    ops.decode_attention(q, kc, vc, st["pos"], float(hd) ** -0.5, key_valid=key_valid, out=a, workspace=attn_ws,
+                                         split=st["attn"] == "split")
             o, oS = lin_d(a, li, 1, "sk_o")
             norm(o, oS, ln2)
             gu = lin(h, li, 2, "sk_gu")
             L.check(lib.vtgb_llm_silu_mul(code, _ptr(gu), _ptr(act), B, self.inter, stream))
             delta, dS = lin_d(act, li, 3, "sk_d")
         norm(delta, dS, self.lm.model.norm.weight)
+        emit = self._beam_emit if beam else self._emit
         if skinny:
-            self._emit(st, ops.gemm_skinny(h, sw[-1], out=st["sk_logits"], workspace=ws))
+            emit(st, ops.gemm_skinny(h, sw[-1], out=st["sk_logits"], workspace=ws))
         elif self._gemm_ok(x.dtype):
-            self._emit(st, ops.gemm(h, self.head_w))
+            emit(st, ops.gemm(h, self.head_w))
         else:
-            self._emit(st, F.linear(h, self.head_w))
+            emit(st, F.linear(h, self.head_w))
 
     def _decode_step(self, st):
         """One token for every sequence, entirely on the device (captured)."""
@@ -742,42 +894,123 @@ class GreedyDecoder(_GraphDecoder):
             mask = torch.where(st["ar"][None, None, None, :] <= pos, 0.0, neg).to(x.dtype)
         for li, w in enumerate(self.layers):
             x = self._layer(x, w, cos, sin, st["kc"][li], st["vc"][li], pos, mask, lora=self._lora_of(li))
-        self._emit(st, self._head(x[:, -1]))
+        (self._beam_emit if "beam" in st else self._emit)(st, self._head(x[:, -1]))
 
-    @torch.no_grad()
-    def generate(self, inputs_embeds: Tensor, max_new_tokens: int, use_graph: bool = True, eos_token_id=None, pad_token_id: int = 0,
-                 min_new_tokens: int = 0, do_sample: bool = False, temperature: float = 1.0, top_k: Optional[int] = 50, top_p: Optional[float] = 1.0,
-                 sample_noise: Optional[Tensor] = None, generator: Optional[torch.Generator] = None, stop_ids=None, text_stop=None,
-                 attention_mask: Optional[Tensor] = None) -> Tensor:
-        """inputs_embeds [B, P, H] -> ids [B, n <= max_new_tokens] (n < max_new_tokens only when every row has finished --
-        emitted ``eos_token_id`` or met a stopping keyword -- as HF generate returns them; finished rows are padded).
-        ``do_sample``: sample from HF's warped distribution (temperature, top_k [HF's default 50], top_p) with ``sample_noise`` [max_new_tokens, B]
-        uniform numbers in [0, 1) (drawn from ``generator`` / the device's default generator when None).  ``stop_ids``: token-id tails that end a
-        row when its last ids equal one of them (KeywordsStoppingCriteria's token test, on the device); ``text_stop(ids [1, n]) -> bool``: its
-        text test, evaluated on the host for every new length once per 16 tokens (batch 1).  ``attention_mask`` [B, P] of 0 / 1 (None: all ones):
-        pads anywhere in the prompt, with HF generate's semantics -- prefill rotary positions ``cumsum(mask) - 1`` (pads at 0), decode step s
-        at position ``position_ids[b, P-1] + s`` in cache slot P-1+s, pad keys masked for the whole decode."""
+    # ---- beam search (opt-in at the interfaces: beam_search="graph").  R = B * K rows run the decode step.  On the device (fused) the state keeps
+    # the prompt's K/V once per batch item (``st["prompt"]``: a B-row state the prefill entries fill, unchanged) and what the beams generate in
+    # kg / vg [R, nkv, tmax_g, hd], one slot per step; re-ordering beams re-orders an int32 ancestry table (``src_row``), never K/V, and the
+    # attention reads through it (vtgb_llm_decode_attention_beam, whatever the cache length).  The append is the existing
+    # vtgb_llm_rope_cache{,_parts}_pos entry on the generated caches: cache row = slot, rotary row = slot + rope_off[r] of tables that are
+    # written before every call to start at the batch's first generated position (cos / sin [tmax_g, hd]; tmax_g covers N plus the spread of
+    # the rows' first positions in a ragged batch).  Elsewhere (CPU, fused=False) the rows keep whole caches, re-ordered by index_select as
+    # HF re-orders its cache: the torch statement of the same search.
+    def _beam_state(self, B: int, K: int, P: int, N: int, device, dtype, eos, fill: int, min_new: int, rep_pen: float, len_pen: float, padded: bool,
+                    spread: int):
+        R = B * K
+        kernel = device.type == "cuda" and self.fused
+        H, HD, inter, nkv, hd = self.cfg.hidden_size, self.nh * self.hd, self.inter, self.nkv, self.hd
+        tmax_p, tmax_g = -(-P // 64) * 64, -(-(N + spread) // 64) * 64
+        if not kernel:
+            tmax_p, tmax_g = -(-(P + N) // 64) * 64, 0      # (one cache per row, as the plain decoder's)
+        elif not (ops.decode_attention_beam_ok(tmax_p, tmax_g, hd) and self.nh % nkv == 0):
+            raise NotImplementedError(f"num_beams > 1 on the device needs head_dim 64 or 128 and a cache up to {ops.DECODE_SPLIT_MAX_KEYS} slots "
+                                      f"(head_dim {hd}, {tmax_p} + {tmax_g} slots)")
+        elif K > ops.BEAM_MAX_BEAMS or 2 * K > self.head_w.shape[0]:
+            raise NotImplementedError(f"num_beams={K}: up to {ops.BEAM_MAX_BEAMS} beams, 2 x num_beams <= vocab_size")
+        tmax = tmax_p + tmax_g
+
+        def z(*shape, dtype=dtype):
+            return torch.zeros(*shape, device=device, dtype=dtype)
+
+        def buffers():
+            cos, sin = self._rope(tmax, device, dtype)
+            pst = dict(ar=torch.arange(tmax_p, device=device), cos=cos[:tmax_p], sin=sin[:tmax_p], tmax=tmax_p, attn="split" if kernel else None,
+                       kc=[z(B, nkv, tmax_p, hd) for _ in self.layers], vc=[z(B, nkv, tmax_p, hd) for _ in self.layers])
+            if padded:
+                pst.update(key_valid=torch.ones(B, tmax_p, dtype=torch.uint8, device=device), rope_off=z(B, dtype=torch.long))
+            st = dict(tmax=tmax, tmax_g=tmax_g, prompt=pst, attn="beam" if kernel else None,
+                      beam=dict(K=K, fill=fill, repetition_penalty=rep_pen, length_penalty=len_pen, kernel=kernel))
+            st.update(self._beam_book(B, K, N, device, fill))
+            if kernel:
+                V = self.head_w.shape[0]
+                st.update(cos_full=cos, sin_full=sin, cos=z(tmax_g, hd), sin=z(tmax_g, hd), x=z(R, H), h=z(R, H), q=z(R, HD), a=z(R, HD), act=z(R, inter),
+                          kg=[z(R, nkv, tmax_g, hd) for _ in self.layers], vg=[z(R, nkv, tmax_g, hd) for _ in self.layers],
+                          src_row=z(R, tmax_g, dtype=torch.int32), row_id=torch.arange(R, dtype=torch.int32, device=device)[:, None],
+                          slot=z(1, dtype=torch.long), nprompt=z(1, dtype=torch.long), rope_off=z(R, dtype=torch.long),
+                          attn_ws=z(ops.decode_attention_workspace_bytes(R, self.nh, hd, tmax), dtype=torch.uint8),
+                          cand_ws=z(ops.beam_candidates_workspace_bytes(R, K, V), dtype=torch.uint8),
+                          feedback=("tok", "pos", "step", "slot", "src_row") + self.BEAM_BOOK)
+                if padded:
+                    st["key_valid"] = pst["key_valid"]      # [B, tmax_p]: the batch item's prompt mask
+                if self._use_skinny(R, dtype):
+                    Hq = (self.nh + 2 * nkv) * hd
+                    shapes = ((Hq, H), (H, HD), (2 * inter, H), (H, inter), (V, H))
+                    st.update(sk_qkv=z(R, Hq), sk_o=z(R, H), sk_gu=z(R, 2 * inter), sk_d=z(R, H), sk_logits=z(R, V),
+                              sk_ws=z(max(ops.gemm_skinny_workspace_bytes(R, n, k) for n, k in shapes), dtype=torch.uint8))
+                    self._skinny_weights()
+            else:
+                st.update(cos=cos, sin=sin, kc=[z(R, nkv, tmax, hd) for _ in self.layers], vc=[z(R, nkv, tmax, hd) for _ in self.layers])
+                if padded:
+                    st.update(key_valid=torch.ones(R, tmax, dtype=torch.uint8, device=device), rope_off=z(R, dtype=torch.long))
+            return st
+        key = ("beams", B, K, tmax_p, tmax_g, N, eos, fill, min_new, rep_pen, len_pen, padded)
+        return self._cached_state(key, R, N, tmax, device, eos, fill, min_new, None, None, buffers)
+
+    def _beam_emit(self, st, logits: Tensor):
+        """``_emit`` of a beam state: the selection, then the beams' K/V follow their parents -- the ancestry table on the device
+        (src_row' = src_row[parent], and the slot the new tokens will be appended at is the row's own), whole caches elsewhere."""
+        rows = self._beam_select(st, logits)
+        if st["attn"] == "beam":
+            st["src_row"].copy_(st["src_row"].index_select(0, rows))
+            st["src_row"].index_copy_(1, st["step"], st["row_id"])
+            st["slot"].add_(1)
+        else:
+            for c in st["kc"] + st["vc"]:
+                c.copy_(c.index_select(0, rows))
+        st["pos"].add_(1)
+        st["step"].add_(1)
+
+    def _generate_beams(self, inputs_embeds: Tensor, N: int, use_graph: bool, eos_token_id, pad_token_id, min_new_tokens, attention_mask, K: int,
+                        length_penalty: float, repetition_penalty: float) -> Tensor:
         B, P, _ = inputs_embeds.shape
         pmask = _padding(attention_mask, B, P)
-        N = max_new_tokens
         dev, dt = inputs_embeds.device, inputs_embeds.dtype
-        eos_token_id, pad_token_id, min_new_tokens = self._special(eos_token_id, pad_token_id, min_new_tokens)
-        sample = None
-        if do_sample:
-            if temperature is None or not float(temperature) > 0.0:
-                raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")      # (HF's TemperatureLogitsWarper)
-            sample = (float(temperature), int(top_k) if top_k else 0, float(top_p) if top_p is not None else 1.0)
-        stop = tuple(tuple(int(v) for v in t) for t in stop_ids if len(t)) if stop_ids else None
-        if text_stop is not None and B != 1:
-            raise AssertionError("Only support batch size 1 (yet)")                                          # (the reference's criteria: builder_utils.py:334)
-        st = self._state(B, P, N, dev, dt, eos_token_id, pad_token_id, min_new_tokens, sample, stop or None, pmask is not None)
-        if sample is not None:
-            if sample_noise is not None:
-                st["u"].copy_(sample_noise.to(dev).reshape(N, B))
-            else:
-                st["u"].copy_(torch.rand(N, B, device=dev, generator=generator))
-        ending = eos_token_id is not None or stop is not None or text_stop is not None
-        # ---- prefill (eager: a handful of large GEMMs)
+        eos, _, min_new = self._special(eos_token_id, pad_token_id, min_new_tokens)
+        fill = -1 if eos is None else int(pad_token_id if pad_token_id else eos)      # HF: ``pad_token_id or eos_token_id`` -- pad 0 fills with eos
+        # the rotary row of every item's first generated token (HF: position_ids[b, P-1] + 1), from the host copy of the mask
+        if pmask is None:
+            first = torch.full((B,), P, dtype=torch.long)
+        else:
+            first = torch.where(pmask[:, -1] != 0, (pmask != 0).sum(-1), torch.ones(B, dtype=torch.long)).long()
+        lo = int(first.min())
+        st = self._beam_state(B, K, P, N, dev, dt, eos, fill, min_new, float(repetition_penalty), float(length_penalty), pmask is not None,
+                              int(first.max()) - lo)
+        pst = st["prompt"]
+        logits = self._head(self._prefill(pst, inputs_embeds, pmask))      # [B, V]: the prompt runs once per batch item
+        if st["attn"] == "beam":
+            st["cos"].copy_(st["cos_full"][lo: lo + st["tmax_g"]])
+            st["sin"].copy_(st["sin_full"][lo: lo + st["tmax_g"]])
+            st["rope_off"].copy_((first - lo).repeat_interleave(K).to(dev))
+            st["nprompt"].fill_(P)
+            st["slot"].fill_(-1)
+            st["src_row"].zero_()
+        else:
+            for src, dst in zip(pst["kc"] + pst["vc"], st["kc"] + st["vc"]):
+                dst.copy_(src.repeat_interleave(K, 0))
+            if pmask is not None:
+                st["key_valid"].copy_(pst["key_valid"].repeat_interleave(K, 0))
+                st["rope_off"].copy_(pst["rope_off"].repeat_interleave(K))
+        self._beam_reset(st)
+        st["step"].zero_()
+        st["pos"].fill_(P - 1)
+        self._beam_emit(st, logits.repeat_interleave(K, 0).contiguous())      # the first step: K identical rows, running scores [0, -1e9, ...]
+        return self._replay_beams(st, use_graph)
+
+    def _prefill(self, st, inputs_embeds: Tensor, pmask: Optional[Tensor]) -> Tensor:
+        """The prompt through the layer stack into the state's K/V cache rows 0 .. P-1 (eager: a handful of large GEMMs); a padded batch's key mask
+        and rotary offsets into the state's device buffers.  Returns the hidden state of the last position [B, H]."""
+        B, P, _ = inputs_embeds.shape
+        dev, dt = inputs_embeds.device, inputs_embeds.dtype
         x = inputs_embeds
         pidx = st["ar"][:P]
         pos_ids = key_mask = None
@@ -813,6 +1046,57 @@ class GreedyDecoder(_GraphDecoder):
             for li, w in enumerate(self.layers):
                 x = self._layer(x, w, cos, sin, st["kc"][li], st["vc"][li], pidx, causal, lora=self._lora_of(li))
             last = x[:, -1]
+        return last
+
+    @torch.no_grad()
+    def generate(self, inputs_embeds: Tensor, max_new_tokens: int, use_graph: bool = True, eos_token_id=None, pad_token_id: int = 0,
+                 min_new_tokens: int = 0, do_sample: bool = False, temperature: float = 1.0, top_k: Optional[int] = 50, top_p: Optional[float] = 1.0,
+                 sample_noise: Optional[Tensor] = None, generator: Optional[torch.Generator] = None, stop_ids=None, text_stop=None,
+                 attention_mask: Optional[Tensor] = None, num_beams: int = 1, length_penalty: float = 1.0, repetition_penalty: float = 1.0) -> Tensor:
+        """inputs_embeds [B, P, H] -> ids [B, n <= max_new_tokens] (n < max_new_tokens only when every row has finished --
+        emitted ``eos_token_id`` or met a stopping keyword -- as HF generate returns them; finished rows are padded).
+        ``do_sample``: sample from HF's warped distribution (temperature, top_k [HF's default 50], top_p) with ``sample_noise`` [max_new_tokens, B]
+        uniform numbers in [0, 1) (drawn from ``generator`` / the device's default generator when None).  ``stop_ids``: token-id tails that end a
+        row when its last ids equal one of them (KeywordsStoppingCriteria's token test, on the device); ``text_stop(ids [1, n]) -> bool``: its
+        text test, evaluated on the host for every new length once per 16 tokens (batch 1).  ``attention_mask`` [B, P] of 0 / 1 (None: all ones):
+        pads anywhere in the prompt, with HF generate's semantics -- prefill rotary positions ``cumsum(mask) - 1`` (pads at 0), decode step s
+        at position ``position_ids[b, P-1] + s`` in cache slot P-1+s, pad keys masked for the whole decode.
+        ``num_beams`` > 1: HF's deterministic beam search (``_beam_search``, early_stopping False) with ``length_penalty`` and
+        ``repetition_penalty`` -- per batch item the best finished beam, cropped to the longest, finished rows filled with ``pad_token_id or
+        eos_token_id``; greedy only, no stopping criteria, the bf16 K/V cache (NotImplementedError otherwise)."""
+        num_beams = int(num_beams)
+        if num_beams < 1 or not float(repetition_penalty) > 0.0:
+            raise ValueError(f"num_beams={num_beams} / repetition_penalty={repetition_penalty}: at least one beam, a positive penalty")
+        if num_beams > 1:
+            if do_sample or stop_ids or text_stop is not None:
+                raise NotImplementedError("num_beams > 1 with sampling or stopping criteria: use HF generate")
+            if self.kv_cache != "bf16":
+                raise NotImplementedError("num_beams > 1 with kv_cache='fp8': use HF generate")
+            return self._generate_beams(inputs_embeds, max_new_tokens, use_graph, eos_token_id, pad_token_id, min_new_tokens, attention_mask, num_beams,
+                                        1.0 if length_penalty is None else float(length_penalty), float(repetition_penalty))
+        if float(repetition_penalty) != 1.0:
+            raise NotImplementedError("repetition_penalty with one beam: use HF generate")
+        B, P, _ = inputs_embeds.shape
+        pmask = _padding(attention_mask, B, P)
+        N = max_new_tokens
+        dev, dt = inputs_embeds.device, inputs_embeds.dtype
+        eos_token_id, pad_token_id, min_new_tokens = self._special(eos_token_id, pad_token_id, min_new_tokens)
+        sample = None
+        if do_sample:
+            if temperature is None or not float(temperature) > 0.0:
+                raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")      # (HF's TemperatureLogitsWarper)
+            sample = (float(temperature), int(top_k) if top_k else 0, float(top_p) if top_p is not None else 1.0)
+        stop = tuple(tuple(int(v) for v in t) for t in stop_ids if len(t)) if stop_ids else None
+        if text_stop is not None and B != 1:
+            raise AssertionError("Only support batch size 1 (yet)")                                          # (the reference's criteria: builder_utils.py:334)
+        st = self._state(B, P, N, dev, dt, eos_token_id, pad_token_id, min_new_tokens, sample, stop or None, pmask is not None)
+        if sample is not None:
+            if sample_noise is not None:
+                st["u"].copy_(sample_noise.to(dev).reshape(N, B))
+            else:
+                st["u"].copy_(torch.rand(N, B, device=dev, generator=generator))
+        ending = eos_token_id is not None or stop is not None or text_stop is not None
+        last = self._prefill(st, inputs_embeds, pmask)
         self._reset(st, ending, P)
         first = self._pick(st, self._head(last), 0)      # the first token comes from the prefill, eagerly; the loop replays the other N - 1
         st["tok"].copy_(first)
@@ -1047,10 +1331,13 @@ class T5GreedyDecoder(_GraphDecoder):
 
     @torch.no_grad()
     def generate(self, inputs_embeds: Tensor, max_new_tokens: int, use_graph: bool = True, eos_token_id=None, pad_token_id: int = 0,
-                 min_new_tokens: int = 0, attention_mask: Optional[Tensor] = None) -> Tensor:
+                 min_new_tokens: int = 0, attention_mask: Optional[Tensor] = None, num_beams: int = 1, length_penalty: float = 1.0,
+                 repetition_penalty: float = 1.0) -> Tensor:
         """inputs_embeds [B, P, D] (encoder input) -> ids [B, 1 + n]: decoder_start_token_id, then n <= max_new_tokens
         greedy tokens (n < max_new_tokens only when every row has emitted ``eos_token_id``), as HF generate returns them.
-        ``attention_mask`` [B, P] of 0 / 1 (None: all ones): the encoder input's padding."""
+        ``attention_mask`` [B, P] of 0 / 1 (None: all ones): the encoder input's padding.  One beam and a neutral repetition penalty only."""
+        if int(num_beams) != 1 or float(repetition_penalty) != 1.0:
+            raise NotImplementedError("T5GreedyDecoder: num_beams > 1 / repetition_penalty are implemented for the Llama decoder only")
         B, P, _ = inputs_embeds.shape
         pmask = _padding(attention_mask, B, P)
         N = max_new_tokens
@@ -1136,6 +1423,7 @@ class Envelope(NamedTuple):
     neutral: dict
     sampling: bool
     need_max_new: bool
+    beams: bool = False      # opt-in (beam_search="graph"): Llama, num_beams > 1 with any positive repetition_penalty and any length_penalty
 
 
 _COMMON_KEYS = {"do_sample", "temperature", "top_p", "min_new_tokens", "eos_token_id", "pad_token_id", "num_beams", "repetition_penalty", "length_penalty"}
@@ -1148,6 +1436,34 @@ MODULE_ENVELOPE = Envelope(frozenset(_COMMON_KEYS | {"max_new_tokens", "use_cach
                            sampling=False, need_max_new=True)
 
 
+# the owner's opt-in (beam_search="graph"): the same, and deterministic beam search on Llama; the modules' configurations may then give the
+# length as HF's ``max_length`` / ``min_length`` (``generated_length``), as the shipped generate_configs do
+GENERATE_ENVELOPE_BEAMS = GENERATE_ENVELOPE._replace(beams=True)
+MODULE_ENVELOPE_BEAMS = MODULE_ENVELOPE._replace(keys=MODULE_ENVELOPE.keys | {"max_length", "min_length"}, beams=True)
+
+
+def envelope_for(owner, module: bool) -> Envelope:
+    """The envelope a caller plans with: today's, or its beam twin when the owner opted in (attribute ``beam_search``, "hf" when it has none)."""
+    graph = check_beam_search(getattr(owner, "beam_search", "hf")) == "graph"
+    if module:
+        return MODULE_ENVELOPE_BEAMS if graph else MODULE_ENVELOPE
+    return GENERATE_ENVELOPE_BEAMS if graph else GENERATE_ENVELOPE
+
+
+def generated_length(lm, request: dict, P: int) -> Optional[Tuple[int, Optional[int]]]:
+    """(max_new_tokens, min_new_tokens from ``min_length`` or None) of a request with HF's ``_prepare_generated_length`` semantics:
+    ``max_new_tokens`` wins over ``max_length``; a Llama over embeddings generates ``max_length - P`` tokens and blocks eos for
+    ``max(min_length - P, 0)``; T5 starts from one decoder token: ``max_length - 1`` and ``max(min_length - 1, 0)``.  None: no length given."""
+    used = 1 if getattr(lm.config, "model_type", "") == "t5" else P
+    if request.get("max_new_tokens") is not None:
+        n = int(request["max_new_tokens"])
+    elif request.get("max_length") is not None:
+        n = int(request["max_length"]) - used
+    else:
+        return None
+    return n, (max(int(request["min_length"]) - used, 0) if request.get("min_length") is not None else None)
+
+
 def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: Envelope) -> Optional[dict]:
     """The keyword arguments of ``decoder_for(owner, lm).generate(inputs_embeds, max_new_tokens, **plan)`` for a request HF ``generate`` would get
     as ``generate(inputs_embeds=..., attention_mask=..., **request)``, or None when it is outside what the graph decoders reproduce (then HF
@@ -1158,14 +1474,21 @@ def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: E
     mt = getattr(lm.config, "model_type", "")
     if not inputs_embeds.is_cuda or not ("llama" in mt or mt == "t5"):
         return None
-    if set(request) - env.keys or (env.need_max_new and "max_new_tokens" not in request):
+    if set(request) - env.keys or (env.need_max_new and "max_new_tokens" not in request and not (env.beams and request.get("max_length") is not None)):
         return None
     if lora_state(lm) not in (None, "ok"):      # adapters the decoders do not apply: HF generate runs the modules' own forward
         return None
-    if any(k in request and request[k] not in ok for k, ok in env.neutral.items()):
-        return None
     do_sample = bool(request.get("do_sample", False))
     crit = list(request["stopping_criteria"]) if request.get("stopping_criteria") is not None else []
+    K = request.get("num_beams", 1)
+    beams = env.beams and isinstance(K, int) and not isinstance(K, bool) and K > 1
+    if beams:      # deterministic beam search on Llama; any positive repetition penalty, any length penalty
+        rp, lp = request.get("repetition_penalty"), request.get("length_penalty")
+        rp, lp = (1.0 if rp is None else rp), (1.0 if lp is None else lp)
+        if "llama" not in mt or do_sample or crit or not all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in (rp, lp)) or not rp > 0:
+            return None
+    elif any(k in request and request[k] not in ok for k, ok in env.neutral.items()):
+        return None
     if (do_sample and not env.sampling) or any(not all(hasattr(c, a) for a in ("keyword_ids", "keywords", "tokenizer")) for c in crit):
         return None
     if mt == "t5" and (do_sample or crit):
@@ -1185,14 +1508,25 @@ def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: E
         if inputs_embeds.shape[0] != 1:
             raise AssertionError("Only support batch size 1 (yet)")      # (the reference's criteria)
         plan.update(keyword_stop_plan(crit))
+    if beams:
+        plan.update(num_beams=K, repetition_penalty=float(rp), length_penalty=float(lp))
     return plan
 
 
 def graph_generate(owner, lm, inputs_embeds: Tensor, attention_mask: Tensor, generate_configs: dict):
     """``lm.generate(inputs_embeds=..., attention_mask=..., **generate_configs)`` through the graph decoder when the configuration is inside
-    MODULE_ENVELOPE (``plan_decode``), else None (the caller then runs HF generate).  The decoder is cached on ``owner``."""
+    the owner's module envelope (``envelope_for``: MODULE_ENVELOPE, or MODULE_ENVELOPE_BEAMS when its ``beam_search`` is "graph"), else None (the
+    caller then runs HF generate).  The decoder is cached on ``owner``."""
     gc = dict(generate_configs or {})
-    plan = plan_decode(lm, inputs_embeds, attention_mask, gc, MODULE_ENVELOPE)
+    env = envelope_for(owner, module=True)
+    plan = plan_decode(lm, inputs_embeds, attention_mask, gc, env)
     if plan is None:
         return None
-    return decoder_for(owner, lm).generate(inputs_embeds, int(gc["max_new_tokens"]), **plan)
+    if not env.beams:
+        return decoder_for(owner, lm).generate(inputs_embeds, int(gc["max_new_tokens"]), **plan)
+    n, min_new = generated_length(lm, gc, inputs_embeds.shape[1])
+    if n <= 0:      # HF generate reports it in its own words
+        return None
+    if gc.get("min_new_tokens") is None and min_new is not None:      # (min_new_tokens wins over min_length, as in HF)
+        plan["min_new_tokens"] = min_new
+    return decoder_for(owner, lm).generate(inputs_embeds, n, **plan)

@@ -440,7 +440,7 @@ class _LSTPBase(nn.Module):
 
     def __init__(self, base_model_path, device="cuda", lora: bool = False, language_model: Optional[nn.Module] = None,
                  compute_dtype="bf16", raft_dtype=None, lm_dtype=None, tgb_cfg: Optional[synth.TgbCfg] = None, decode_weights: str = "bf16",
-                 kv_cache: str = "bf16"):
+                 kv_cache: str = "bf16", beam_search: str = "hf"):
         """Reference signature (eval/utils/model.py:21-45, :240-264): ``LSTP(base_model_path, device, lora=False)`` -- the
         HF config in ``base_model_path`` sizes the vision tower, Q-Former and language model (random init, the checkpoint
         fills them), the TGB is BERT-base with fusion_layer 6, RAFT is RAFT-large.  ``base_model_path`` may also be a
@@ -452,11 +452,14 @@ class _LSTPBase(nn.Module):
         ("bf16"; "fp8" = opt-in: the graph decoder streams the Llama projections and lm_head as per-row e4m3 codes -- half the weight bytes per
         token, and the ids are those of the quantised model, not the reference's; see decode.GreedyDecoder), ``kv_cache`` ("bf16"; "fp8" =
         opt-in: the graph decoder keeps the Llama K/V cache as per-row e4m3 codes -- half the cache bytes per token and per state; the ids are
-        those of the model whose K/V are rounded that way, not the reference's; see decode.GreedyDecoder)."""
+        those of the model whose K/V are rounded that way, not the reference's; see decode.GreedyDecoder), ``beam_search`` ("hf": requests with
+        ``num_beams`` > 1 run on HF generate, as before; "graph" = opt-in: the Llama graph decoder runs HF's deterministic beam search --
+        num_beams, repetition_penalty, length_penalty -- on its own kernels; see decode.GreedyDecoder.generate)."""
         super().__init__()
-        from .decode import check_decode_weights, check_kv_cache
+        from .decode import check_beam_search, check_decode_weights, check_kv_cache
         self.decode_weights = check_decode_weights(decode_weights)      # (decode.decoder_for reads it from its owner)
         self.kv_cache = check_kv_cache(kv_cache)                        # (likewise)
+        self.beam_search = check_beam_search(beam_search)               # (decode.envelope_for reads it from its owner)
         hf_config = None
         if isinstance(base_model_path, synth.PathCfg):
             cfg = base_model_path
@@ -498,8 +501,8 @@ class _LSTPBase(nn.Module):
 
     @classmethod
     def from_cfg(cls, cfg: synth.PathCfg, device="cuda", language_model: Optional[nn.Module] = None, compute_dtype="bf16", raft_dtype=None,
-                 decode_weights: str = "bf16", kv_cache: str = "bf16"):
-        return cls(cfg, device, False, language_model, compute_dtype, raft_dtype, decode_weights=decode_weights, kv_cache=kv_cache)
+                 decode_weights: str = "bf16", kv_cache: str = "bf16", beam_search: str = "hf"):
+        return cls(cfg, device, False, language_model, compute_dtype, raft_dtype, decode_weights=decode_weights, kv_cache=kv_cache, beam_search=beam_search)
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         """Accepts a reference (Lightning) checkpoint's ``state_dict`` as is: peft's ``language_model.base_model.model.``
@@ -581,11 +584,12 @@ class _LSTPBase(nn.Module):
         return self.model.language_projection.pool(qo, [nframe] * batch_size, pool)
 
     @staticmethod
-    def _graph_plan(lm, inputs_embeds, attention_mask, do_sample, temperature, stopping_criteria, kw):
-        """``decode.plan_decode`` for LSTP.generate's own parameters and its ``**gen_kwargs`` (``kw``): the decoder's keyword arguments, or None."""
+    def _graph_plan(lm, inputs_embeds, attention_mask, do_sample, temperature, stopping_criteria, kw, env=None):
+        """``decode.plan_decode`` for LSTP.generate's own parameters and its ``**gen_kwargs`` (``kw``): the decoder's keyword arguments, or None.
+        ``env``: the caller's envelope (None: GENERATE_ENVELOPE)."""
         from .decode import GENERATE_ENVELOPE, plan_decode
         return plan_decode(lm, inputs_embeds, attention_mask, dict(kw, do_sample=do_sample, temperature=temperature, stopping_criteria=stopping_criteria),
-                           GENERATE_ENVELOPE)
+                           GENERATE_ENVELOPE if env is None else env)
 
     # ---- the reference entry point ---------------------------------------------------------------
     @torch.no_grad()
@@ -631,7 +635,9 @@ class _LSTPBase(nn.Module):
         attention_mask = torch.cat([lm_mask, text_encoding["attention_mask"]], dim=1)
         inputs_embeds = self.model.get_input_embeddings()(text_encoding["input_ids"])
         inputs_embeds = torch.cat([lm_inputs, inputs_embeds.to(lm_dtype)], dim=1)
-        plan = None if fast_decode is False else self._graph_plan(lm, inputs_embeds, attention_mask, do_sample, temperature, stopping_criteria, dict(gen_kwargs))
+        from .decode import envelope_for
+        plan = None if fast_decode is False else self._graph_plan(lm, inputs_embeds, attention_mask, do_sample, temperature, stopping_criteria, dict(gen_kwargs),
+                                                                  envelope_for(self, module=False))
         if fast_decode is True and plan is None:      # (nothing is dropped silently -- and nothing is decoded first)
             raise TypeError(f"generate(fast_decode=True): outside the graph decoder's envelope (do_sample={do_sample}, stopping_criteria="
                             f"{type(stopping_criteria).__name__}, kwargs {sorted(gen_kwargs)}); call with fast_decode=False or \"auto\"")

@@ -502,6 +502,73 @@ def decode_attention_fp8(q: Tensor, kc8: Tensor, vc8: Tensor, ks: Tensor, vs: Te
     return out
 
 
+# ---- beam search on the Llama decode step (opt-in: beam_search="graph").  R = B * K beam rows, the beams of item b are rows b K .. b K + K - 1.
+BEAM_MAX_BEAMS = 16
+BEAM_MAX_VOCAB = 1 << 20
+
+
+def decode_attention_beam_ok(tmax_p: int, tmax_g: int, hd: int) -> bool:
+    """Whether vtgb_llm_decode_attention_beam takes these cache lengths and head_dim (the split kernel's limits on tmax_p + tmax_g)."""
+    return hd in (64, 128) and tmax_p > 0 and tmax_g > 0 and tmax_p % 64 == 0 and tmax_g % 64 == 0 and tmax_p + tmax_g <= DECODE_SPLIT_MAX_KEYS
+
+
+def decode_attention_beam(q: Tensor, kp: Tensor, vp: Tensor, kg: Tensor, vg: Tensor, src_row: Tensor, n_prompt: Tensor, pos: Tensor, scale: float,
+                          key_valid: Optional[Tensor] = None, out: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
+    """``decode_attention(split=True)`` for the R = B * K beam rows of a batch, over two K/V sources and without K/V copies: q [R, nq*hd];
+    kp / vp [B, nkv, tmax_p, hd] the prompt cache (once per batch item); kg / vg [R, nkv, tmax_g, hd] what the beams generated, one slot per
+    step; src_row [R, tmax_g] int32, the generated-cache row that holds row r's key of slot s.  Key t of row r is ``kp[r // K, :, t]`` for
+    t < n_prompt, else ``kg[src_row[r, t - n_prompt], :, t - n_prompt]``; visible while t <= pos (n_prompt, pos: device int64) and, for
+    prompt keys, ``key_valid`` [B, tmax_p] uint8 != 0.  The result equals ``decode_attention(q, K, V, pos, scale, split=True)`` on the caches
+    K / V [R, nkv, T, hd] materialised by that gather, bit for bit.  ``workspace``: ``decode_attention_workspace_bytes(R, nq, hd, tmax_p + tmax_g)``."""
+    _need_cuda(q, kp, vp, kg, vg, src_row, n_prompt, pos)
+    B, nkv, tmax_p, hd = kp.shape
+    R, _, tmax_g, _ = kg.shape
+    nq = q.numel() // (R * hd)
+    assert R % B == 0 and kg.shape == (R, nkv, tmax_g, hd) and vp.shape == kp.shape and vg.shape == kg.shape
+    assert all(t.is_contiguous() for t in (q, kp, vp, kg, vg, src_row)) and q.dtype == kp.dtype == vp.dtype == kg.dtype == vg.dtype
+    assert src_row.dtype == torch.int32 and src_row.shape == (R, tmax_g) and pos.dtype == torch.int64 and n_prompt.dtype == torch.int64
+    assert key_valid is None or (key_valid.dtype == torch.uint8 and key_valid.shape == (B, tmax_p) and key_valid.is_contiguous())
+    if out is None:
+        out = torch.empty(R, nq * hd, dtype=q.dtype, device=q.device)
+    need = decode_attention_workspace_bytes(R, nq, hd, tmax_p + tmax_g)
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)
+    assert workspace.numel() * workspace.element_size() >= need, "decode_attention_beam: workspace too small"
+    a = L.LlmDecodeAttentionBeamArgs(dtype_code(q.dtype), R, R // B, nq, nkv, hd, tmax_p, tmax_g, float(scale), _ptr(q), _ptr(kp), _ptr(vp), _ptr(kg),
+                                     _ptr(vg), _ptr(src_row), _ptr(out), _ptr(n_prompt), _ptr(pos), _ptr(key_valid), _ptr(workspace))
+    L.check(L.lib().vtgb_llm_decode_attention_beam(C.byref(a), _stream()))
+    return out
+
+
+def beam_candidates_workspace_bytes(R: int, K: int, V: int) -> int:
+    """vtgb_llm_beam_candidates' workspace: the rows' fp32 log-probabilities and their 2 K candidates each."""
+    return R * V * 4 + R * 2 * K * 8
+
+
+def beam_candidates(logits: Tensor, seq: Tensor, step: Tensor, running: Tensor, repetition_penalty: float = 1.0, eos: Optional[int] = None,
+                    min_new: int = 0, out: Optional[Tuple[Tensor, Tensor]] = None, workspace: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """One beam-search step's candidates (vtgb_llm_beam_candidates): logits [B*K, V] bf16 / fp32, seq [B*K, N] int64 generated ids of which the
+    first ``step`` (device int64) count, running [B, K] fp32 -> (cand_score [B, 2K] fp32, cand_idx [B, 2K] int32 = k * V + token): per batch
+    item the 2K largest of ``log_softmax(logits.float())`` after HF's repetition penalty on the ids generated so far (each once), with
+    ``eos`` at -inf while step < min_new, plus the running score of the row -- descending, equal scores in ascending index."""
+    _need_cuda(logits, seq, step, running)
+    R, V = logits.shape
+    B, K = running.shape
+    N = seq.shape[1]
+    assert R == B * K and seq.shape == (R, N) and seq.dtype == torch.int64 and step.dtype == torch.int64 and running.dtype == torch.float32
+    assert logits.is_contiguous() and seq.is_contiguous() and running.is_contiguous()
+    if out is None:
+        out = (torch.empty(B, 2 * K, dtype=torch.float32, device=logits.device), torch.empty(B, 2 * K, dtype=torch.int32, device=logits.device))
+    need = beam_candidates_workspace_bytes(R, K, V)
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=logits.device)
+    a = L.LlmBeamCandidatesArgs(dtype_code(logits.dtype), R, K, V, N, -1 if eos is None else int(eos), int(min_new), float(repetition_penalty),
+                                _ptr(logits), _ptr(seq) if N else None, _ptr(step), _ptr(running), _ptr(out[0]), _ptr(out[1]), _ptr(workspace),
+                                workspace.numel() * workspace.element_size())
+    L.check(L.lib().vtgb_llm_beam_candidates(C.byref(a), _stream()))
+    return out
+
+
 def lora_update(x: Tensor, y: Tensor, segments) -> Tensor:
     """Unmerged LoRA adapters on a projection's output, in place (vtgb_llm_lora): for every ``(col0, A, B, scaling)`` of ``segments`` (1 .. 4,
     disjoint column ranges), ``y[:, col0 : col0 + n] += ((x.float() @ A.T) @ B.T * scaling).to(y.dtype)`` -- train.LoraLinear.forward in eval
