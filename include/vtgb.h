@@ -907,6 +907,21 @@ typedef struct {
 } vtgb_llm_beam_candidates_args;
 int vtgb_llm_beam_candidates(const vtgb_llm_beam_candidates_args* a, vtgb_stream_t stream);
 
+/* ---- Beam search on the T5 decode step (opt-in: beam_search = "graph+t5"; llm.hip; added at version 601 without a bump).
+ * vtgb_llm_attention_rows_beam: vtgb_llm_attention_rows in its decode form -- `pos` given, keys [0, *pos], bias row *pos -- over the caches
+ *   k / v of `cache_rows` rows (row stride kv_batch), where K and V of key t of query row r come from cache row
+ *   clamp(src_row[r * src_row_stride + t], 0, cache_rows - 1) instead of row r / rows_per_batch (int32 table, stride in elements): the beam
+ *   rows keep what they generated in place and re-ordering beams re-orders the table.  One wave per (row, head), key t on lane t % 64, the
+ *   rounding points and the order of every sum are vtgb_llm_attention_rows': the output equals that entry's on the gathered cache
+ *   (k'[r, :, t] = k[src_row[r, t], :, t]) BIT FOR BIT, in bf16 and in fp32.  Table entries at slots past *pos are not read, neither are K/V
+ *   slots past *pos (*pos is clamped to t_pad - 1); a wrong entry at a visible slot gives wrong numbers, never a read outside the caches.
+ *   VTGB_EINVAL: NULL src_row, NULL pos, cache_rows < 1, src_row_stride < t_pad, and what vtgb_llm_attention_rows calls so;
+ *   VTGB_EUNSUPPORTED: what vtgb_llm_attention_rows refuses, and t_pad > VTGB_LLM_ATTN_ROWS_BEAM_MAX_T (scores and the table rows of four
+ *   waves in 64 KiB of LDS) -- on the host, before any launch. */
+#define VTGB_LLM_ATTN_ROWS_BEAM_MAX_T 1920
+int vtgb_llm_attention_rows_beam(const vtgb_llm_attn_rows_args* a, const int32_t* src_row, int64_t src_row_stride, int32_t cache_rows,
+                                 vtgb_stream_t stream);
+
 /* ---- LoRA adapters on the language model's q / k / v projections (lora.hip; added at version 601 without a bump).  An in-place low-rank
  *   update of a projection's output -- videotgb_amd.train.LoraLinear.forward in eval mode (peft 0.4.0 tuners.lora.Linear, unmerged, fp32
  *   adapters), rounding for rounding:

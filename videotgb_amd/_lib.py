@@ -46,7 +46,7 @@ EXPORTS = [
     "vtgb_llm_decode_attention_split_workspace_bytes", "vtgb_llm_decode_attention_split",
     "vtgb_llm_decode_attention_split_fp8", "vtgb_llm_rope_cache_fp8", "vtgb_llm_rope_cache_prefill_fp8",
     "vtgb_raft_lookup_convc1", "vtgb_raft_gru_half", "vtgb_llm_lora", "vtgb_conv_launch", "vtgb_attention_cached",
-    "vtgb_llm_decode_attention_beam", "vtgb_llm_beam_candidates",
+    "vtgb_llm_decode_attention_beam", "vtgb_llm_beam_candidates", "vtgb_llm_attention_rows_beam",
 ]
 COMM_ID_BYTES = 128
 
@@ -352,6 +352,8 @@ def lib() -> C.CDLL:
     L.vtgb_llm_decode_attention_beam.restype = C.c_int
     L.vtgb_llm_beam_candidates.argtypes = [C.POINTER(LlmBeamCandidatesArgs), vp]
     L.vtgb_llm_beam_candidates.restype = C.c_int
+    L.vtgb_llm_attention_rows_beam.argtypes = [C.POINTER(LlmAttnRowsArgs), vp, i64, i32, vp]
+    L.vtgb_llm_attention_rows_beam.restype = C.c_int
     L.vtgb_llm_lora.argtypes = [C.POINTER(LlmLoraArgs), vp]
     L.vtgb_llm_lora.restype = C.c_int
     L.vtgb_llm_rope_cache_prefill_fp8.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]

@@ -699,6 +699,90 @@ extern "C" int vtgb_llm_attention_rows_masked(const vtgb_llm_attn_rows_args* a, 
     return VTGB_OK;
 }
 
+// ---- beam search on the T5 decoder (opt-in: beam_search="graph+t5"): attn_rows_body's decode form (pos given, keys [0, *pos], bias row
+// *pos) where K and V of key t of query row r come from cache row clamp(src_row[r * src_stride + t], 0, cache_rows - 1) -- the beam that
+// wrote slot t of row r's ancestry -- instead of row r / rows_per_batch, so re-ordering beams re-orders an int32 table and never K/V.  The
+// lane that owns key t (t % 64) reads its table entry once and leaves the clamped row in LDS next to the score; the V pass reads it back
+// for every lane (one address per wave: a broadcast).  Rounding points and the order of every sum are attn_rows_body's, so the output
+// equals vtgb_llm_attention_rows on the gathered cache bit for bit.  Table entries and K/V slots past *pos are never read (*pos itself is
+// clamped to t_pad - 1: the score and row buffers hold t_pad entries).
+constexpr int ATTN_ROWS_BEAM_MAX_T = VTGB_LLM_ATTN_ROWS_BEAM_MAX_T;      // 1920: 4 waves x (head_dim <= 256 + 2 x t_pad) words = the 64 KiB a launch gets without opting in to more
+
+template <typename T>
+__global__ __launch_bounds__(256) void llm_attn_rows_beam_kernel(const vtgb_llm_attn_rows_args a, const int32_t* __restrict__ src_row, int64_t src_stride,
+                                                                 int cache_rows) {
+    extern __shared__ float dsm[];   // per wave: hd floats of q + t_pad scores + t_pad cache rows
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int hd = a.head_dim, nq = a.heads;
+    const int64_t idx = (int64_t)blockIdx.x * 4 + wave;
+    const int64_t total = (int64_t)a.rows * nq;
+    const int64_t id = idx < total ? idx : total - 1;
+    const int64_t r = id / nq;
+    const int head = (int)(id - r * nq);
+    const int64_t p64 = *a.pos;
+    const int qpos = (int)(p64 < 0 ? 0 : p64 >= a.t_pad ? a.t_pad - 1 : p64);
+    const int n_keys = p64 < 0 ? 0 : qpos + 1;
+    float* qs = dsm + wave * (hd + 2 * a.t_pad);
+    float* sc = qs + hd;
+    int* rows = reinterpret_cast<int*>(sc + a.t_pad);
+    const T* qr = reinterpret_cast<const T*>(a.q) + r * a.q_row + (int64_t)head * hd;
+    const T* kr = reinterpret_cast<const T*>(a.k) + (int64_t)head * a.kv_head;
+    const T* vr = reinterpret_cast<const T*>(a.v) + (int64_t)head * a.kv_head;
+    const T* br = a.bias ? reinterpret_cast<const T*>(a.bias) + (int64_t)qpos * a.bias_pos + (int64_t)head * a.bias_head : nullptr;
+    const int32_t* sr = src_row + r * src_stride;
+    for (int d = lane; d < hd; d += 64) qs[d] = (float)qr[d];
+    __syncthreads();
+    float mx = -INFINITY;
+    for (int key = lane; key < n_keys; key += 64) {
+        const int s = sr[key];
+        const int row = s < 0 ? 0 : s >= cache_rows ? cache_rows - 1 : s;
+        rows[key] = row;
+        const T* k = kr + (int64_t)row * a.kv_batch + (int64_t)key * a.kv_tok;
+        float dot = 0.f;
+        for (int d = 0; d < hd; d++) dot = fmaf(qs[d], (float)k[d], dot);
+        dot = Cvt<T>::rnd(dot * a.scale);
+        if (br) dot = Cvt<T>::rnd(dot + (float)br[key]);
+        sc[key] = dot;
+        mx = fmaxf(mx, dot);
+    }
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    float sum = 0.f;
+    for (int key = lane; key < n_keys; key += 64) {
+        const float e = expf(sc[key] - mx);
+        sc[key] = e;
+        sum += e;
+    }
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+    __syncthreads();
+    const float inv = 1.0f / sum;
+    if (idx < total) {
+        T* o = reinterpret_cast<T*>(a.out) + r * a.o_row + (int64_t)head * hd;
+        for (int d = lane; d < hd; d += 64) {
+            float acc = 0.f;
+            for (int key = 0; key < n_keys; key++) {
+                const float v = (float)vr[(int64_t)rows[key] * a.kv_batch + (int64_t)key * a.kv_tok + d];
+                acc = fmaf(Cvt<T>::rnd(sc[key] * inv), v, acc);
+            }
+            o[d] = Cvt<T>::to(acc);
+        }
+    }
+}
+
+extern "C" int vtgb_llm_attention_rows_beam(const vtgb_llm_attn_rows_args* a, const int32_t* src_row, int64_t src_row_stride, int32_t cache_rows,
+                                            vtgb_stream_t s) {
+    if (const int rc = attn_rows_check(a)) return rc;
+    VTGB_REQUIRE(src_row && a->pos && cache_rows >= 1 && src_row_stride >= a->t_pad, VTGB_EINVAL,
+                 "llm_attention_rows_beam: src_row, pos, cache_rows >= 1 and a table stride >= t_pad");
+    VTGB_REQUIRE(a->t_pad <= ATTN_ROWS_BEAM_MAX_T, VTGB_EUNSUPPORTED, "llm_attention_rows_beam: t_pad=%d, built for up to %d (scores and the table in LDS)",
+                 a->t_pad, ATTN_ROWS_BEAM_MAX_T);
+    const size_t lds = 4 * (size_t)(a->head_dim + 2 * a->t_pad) * sizeof(float);
+    const dim3 grid((unsigned)(((int64_t)a->rows * a->heads + 3) / 4));
+    if (a->dtype == VTGB_BF16) hipLaunchKernelGGL(llm_attn_rows_beam_kernel<bf16_t>, grid, dim3(256), lds, s, *a, src_row, src_row_stride, cache_rows);
+    else hipLaunchKernelGGL(llm_attn_rows_beam_kernel<float>, grid, dim3(256), lds, s, *a, src_row, src_row_stride, cache_rows);
+    VTGB_HIP(hipGetLastError());
+    return VTGB_OK;
+}
+
 // ---- feed-forward activations of the language models: act[r, i] = f(gu[r, i]) (* gu[r, I + i] when gated).  kind 0 SiLU (Llama's SwiGLU = vtgb_llm_silu_mul),
 // 1 gelu_new (T5 v1.1 / Flan-T5 "gated-gelu": 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3)))), 2 ReLU (original T5), 3 exact GELU.
 template <typename T>

@@ -79,11 +79,12 @@ def check_kv_cache(kv_cache) -> str:
     return kv_cache
 
 
-BEAM_SEARCH = ("hf", "graph")
+BEAM_SEARCH = ("hf", "graph", "graph+t5")
 
 
 def check_beam_search(beam_search) -> str:
-    """Who runs a beam-search request: "hf" (HF generate, the default) or "graph" (opt-in: the Llama graph decoder); ValueError otherwise."""
+    """Who runs a beam-search request: "hf" (HF generate, the default), "graph" (opt-in: the Llama graph decoder; a T5's beam requests stay
+    on HF) or "graph+t5" (opt-in: that, and the T5 graph decoder); ValueError otherwise."""
     if beam_search not in BEAM_SEARCH:
         raise ValueError(f"beam_search must be one of {BEAM_SEARCH}, got {beam_search!r}")
     return beam_search
@@ -1230,24 +1231,31 @@ class T5GreedyDecoder(_GraphDecoder):
         x, h, q = st["x"], st["h"], st["q"]
         x.copy_(lm.decoder.embed_tokens(st["tok"]))
         ws, pos = st.get("sk_ws"), st["pos"]
+        # a beam state (st["attn"] == "beam"): the rows are the B = items x K beams; a row appends its K/V at slot *pos of its own cache row and
+        # reads the slots of its ancestry through ``src_row`` (vtgb_llm_attention_rows_beam); the encoder states are the batch item's (K rows each)
+        beam = st.get("attn") == "beam"
+        K = st["beam"]["K"] if beam else 1
         delta = None
         for li, w in enumerate(self.layers):
             self._rms(x, delta, w["ln0"], h)
             qkv = self._lin(h, w["wqkv"], ws)                                                                # [B, 3 H dk] = [B, (q | k | v heads), dk]
             L.check(L.lib().vtgb_llm_rope_cache(dtype_code(x.dtype), _ptr(qkv), _ptr(q), _ptr(st["kc"][li]), _ptr(st["vc"][li]), None, None, _ptr(pos),
                                                 B, H, H, dk, N, _stream()))                                  # (no rotary: cache append)
-            a = self._attn_rows(q, HD, st["kc"][li], st["vc"][li], (H * N * dk, N * dk, dk), B, 1, 0, N, st["rel"], (N, N * N), pos)
+            if beam:
+                a = ops.attention_rows_beam(q, st["kc"][li], st["vc"][li], st["src_row"], pos, self.scaling, bias=st["rel"])
+            else:
+                a = self._attn_rows(q, HD, st["kc"][li], st["vc"][li], (H * N * dk, N * dk, dk), B, 1, 0, N, st["rel"], (N, N * N), pos)
             o = self._lin(a, w["wo"], ws)
             self._rms(x, o, w["ln1"], h)
             cq = self._lin(h, w["cq"], ws)
-            ckv = st["ckv"][li].view(B * Pb, 2 * HD)                                                         # k | v of the encoder states, rows [0, *plen] of every batch entry valid
-            a = self._attn_rows(cq, HD, ckv, ckv[:, HD:], (Pb * 2 * HD, dk, 2 * HD), B, 1, 0, Pb, None, (0, 0), st["plen"], st.get("ckv_valid"))
+            ckv = st["ckv"][li].view(-1, 2 * HD)                                                             # k | v of the encoder states, rows [0, *plen] of every batch entry valid
+            a = self._attn_rows(cq, HD, ckv, ckv[:, HD:], (Pb * 2 * HD, dk, 2 * HD), B, K, 0, Pb, None, (0, 0), st["plen"], st.get("ckv_valid"))
             o = self._lin(a, w["co"], ws)
             self._rms(x, o, w["ln2"], h)
             delta = self._ffn(h, w, ws)
         self._rms(x, delta, lm.decoder.final_layer_norm.weight, h)
         hh = h * (self.D ** -0.5) if self.scale_out else h
-        self._emit(st, self._lin(hh, lm.lm_head.weight, ws))
+        (self._beam_emit if beam else self._emit)(st, self._lin(hh, lm.lm_head.weight, ws))
 
     def _norm(self, x: Tensor, w: Tensor) -> Tensor:
         # T5LayerNorm.forward: fp32 variance, no mean subtraction, no bias; cast to the weight's dtype when it is half / bf16
@@ -1257,13 +1265,26 @@ class T5GreedyDecoder(_GraphDecoder):
             y = y.to(w.dtype)
         return w * y
 
-    def _state(self, B, P, N, device, dtype, eos, pad, min_new, padded=False):
+    def _state(self, B, P, N, device, dtype, eos, pad, min_new, padded=False, beam: Optional[dict] = None):
         # On libvtgb.so the encoder length is DEVICE data (`plen`, read by the cross-attention kernel) and the cross-attention K | V live in
         # persistent buffers of a bucketed length (multiples of 64): an eval loop over real questions of varying length reuses a handful of
         # captured graphs (round-3 VERDICT: the state keyed on the exact P).  The torch path (CPU, fused=False) keeps exact-P caches.
-        hip = self._hip(torch.empty(0, device=device, dtype=dtype)) and P <= self.MAX_KEYS and N <= self.MAX_KEYS
+        # ``beam`` (K, fill, repetition_penalty, length_penalty; opt-in, beam_search="graph+t5"): a state of R = B * K decoder rows.  On
+        # libvtgb.so the encoder's K | V and key mask stay B rows (the cross-attention reads item r / K) and the self-attention caches are
+        # kc / vc [R, H, N, dk] -- row r holds what beam row r appended, one slot per decoder position -- read through the int32 ancestry table
+        # ``src_row`` [R, N + 1] (slot N is the append target named after the last step and never read); K/V are never copied.  On the torch
+        # path the rows keep whole caches, re-ordered by index_select as HF re-orders its cache, and the encoder's K / V are repeated per row.
+        hip = self._hip(torch.empty(0, device=device, dtype=dtype))
+        if beam is not None and hip and (P > self.MAX_KEYS or N > ops.ATTENTION_ROWS_BEAM_MAX_KEYS):
+            raise NotImplementedError(f"num_beams > 1 on the device: up to {self.MAX_KEYS} encoder positions and {ops.ATTENTION_ROWS_BEAM_MAX_KEYS} new "
+                                      f"tokens ({P}, {N})")
+        hip = hip and P <= self.MAX_KEYS and N <= self.MAX_KEYS
         Pb = -(-P // 64) * 64 if hip else P
         H, dk, nl = self.H, self.dk, len(self.layers)
+        items = Be = B                           # batch items; rows of the encoder-side buffers
+        if beam is not None:
+            B = B * beam["K"]                    # rows of the decoder step
+            Be = Be if hip else B
 
         def z(*shape, dtype=dtype):
             return torch.zeros(*shape, device=device, dtype=dtype)
@@ -1276,13 +1297,22 @@ class T5GreedyDecoder(_GraphDecoder):
             st = dict(bias=bias + causal[:, None, :], rel=bias.permute(1, 0, 2).contiguous(), N=N, Pb=Pb, hip=hip,      # rel [H, N (query), N (key)]: the kernel's layout (causality = its key range)
                       x=z(B, self.D), h=z(B, self.D), q=z(B, H * dk),
                       # cross-attention K | V of every decoder layer [B, Pb, 2 H dk] (fixed addresses: the captured graph reads them) and the encoder length - 1
-                      ckv=[z(B, Pb, 2 * H * dk) for _ in range(nl)] if hip else [None] * nl, plen=z(1, dtype=torch.long),
+                      ckv=[z(Be, Pb, 2 * H * dk) for _ in range(nl)] if hip else [None] * nl, plen=z(1, dtype=torch.long),
                       kc=[z(B, H, N, dk) for _ in range(nl)], vc=[z(B, H, N, dk) for _ in range(nl)],
-                      ck=[] if hip else [z(B, H, P, dk) for _ in range(nl)], cv=[] if hip else [z(B, H, P, dk) for _ in range(nl)])
+                      ck=[] if hip else [z(Be, H, P, dk) for _ in range(nl)], cv=[] if hip else [z(Be, H, P, dk) for _ in range(nl)])
             if padded and hip:      # cross-attention key mask over the bucketed encoder length (written before every call)
-                st["ckv_valid"] = z(B, Pb, dtype=torch.uint8)
+                st["ckv_valid"] = z(Be, Pb, dtype=torch.uint8)
             elif padded:
-                st["cmask"] = z(B, 1, 1, P)
+                st["cmask"] = z(Be, 1, 1, P)
+            if beam is not None:
+                K, V = beam["K"], self.lm.lm_head.weight.shape[0]
+                st.update(self._beam_book(items, K, N, device, beam["fill"]))
+                st.update(beam=dict(beam, kernel=hip), attn="beam" if hip else None, pen_step=z(1, dtype=torch.long),
+                          pen_seq=torch.full((B, N + 1), self.start, dtype=torch.long, device=device))
+                if hip:
+                    st.update(src_row=z(B, N + 1, dtype=torch.int32), row_id=torch.arange(B, dtype=torch.int32, device=device)[:, None],
+                              cand_ws=z(ops.beam_candidates_workspace_bytes(B, K, V), dtype=torch.uint8),
+                              feedback=("tok", "pos", "step", "src_row") + self.BEAM_BOOK)
             if device.type == "cuda" and dtype == torch.bfloat16 and self.fused and B <= 128:
                 shapes = [(3 * H * dk, self.D), (self.D, H * dk), (H * dk, self.D), (self.layers[0]["wi"].shape[0], self.D), (self.D, self.cfg.d_ff),
                           (self.lm.lm_head.weight.shape[0], self.D)]
@@ -1290,7 +1320,10 @@ class T5GreedyDecoder(_GraphDecoder):
                 if need:
                     st["sk_ws"] = z(need, dtype=torch.uint8)
             return st
-        return self._cached_state((B, Pb, N, eos, pad, min_new, hip, padded), B, N, N, device, eos, pad, min_new, None, None, buffers)
+        key = (B, Pb, N, eos, pad, min_new, hip, padded)
+        if beam is not None:      # (keyed by K and the penalties as well: they are constants of the captured step)
+            key = ("beams", items, beam["K"], beam["repetition_penalty"], beam["length_penalty"]) + key[1:]
+        return self._cached_state(key, B, N, N if beam is None else N + 1, device, eos, pad, min_new, None, None, buffers)
 
     def _decode_step(self, st):
         """One token for every sequence, entirely on the device (captured): `tok` at decoder position `pos` -> next token."""
@@ -1327,25 +1360,84 @@ class T5GreedyDecoder(_GraphDecoder):
         h = self._norm(x, lm.decoder.final_layer_norm.weight)
         if self.scale_out:
             h = h * (self.D ** -0.5)
-        self._emit(st, F.linear(h, lm.lm_head.weight))
+        (self._beam_emit if "beam" in st else self._emit)(st, F.linear(h, lm.lm_head.weight))
+
+    # ---- beam search (opt-in at the interfaces: beam_search="graph+t5"): HF's ``_beam_search`` over an encoder-decoder, on the shared bookkeeping of
+    # ``_GraphDecoder``.  What differs from the Llama case: every one of the N tokens is a decoder step from the start token (the first runs K
+    # identical rows with running scores [0, -1e9, ...]); HF's decoder input is the start token, so ``decoder_prompt_len`` is 1 and the
+    # repetition-penalty processor sees that token next to the generated ids -- every length, length-penalty and early-stop count stays the
+    # number of generated tokens.
+    def _beam_candidates(self, st, logits: Tensor):
+        """The shared statement over the ids HF's processors see: the start token, then the ``*step`` generated ids (``pen_seq`` [R, 1 + N] and
+        ``pen_step`` = step + 1; the eos block counts generated tokens, so it ends at min_new + 1 of these)."""
+        bm, step = st["beam"], st["step"]
+        B, K, N = st["run_seq"].shape
+        V = logits.shape[-1]
+        st["pen_seq"][:, 1:].copy_(st["run_seq"].view(B * K, N))
+        st["pen_step"].copy_(step + 1)
+        if bm["kernel"]:
+            sc, ix = ops.beam_candidates(logits, st["pen_seq"], st["pen_step"], st["run_scores"], bm["repetition_penalty"], st["eos"],
+                                         st["min_new"] + 1 if st["min_new"] > 0 else 0, out=(st["cand_score"], st["cand_idx"]), workspace=st["cand_ws"])
+            return sc, ix.long()
+        lp = F.log_softmax(logits.float(), dim=-1)
+        if bm["repetition_penalty"] != 1.0:      # RepetitionPenaltyLogitsProcessor on the log-probabilities; ids behind the step go to a spare column
+            ids = torch.where(st["ar"][None, :N + 1] < st["pen_step"], st["pen_seq"], torch.full_like(st["pen_seq"], V))
+            lp = torch.cat((lp, torch.zeros_like(lp[:, :1])), dim=-1)
+            g = lp.gather(1, ids)
+            lp = lp.scatter(1, ids, torch.where(g < 0, g * bm["repetition_penalty"], g / bm["repetition_penalty"]))[:, :V]
+        if st["eos"] is not None and st["min_new"] > 0:
+            lp = lp.clone()
+            lp[:, st["eos"]] = torch.where(step < st["min_new"], torch.full_like(lp[:, st["eos"]], float("-inf")), lp[:, st["eos"]])
+        acc = (lp.view(B, K, V) + st["run_scores"][:, :, None]).reshape(B, K * V)
+        return torch.topk(acc, k=2 * K)
+
+    def _beam_emit(self, st, logits: Tensor):
+        """``_emit`` of a beam state: the selection, then the beams' K/V follow their parents -- the ancestry table on the device
+        (src_row' = src_row[parent]; the slot the chosen tokens will be appended at, *step + 1, is the row's own), whole caches elsewhere."""
+        rows = self._beam_select(st, logits)
+        if st["attn"] == "beam":
+            st["src_row"].copy_(st["src_row"].index_select(0, rows))
+            st["src_row"].index_copy_(1, st["step"] + 1, st["row_id"])
+        else:
+            for c in st["kc"] + st["vc"]:
+                c.copy_(c.index_select(0, rows))
+        st["pos"].add_(1)
+        st["step"].add_(1)
 
     @torch.no_grad()
     def generate(self, inputs_embeds: Tensor, max_new_tokens: int, use_graph: bool = True, eos_token_id=None, pad_token_id: int = 0,
                  min_new_tokens: int = 0, attention_mask: Optional[Tensor] = None, num_beams: int = 1, length_penalty: float = 1.0,
-                 repetition_penalty: float = 1.0) -> Tensor:
+                 repetition_penalty: float = 1.0, do_sample: bool = False, stop_ids=None, text_stop=None) -> Tensor:
         """inputs_embeds [B, P, D] (encoder input) -> ids [B, 1 + n]: decoder_start_token_id, then n <= max_new_tokens
         greedy tokens (n < max_new_tokens only when every row has emitted ``eos_token_id``), as HF generate returns them.
-        ``attention_mask`` [B, P] of 0 / 1 (None: all ones): the encoder input's padding.  One beam and a neutral repetition penalty only."""
-        if int(num_beams) != 1 or float(repetition_penalty) != 1.0:
-            raise NotImplementedError("T5GreedyDecoder: num_beams > 1 / repetition_penalty are implemented for the Llama decoder only")
+        ``attention_mask`` [B, P] of 0 / 1 (None: all ones): the encoder input's padding.
+        ``num_beams`` > 1: HF's deterministic beam search (``_beam_search``, early_stopping False) with ``length_penalty`` and
+        ``repetition_penalty`` -- the start token, then per batch item the best finished beam, cropped to the longest, finished rows filled
+        with ``pad_token_id or eos_token_id``.  Sampling and stopping criteria are not served (NotImplementedError), nor is a repetition
+        penalty on one beam."""
+        num_beams = int(num_beams)
+        if num_beams < 1 or not float(repetition_penalty) > 0.0:
+            raise ValueError(f"num_beams={num_beams} / repetition_penalty={repetition_penalty}: at least one beam, a positive penalty")
+        if do_sample or stop_ids or text_stop is not None:
+            raise NotImplementedError("T5GreedyDecoder: sampling and stopping criteria are not implemented: use HF generate")
+        if num_beams == 1 and float(repetition_penalty) != 1.0:
+            raise NotImplementedError("repetition_penalty with one beam: use HF generate")
         B, P, _ = inputs_embeds.shape
         pmask = _padding(attention_mask, B, P)
         N = max_new_tokens
         dev, dt = inputs_embeds.device, inputs_embeds.dtype
+        K, beam = num_beams, None
+        rep = (lambda t: t.repeat_interleave(K, 0)) if K > 1 else (lambda t: t)      # (torch path of a beam state: K rows per batch item)
         eos_token_id, pad_token_id, min_new_tokens = self._special(eos_token_id, pad_token_id, min_new_tokens)
-        st = self._state(B, P, N, dev, dt, eos_token_id, pad_token_id, min_new_tokens, pmask is not None)
+        if K > 1:
+            if K > ops.BEAM_MAX_BEAMS or 2 * K > self.lm.lm_head.weight.shape[0]:
+                raise NotImplementedError(f"num_beams={K}: up to {ops.BEAM_MAX_BEAMS} beams, 2 x num_beams <= vocab_size")
+            # HF fills with ``pad_token_id or eos_token_id``: pad 0 fills with eos
+            beam = dict(K=K, fill=-1 if eos_token_id is None else int(pad_token_id if pad_token_id else eos_token_id),
+                        repetition_penalty=float(repetition_penalty), length_penalty=1.0 if length_penalty is None else float(length_penalty))
+        st = self._state(B, P, N, dev, dt, eos_token_id, beam["fill"] if beam else pad_token_id, min_new_tokens, pmask is not None, beam)
         valid = None if pmask is None else (pmask.to(dev) != 0)
-        if st["hip"]:
+        if st["hip"]:      # (a beam state too: the encoder and the ckv projections run once per batch item)
             if valid is not None:
                 st["ckv_valid"][:, :P].copy_(valid)
             enc = self._encode_hip(inputs_embeds, None if valid is None else valid.to(torch.uint8).contiguous())      # [B P, D]
@@ -1356,10 +1448,21 @@ class T5GreedyDecoder(_GraphDecoder):
             am = torch.ones(B, P, dtype=torch.long, device=dev) if valid is None else valid.long()
             enc = self.lm.encoder(inputs_embeds=inputs_embeds, attention_mask=am).last_hidden_state
             if valid is not None:
-                st["cmask"].copy_(torch.where(valid, 0.0, torch.finfo(dt).min).to(dt)[:, None, None, :])
+                st["cmask"].copy_(rep(torch.where(valid, 0.0, torch.finfo(dt).min).to(dt)[:, None, None, :]))
             for li, w in enumerate(self.layers):
-                st["ck"][li].copy_(F.linear(enc, w["ck"]).view(B, P, self.H, self.dk).transpose(1, 2))
-                st["cv"][li].copy_(F.linear(enc, w["cv"]).view(B, P, self.H, self.dk).transpose(1, 2))
+                st["ck"][li].copy_(rep(F.linear(enc, w["ck"]).view(B, P, self.H, self.dk).transpose(1, 2)))
+                st["cv"][li].copy_(rep(F.linear(enc, w["cv"]).view(B, P, self.H, self.dk).transpose(1, 2)))
+        if beam is not None:
+            self._beam_reset(st)
+            st["step"].zero_()
+            st["pos"].zero_()
+            st["tok"].fill_(self.start)
+            if st["attn"] == "beam":      # slot 0 holds the start token and is the row's own
+                st["src_row"].zero_()
+                st["src_row"][:, :1] = st["row_id"]
+            self._decode_step(st)         # the first step, eagerly: K identical rows, running scores [0, -1e9, ...]
+            out = self._replay_beams(st, use_graph)
+            return torch.cat([torch.full((B, 1), self.start, dtype=torch.long, device=dev), out], dim=1)
         self._reset(st, eos_token_id is not None, 0)
         st["tok"].fill_(self.start)                                                 # every one of the N tokens is a replayed step from the start token
         out = self._replay(st, 0, use_graph, eos_token_id is not None)
@@ -1424,6 +1527,7 @@ class Envelope(NamedTuple):
     sampling: bool
     need_max_new: bool
     beams: bool = False      # opt-in (beam_search="graph"): Llama, num_beams > 1 with any positive repetition_penalty and any length_penalty
+    t5_beams: bool = False   # opt-in (beam_search="graph+t5"): the same requests on a T5 as well
 
 
 _COMMON_KEYS = {"do_sample", "temperature", "top_p", "min_new_tokens", "eos_token_id", "pad_token_id", "num_beams", "repetition_penalty", "length_penalty"}
@@ -1440,14 +1544,20 @@ MODULE_ENVELOPE = Envelope(frozenset(_COMMON_KEYS | {"max_new_tokens", "use_cach
 # length as HF's ``max_length`` / ``min_length`` (``generated_length``), as the shipped generate_configs do
 GENERATE_ENVELOPE_BEAMS = GENERATE_ENVELOPE._replace(beams=True)
 MODULE_ENVELOPE_BEAMS = MODULE_ENVELOPE._replace(keys=MODULE_ENVELOPE.keys | {"max_length", "min_length"}, beams=True)
+# beam_search="graph+t5": their twins that let a T5's beam requests through as well
+GENERATE_ENVELOPE_T5_BEAMS = GENERATE_ENVELOPE_BEAMS._replace(t5_beams=True)
+MODULE_ENVELOPE_T5_BEAMS = MODULE_ENVELOPE_BEAMS._replace(t5_beams=True)
 
 
 def envelope_for(owner, module: bool) -> Envelope:
-    """The envelope a caller plans with: today's, or its beam twin when the owner opted in (attribute ``beam_search``, "hf" when it has none)."""
-    graph = check_beam_search(getattr(owner, "beam_search", "hf")) == "graph"
+    """The envelope a caller plans with: today's, or its beam twin when the owner opted in (attribute ``beam_search``, "hf" when it has none;
+    "graph+t5": the twin with ``t5_beams``)."""
+    mode = check_beam_search(getattr(owner, "beam_search", "hf"))
+    if mode == "graph+t5":
+        return MODULE_ENVELOPE_T5_BEAMS if module else GENERATE_ENVELOPE_T5_BEAMS
     if module:
-        return MODULE_ENVELOPE_BEAMS if graph else MODULE_ENVELOPE
-    return GENERATE_ENVELOPE_BEAMS if graph else GENERATE_ENVELOPE
+        return MODULE_ENVELOPE_BEAMS if mode == "graph" else MODULE_ENVELOPE
+    return GENERATE_ENVELOPE_BEAMS if mode == "graph" else GENERATE_ENVELOPE
 
 
 def generated_length(lm, request: dict, P: int) -> Optional[Tuple[int, Optional[int]]]:
@@ -1467,7 +1577,8 @@ def generated_length(lm, request: dict, P: int) -> Optional[Tuple[int, Optional[
 def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: Envelope) -> Optional[dict]:
     """The keyword arguments of ``decoder_for(owner, lm).generate(inputs_embeds, max_new_tokens, **plan)`` for a request HF ``generate`` would get
     as ``generate(inputs_embeds=..., attention_mask=..., **request)``, or None when it is outside what the graph decoders reproduce (then HF
-    ``generate`` runs it).  Inside: a Llama / T5 language model on the device, only keys ``env`` knows, one beam, neutral penalties, a 0 / 1
+    ``generate`` runs it).  Inside: a Llama / T5 language model on the device, only keys ``env`` knows, one beam, neutral penalties (or, where
+    ``env.beams`` -- for a T5 ``env.t5_beams`` -- says so, deterministic beam search with a positive repetition penalty), a 0 / 1
     attention mask with a token in every row (a padded mask goes into the plan as its host copy); greedy, or -- Llama, where ``env`` serves it --
     sampling with temperature / top_k / top_p; ``stopping_criteria`` None or (Llama) KeywordsStoppingCriteria objects (eval/utils/builder_utils.py:
     320-346: recognised by their ``keyword_ids`` / ``keywords`` / ``tokenizer`` attributes)."""
@@ -1482,10 +1593,10 @@ def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: E
     crit = list(request["stopping_criteria"]) if request.get("stopping_criteria") is not None else []
     K = request.get("num_beams", 1)
     beams = env.beams and isinstance(K, int) and not isinstance(K, bool) and K > 1
-    if beams:      # deterministic beam search on Llama; any positive repetition penalty, any length penalty
+    if beams:      # deterministic beam search on Llama (on T5: under ``env.t5_beams``); any positive repetition penalty, any length penalty
         rp, lp = request.get("repetition_penalty"), request.get("length_penalty")
         rp, lp = (1.0 if rp is None else rp), (1.0 if lp is None else lp)
-        if "llama" not in mt or do_sample or crit or not all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in (rp, lp)) or not rp > 0:
+        if not ("llama" in mt or (mt == "t5" and env.t5_beams)) or do_sample or crit or not all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in (rp, lp)) or not rp > 0:
             return None
     elif any(k in request and request[k] not in ok for k, ok in env.neutral.items()):
         return None
@@ -1515,7 +1626,7 @@ def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: E
 
 def graph_generate(owner, lm, inputs_embeds: Tensor, attention_mask: Tensor, generate_configs: dict):
     """``lm.generate(inputs_embeds=..., attention_mask=..., **generate_configs)`` through the graph decoder when the configuration is inside
-    the owner's module envelope (``envelope_for``: MODULE_ENVELOPE, or MODULE_ENVELOPE_BEAMS when its ``beam_search`` is "graph"), else None (the
+    the owner's module envelope (``envelope_for``: MODULE_ENVELOPE, or MODULE_ENVELOPE_BEAMS / MODULE_ENVELOPE_T5_BEAMS when its ``beam_search`` is "graph" / "graph+t5"), else None (the
     caller then runs HF generate).  The decoder is cached on ``owner``."""
     gc = dict(generate_configs or {})
     env = envelope_for(owner, module=True)

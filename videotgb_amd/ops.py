@@ -569,6 +569,30 @@ def beam_candidates(logits: Tensor, seq: Tensor, step: Tensor, running: Tensor, 
     return out
 
 
+# ---- beam search on the T5 decode step (opt-in: beam_search="graph+t5").  vtgb_llm_attention_rows_beam keeps its scores and the table rows of a
+# (row, head) in LDS: the largest t_pad (= decoder positions of a state) it is launched with, VTGB_LLM_ATTN_ROWS_BEAM_MAX_T of include/vtgb.h.
+ATTENTION_ROWS_BEAM_MAX_KEYS = 1920
+
+
+def attention_rows_beam(q: Tensor, kc: Tensor, vc: Tensor, src_row: Tensor, pos: Tensor, scale: float, bias: Optional[Tensor] = None,
+                        out: Optional[Tensor] = None) -> Tensor:
+    """The T5 decoder's self-attention of R beam rows through an ancestry table (vtgb_llm_attention_rows_beam): q [R, H*dk]; kc / vc
+    [R, H, N, dk], row r holding what beam row r appended; src_row [R, >= N] int32, the cache row that holds row r's key of slot t; keys
+    [0, *pos] (device int64) with the bias row *pos of ``bias`` [H, N, N] (None: no bias).  Equals vtgb_llm_attention_rows on the gathered
+    caches ``kc[src_row[r, t], :, t]`` bit for bit."""
+    _need_cuda(q, kc, vc, src_row, pos)
+    R, H, N, dk = kc.shape
+    assert q.shape == (R, H * dk) and vc.shape == kc.shape and q.dtype == kc.dtype == vc.dtype and all(t.is_contiguous() for t in (q, kc, vc))
+    assert src_row.dtype == torch.int32 and src_row.dim() == 2 and src_row.shape[0] == R and src_row.stride(1) == 1 and pos.dtype == torch.int64
+    assert bias is None or (bias.shape == (H, N, N) and bias.dtype == q.dtype and bias.is_contiguous())
+    if out is None:
+        out = torch.empty(R, H * dk, dtype=q.dtype, device=q.device)
+    a = L.LlmAttnRowsArgs(dtype_code(q.dtype), R, H, dk, 1, 0, N, float(scale), _ptr(q), H * dk, _ptr(kc), _ptr(vc), H * N * dk, N * dk, dk,
+                          _ptr(bias), N, N * N, _ptr(pos), _ptr(out), H * dk)
+    L.check(L.lib().vtgb_llm_attention_rows_beam(C.byref(a), _ptr(src_row), src_row.stride(0), R, _stream()))
+    return out
+
+
 def lora_update(x: Tensor, y: Tensor, segments) -> Tensor:
     """Unmerged LoRA adapters on a projection's output, in place (vtgb_llm_lora): for every ``(col0, A, B, scaling)`` of ``segments`` (1 .. 4,
     disjoint column ranges), ``y[:, col0 : col0 + n] += ((x.float() @ A.T) @ B.T * scaling).to(y.dtype)`` -- train.LoraLinear.forward in eval
