@@ -406,6 +406,21 @@ def decode_attention_workspace_bytes(B: int, nq: int, hd: int, tmax: int) -> int
     return int(L.lib().vtgb_llm_decode_attention_split_workspace_bytes(B, nq, hd, tmax))
 
 
+def _decode_attention_buffers(what: str, q: Tensor, rows: int, nq: int, hd: int, ws_tmax: Optional[int], key_valid: Optional[Tensor], valid_shape,
+                              out: Optional[Tensor], workspace: Optional[Tensor]) -> Tuple[Tensor, Optional[Tensor]]:
+    """What the decode-attention entries share: the form of ``key_valid`` [valid_shape] uint8, ``out`` [rows, nq*hd] and the split-KV
+    workspace for a cache of ``ws_tmax`` slots, both allocated here when None (``ws_tmax`` None: the one-wave kernel, no workspace)."""
+    assert key_valid is None or (key_valid.dtype == torch.uint8 and key_valid.shape == valid_shape and key_valid.is_contiguous())
+    if out is None:
+        out = torch.empty(rows, nq * hd, dtype=q.dtype, device=q.device)
+    if ws_tmax is not None:
+        need = decode_attention_workspace_bytes(rows, nq, hd, ws_tmax)
+        if workspace is None:
+            workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)
+        assert workspace.numel() * workspace.element_size() >= need, f"{what}: workspace too small"
+    return out, workspace
+
+
 def decode_attention(q: Tensor, kc: Tensor, vc: Tensor, pos: Tensor, scale: float, key_valid: Optional[Tensor] = None,
                      out: Optional[Tensor] = None, workspace: Optional[Tensor] = None, split: Optional[bool] = None) -> Tensor:
     """q [B, nq*hd], kc / vc [B, nkv, tmax, hd] (the static cache), pos: device int64 -> out [B, nq*hd] = softmax(scale q K[0..pos]^T) V[0..pos].
@@ -416,19 +431,14 @@ def decode_attention(q: Tensor, kc: Tensor, vc: Tensor, pos: Tensor, scale: floa
     B, nkv, tmax, hd = kc.shape
     nq = q.numel() // (B * hd)
     assert kc.is_contiguous() and vc.is_contiguous() and q.is_contiguous() and vc.shape == kc.shape and q.dtype == kc.dtype == vc.dtype
-    assert pos.dtype == torch.int64 and (key_valid is None or (key_valid.dtype == torch.uint8 and key_valid.shape == (B, tmax) and key_valid.is_contiguous()))
+    assert pos.dtype == torch.int64
     if split is None:
         route = decode_attention_route(tmax, hd)
         split = route == "split" if route is not None else tmax > DECODE_SINGLE_MAX_KEYS      # (neither: the entry that refuses it names the reason)
     code = dtype_code(q.dtype)
-    if out is None:
-        out = torch.empty(B, nq * hd, dtype=q.dtype, device=q.device)
+    out, workspace = _decode_attention_buffers("decode_attention", q, B, nq, hd, tmax if split else None, key_valid, (B, tmax), out, workspace)
     lib = L.lib()
     if split:
-        need = decode_attention_workspace_bytes(B, nq, hd, tmax)
-        if workspace is None:
-            workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)
-        assert workspace.numel() * workspace.element_size() >= need, "decode_attention: workspace too small"
         L.check(lib.vtgb_llm_decode_attention_split(code, _ptr(q), _ptr(kc), _ptr(vc), _ptr(out), _ptr(pos), _ptr(key_valid), _ptr(workspace), B, nq, nkv,
                                                     hd, tmax, float(scale), _stream()))
     elif key_valid is not None:
@@ -490,13 +500,7 @@ def decode_attention_fp8(q: Tensor, kc8: Tensor, vc8: Tensor, ks: Tensor, vs: Te
     assert kc8.element_size() == 1 and vc8.element_size() == 1 and kc8.is_contiguous() and vc8.is_contiguous() and vc8.shape == kc8.shape
     assert ks.dtype == vs.dtype == torch.float32 and ks.shape == vs.shape == (B, nkv, tmax) and ks.is_contiguous() and vs.is_contiguous()
     assert q.is_contiguous() and pos.dtype == torch.int64
-    assert key_valid is None or (key_valid.dtype == torch.uint8 and key_valid.shape == (B, tmax) and key_valid.is_contiguous())
-    if out is None:
-        out = torch.empty(B, nq * hd, dtype=q.dtype, device=q.device)
-    need = decode_attention_workspace_bytes(B, nq, hd, tmax)
-    if workspace is None:
-        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)
-    assert workspace.numel() * workspace.element_size() >= need, "decode_attention_fp8: workspace too small"
+    out, workspace = _decode_attention_buffers("decode_attention_fp8", q, B, nq, hd, tmax, key_valid, (B, tmax), out, workspace)
     L.check(L.lib().vtgb_llm_decode_attention_split_fp8(dtype_code(q.dtype), _ptr(q), _ptr(kc8), _ptr(vc8), _ptr(ks), _ptr(vs), _ptr(out), _ptr(pos),
                                                         _ptr(key_valid), _ptr(workspace), B, nq, nkv, hd, tmax, float(scale), _stream()))
     return out
@@ -527,13 +531,7 @@ def decode_attention_beam(q: Tensor, kp: Tensor, vp: Tensor, kg: Tensor, vg: Ten
     assert R % B == 0 and kg.shape == (R, nkv, tmax_g, hd) and vp.shape == kp.shape and vg.shape == kg.shape
     assert all(t.is_contiguous() for t in (q, kp, vp, kg, vg, src_row)) and q.dtype == kp.dtype == vp.dtype == kg.dtype == vg.dtype
     assert src_row.dtype == torch.int32 and src_row.shape == (R, tmax_g) and pos.dtype == torch.int64 and n_prompt.dtype == torch.int64
-    assert key_valid is None or (key_valid.dtype == torch.uint8 and key_valid.shape == (B, tmax_p) and key_valid.is_contiguous())
-    if out is None:
-        out = torch.empty(R, nq * hd, dtype=q.dtype, device=q.device)
-    need = decode_attention_workspace_bytes(R, nq, hd, tmax_p + tmax_g)
-    if workspace is None:
-        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)
-    assert workspace.numel() * workspace.element_size() >= need, "decode_attention_beam: workspace too small"
+    out, workspace = _decode_attention_buffers("decode_attention_beam", q, R, nq, hd, tmax_p + tmax_g, key_valid, (B, tmax_p), out, workspace)
     a = L.LlmDecodeAttentionBeamArgs(dtype_code(q.dtype), R, R // B, nq, nkv, hd, tmax_p, tmax_g, float(scale), _ptr(q), _ptr(kp), _ptr(vp), _ptr(kg),
                                      _ptr(vg), _ptr(src_row), _ptr(out), _ptr(n_prompt), _ptr(pos), _ptr(key_valid), _ptr(workspace))
     L.check(L.lib().vtgb_llm_decode_attention_beam(C.byref(a), _stream()))
