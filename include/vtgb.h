@@ -975,6 +975,18 @@ size_t vtgb_pack_skinny_weight_fp8_bytes(int32_t N, int32_t K);
 int vtgb_pack_skinny_weight_fp8(const void* w, int64_t ldw, int32_t N, int32_t K, void* dst, float* scale_out, vtgb_stream_t stream);
 int vtgb_gemm_skinny_fp8(const vtgb_gemm_skinny_args* a, const float* w_scale, vtgb_stream_t stream);
 
+/* Either weight stream with a projection bias (LlamaConfig.attention_bias / mlp_bias): out = x . w^T + bias[n], what `F.linear(h, weight, bias)`
+ * computes.  w_scale NULL: the bf16 stream, `a` read as vtgb_gemm_skinny reads it; w_scale given: the fp8 stream, as vtgb_gemm_skinny_fp8 reads it
+ * (w_tiled must be 1).  bias is fp32 [N], 4-byte aligned, never quantised; entries n >= N of the last 128-row tile are not read.  It is added in
+ * fp32 to the accumulators of K split 0 alone, after the fp8 row scale and before the fragment is written -- without a split, before the single
+ * rounding to `out` -- so fragment 0 holds acc0 + bias, the other fragments are those of the unbiased call, and every reader that adds the
+ * fragments in split order (the second launch, vtgb_llm_rmsnorm_parts, vtgb_llm_rope_cache_parts{,_pos}, vtgb_llm_rope_cache_fp8) rounds
+ * ((acc0 + bias) + acc1 + ...) once, unchanged.  n_splits, the workspace and defer_reduce are vtgb_gemm_skinny's.  Errors, before any launch:
+ * vtgb_gemm_skinny's for `a`; VTGB_EINVAL for a NULL x / w / out / bias and for w_scale with w_tiled != 1; VTGB_EUNSUPPORTED for a bias that
+ * is not 4-byte aligned. */
+int vtgb_gemm_skinny_bias(const vtgb_gemm_skinny_args* a, const float* w_scale /* NULL: bf16 stream */, const float* bias /* [N] fp32 */,
+                          vtgb_stream_t stream);
+
 /* ---- attention for the TRAINABLE stages (config C5, SF flavours): forward + backward, fp32 ---------------------------
  * Replaces, with its autograd, the matmul / softmax / dropout / matmul sequence of InstructBlipQFormerMultiHeadAttention.forward
  * (xinstructblip.py:611-694; BLIP-2 twin xblip2.py) and RopeBertSelfAttention.forward (xropebert.py:243-332; the rotary

@@ -35,7 +35,7 @@ EXPORTS = [
     "vtgb_llm_rope_cache_pos", "vtgb_llm_rope_cache_parts_pos", "vtgb_llm_rope_cache_prefill_pos", "vtgb_llm_decode_attention_masked",
     "vtgb_llm_attention_rows_masked",
     "vtgb_gemm_skinny_workspace_bytes", "vtgb_gemm_skinny", "vtgb_pack_skinny_weight_bytes", "vtgb_pack_skinny_weight",
-    "vtgb_pack_skinny_weight_fp8_bytes", "vtgb_pack_skinny_weight_fp8", "vtgb_gemm_skinny_fp8",
+    "vtgb_pack_skinny_weight_fp8_bytes", "vtgb_pack_skinny_weight_fp8", "vtgb_gemm_skinny_fp8", "vtgb_gemm_skinny_bias",
     "vtgb_raft_update_workspace_bytes", "vtgb_raft_update", "vtgb_raft_encoder_workspace_bytes", "vtgb_raft_encoder",
     "vtgb_raft_corr_workspace_bytes", "vtgb_raft_corr", "vtgb_preprocess_frames", "vtgb_concat_text_io", "vtgb_shifted_ce_forward", "vtgb_shifted_ce_backward",
     "vtgb_comm_unique_id", "vtgb_comm_init", "vtgb_comm_destroy", "vtgb_allreduce_f32",
@@ -374,6 +374,8 @@ def lib() -> C.CDLL:
     L.vtgb_pack_skinny_weight_fp8.restype = C.c_int
     L.vtgb_gemm_skinny_fp8.argtypes = [C.POINTER(GemmSkinnyArgs), vp, vp]
     L.vtgb_gemm_skinny_fp8.restype = C.c_int
+    L.vtgb_gemm_skinny_bias.argtypes = [C.POINTER(GemmSkinnyArgs), vp, vp, vp]
+    L.vtgb_gemm_skinny_bias.restype = C.c_int
     for fn in (L.vtgb_attn_train_forward, L.vtgb_attn_train_backward):
         fn.argtypes = [C.POINTER(AttnTrainArgs), vp]
         fn.restype = C.c_int

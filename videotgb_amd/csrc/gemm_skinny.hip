@@ -92,7 +92,7 @@ __device__ __forceinline__ bf16x8 sk8_widen(int lo, int hi) {
 // q ^ ((r >> 1) & 7)).  Load 2 i + h: fragment i, half h.
 struct SkinnyBf16 {
     static constexpr int D = 8, LOADS = 4;
-    static constexpr bool SCALED = false;
+    static constexpr bool SCALED = false, BIASED = false;
     static constexpr const char* ENTRY = "gemm_skinny";
     const bf16_t* w;
     int ldw, tiled;
@@ -114,7 +114,7 @@ struct SkinnyBf16 {
 // both 32-deep MFMAs of the k-tile (a wave reads 1 KiB contiguous per fragment).  Load i: fragment i.
 struct SkinnyFp8 {
     static constexpr int D = 16, LOADS = 2;
-    static constexpr bool SCALED = true;
+    static constexpr bool SCALED = true, BIASED = false;
     static constexpr const char* ENTRY = "gemm_skinny_fp8";
     const uint8_t* w;
     const float* scale;
@@ -123,6 +123,17 @@ struct SkinnyFp8 {
     __device__ int kstep() const { return SK8_TILE; }
     __device__ unsigned offset(int l, int row, int fg) const { return (unsigned)((row + l * 16) * 64 + fg * 16); }
     static __device__ __forceinline__ bf16x8 frag(const sk_i32x4 (&r)[LOADS], int i, int half) { return sk8_widen(r[i][2 * half], r[i][2 * half + 1]); }
+};
+
+// Either stream with a projection bias (vtgb_gemm_skinny_bias): bias[n] fp32 is added to the fp32 accumulators of split 0 alone, behind the row
+// scale and before the fragment leaves the registers, so whoever adds the fragments in split order -- the reduce launch, the deferred
+// consumers -- rounds acc + bias once and needs no change.  A stream type of its own: the kernels of the plain streams keep their
+// parameters and their code.
+template <typename Base>
+struct SkinnyBiased : Base {
+    static constexpr bool BIASED = true;
+    static constexpr const char* ENTRY = "gemm_skinny_bias";
+    const float* bias;
 };
 
 template <typename WS, int XB>
@@ -244,8 +255,21 @@ __global__ __launch_bounds__(SK_THREADS) void gemm_skinny_kernel(const bf16_t* _
 #undef SK_READ_X
 #undef SK_ISSUE_W
 #undef SK_WAIT_W
-    // D layout: column (lane & 15) <- x row (m), rows (lane >> 4) * 4 + reg <- w row (n); a scaled stream's row scales first (rows beyond N: 1)
+    // D layout: column (lane & 15) <- x row (m), rows (lane >> 4) * 4 + reg <- w row (n); a scaled stream's row scales first (rows beyond N: 1),
+    // then split 0's bias (rows beyond N: 0, never read)
     f32x4 sc[2] = {};
+    f32x4 bi[2] = {};
+    if constexpr (WS::BIASED) {
+        if (sp == 0) {
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    const int n = b * SK_BN + wave * 32 + i * 16 + fg * 4 + e;
+                    bi[i][e] = n < N ? ws.bias[n] : 0.f;
+                }
+        }
+    }
     if constexpr (WS::SCALED) {
 #pragma unroll
         for (int i = 0; i < 2; i++)
@@ -264,6 +288,7 @@ __global__ __launch_bounds__(SK_THREADS) void gemm_skinny_kernel(const bf16_t* _
             const int c = wave * 32 + i * 16 + fg * 4, n = b * SK_BN + c;
             f32x4 v = acc[i][j];
             if constexpr (WS::SCALED) v *= sc[i];
+            if constexpr (WS::BIASED) v += bi[i];
             if (S > 1) {
                 *reinterpret_cast<f32x4*>(part + ((int64_t)(b * S + sp) * M + m) * SK_BN + c) = v;
             } else if (n < N) {                                // no K split: round once and store straight to `out`
@@ -452,7 +477,7 @@ static int skinny_run(const vtgb_gemm_skinny_args* a, const WS& ws, vtgb_stream_
     const int S = skinny_splits(a);
     const size_t need = skinny_part_bytes(a, S);
     VTGB_REQUIRE(need == 0 || (a->workspace && a->workspace_bytes >= need), VTGB_EWORKSPACE, "%s: workspace %zu < %zu bytes", WS::ENTRY, a->workspace_bytes, need);
-    if constexpr (std::is_same<WS, SkinnyBf16>::value) {
+    if constexpr (!WS::SCALED) {
         // bf16 always runs all 8 x row blocks: specialising it on XB as fp8 does would change what the default mode launches at small batch
         VTGB_TRY((skinny_launch<WS, 8>(a, ws, S, s)));
     } else {
@@ -484,4 +509,13 @@ extern "C" int vtgb_gemm_skinny_fp8(const vtgb_gemm_skinny_args* a, const float*
     VTGB_REQUIRE(a->x && a->w && a->out && w_scale, VTGB_EINVAL, "gemm_skinny_fp8: NULL operand");
     VTGB_REQUIRE(a->w_tiled == 1, VTGB_EINVAL, "gemm_skinny_fp8: the weights are a vtgb_pack_skinny_weight_fp8 stream (w_tiled = 1)");
     return skinny_run(a, SkinnyFp8{(const uint8_t*)a->w, w_scale}, s);
+}
+
+extern "C" int vtgb_gemm_skinny_bias(const vtgb_gemm_skinny_args* a, const float* w_scale, const float* bias, vtgb_stream_t s) {
+    VTGB_TRY(skinny_check(a));
+    VTGB_REQUIRE(a->x && a->w && a->out && bias, VTGB_EINVAL, "gemm_skinny_bias: NULL operand");
+    VTGB_REQUIRE((reinterpret_cast<uintptr_t>(bias) & 3) == 0, VTGB_EUNSUPPORTED, "gemm_skinny_bias: bias %p is not 4-byte aligned", (const void*)bias);
+    if (!w_scale) return skinny_run(a, SkinnyBiased<SkinnyBf16>{{(const bf16_t*)a->w, (int)a->ldw, a->w_tiled}, bias}, s);
+    VTGB_REQUIRE(a->w_tiled == 1, VTGB_EINVAL, "gemm_skinny_bias: fp8 weights are a vtgb_pack_skinny_weight_fp8 stream (w_tiled = 1)");
+    return skinny_run(a, SkinnyBiased<SkinnyFp8>{{(const uint8_t*)a->w, w_scale}, bias}, s);
 }

@@ -149,6 +149,63 @@ def _lora_servable(lm) -> bool:
     return state == "ok"
 
 
+ROPE_TYPES = ("default", "linear", "llama3", "yarn")      # rotary tables that depend on the position alone
+
+
+def _rope_type(lm) -> str:
+    """The rope type of a Llama: the rotary module's own, else the configuration's (``rope_parameters``; ``rope_scaling`` with its older
+    ``type`` key), else "default"."""
+    cfg = getattr(lm, "config", None)
+    rot = getattr(getattr(lm, "model", None), "rotary_emb", None)
+    rp = getattr(cfg, "rope_parameters", None) or getattr(cfg, "rope_scaling", None) or {}
+    t = getattr(rot, "rope_type", None) or (rp.get("rope_type") or rp.get("type") if isinstance(rp, dict) else None)
+    return str(t or "default")
+
+
+def llama_state(lm) -> Optional[str]:
+    """None: ``GreedyDecoder`` states this Llama -- plain or position-only scaled rotary embedding (``ROPE_TYPES``, tables built from the model's own
+    ``rotary_emb.inv_freq`` and ``attention_scaling``), with or without projection biases (``attention_bias`` / ``mlp_bias``).  Any string: what
+    the layer statement does not compute -- the decoder raises NotImplementedError with it and ``plan_decode`` hands the request to HF generate.
+    An attribute a stand-in object lacks counts as a default Llama's.  Never "decoded as a plain Llama"."""
+    cfg = getattr(lm, "config", None)
+    mt = getattr(cfg, "model_type", "")
+    if mt != "llama":
+        return f"model_type {mt!r}: the layer statement is LlamaForCausalLM's"
+    rt = _rope_type(lm)
+    if rt not in ROPE_TYPES:
+        return f"rope_type {rt!r}: rotary tables that depend on the running sequence length, or unknown ones, are not built (served: {ROPE_TYPES})"
+    rot = getattr(getattr(lm, "model", None), "rotary_emb", None)
+    if rt != "default":
+        inv = getattr(rot, "inv_freq", None)
+        if not isinstance(inv, Tensor):
+            return f"rope_type {rt!r} on a model without rotary_emb.inv_freq to build the tables from"
+        nh = getattr(cfg, "num_attention_heads", None)
+        hd = getattr(cfg, "head_dim", None) or (cfg.hidden_size // nh if nh else None)
+        if hd is not None and inv.numel() * 2 != hd:
+            return f"rotary_emb.inv_freq of {inv.numel()} frequencies for head_dim {hd} (partial rotary embedding)"
+    act = getattr(cfg, "hidden_act", "silu")
+    if act not in ("silu", "swish"):
+        return f"hidden_act {act!r}: the MLP statement is SwiGLU"
+    if getattr(getattr(lm, "lm_head", None), "bias", None) is not None:
+        return "an lm_head with a bias"
+    layers = getattr(getattr(lm, "model", None), "layers", None) or ()
+    for li, l in enumerate(layers):      # anything but the norm -> attention -> norm -> MLP layer of modeling_llama
+        a, m = getattr(l, "self_attn", None), getattr(l, "mlp", None)
+        missing = [p for p in ("q_proj", "k_proj", "v_proj", "o_proj") if not hasattr(a, p)] + [p for p in ("gate_proj", "up_proj", "down_proj") if not hasattr(m, p)]
+        if missing:
+            return f"layer {li} without {missing[0]}"
+        for n in ("q_norm", "k_norm"):
+            if hasattr(a, n):
+                return f"layer {li}: self_attn.{n}"
+    return None
+
+
+def _llama_servable(lm):
+    state = llama_state(lm)
+    if state is not None:
+        raise NotImplementedError(f"a Llama outside the graph decoder's statement -- {state}; use HF generate")
+
+
 def prefill_chunks(P: int, chunk: int):
     """The chunked prefill's plan: [(q0, n), ...] -- consecutive row ranges [q0, q0 + n) covering 0 .. P-1, every n == chunk but the last."""
     if P <= 0 or chunk <= 0:
@@ -474,12 +531,18 @@ class GreedyDecoder(_GraphDecoder):
     through ``ops.fp8_kv_round``.  On the device, fused, with a cache the split-KV kernel takes (head_dim 64 / 128, up to 16384 slots) the state
     holds the codes and scales (half the bytes: ``st["attn"] == "split_fp8"``, vtgb_llm_rope_cache{,_prefill}_fp8 +
     vtgb_llm_decode_attention_split_fp8); otherwise it keeps bf16 caches of dequantised values and decodes on the torch step (``_layer`` states
-    the model; no memory is saved).  The fused path takes a bf16 model; the torch path also an fp32 one."""
+    the model; no memory is saved).  The fused path takes a bf16 model; the torch path also an fp32 one.
+
+    Which Llama: ``llama_state`` -- rope types default / linear / llama3 / yarn (scaled types: tables from the model's own rotary module,
+    ``_rope``), with or without projection biases (``self.bias``: fp32, never quantised; the decode step adds them in the skinny GEMM's
+    epilogue -- ops.gemm_skinny(bias=), vtgb_gemm_skinny_bias --, prefill and large batches through vtgb_gemm's bias, ``_layer`` through
+    F.linear).  Anything else raises NotImplementedError with the reason."""
 
     def __init__(self, lm, fused: bool = True, weights: str = "bf16", kv_cache: str = "bf16"):
         cfg = lm.config
         if "llama" not in cfg.model_type:
             raise NotImplementedError("GreedyDecoder handles Llama-architecture models; use HF generate otherwise")
+        _llama_servable(lm)
         has_lora = _lora_servable(lm)
         super().__init__(lm, fused, weights, kv_cache)
         wdt = lm.lm_head.weight.dtype
@@ -497,14 +560,32 @@ class GreedyDecoder(_GraphDecoder):
         self.eps = cfg.rms_norm_eps
         rp = getattr(cfg, "rope_parameters", None) or {}
         self.theta = float(rp.get("rope_theta", getattr(cfg, "rope_theta", 10000.0)))
+        # a scaled rotary embedding (linear, llama3, yarn): the model's own frequencies and cos / sin factor, from which ``_rope`` builds the
+        # tables as LlamaRotaryEmbedding.forward does; None: the default type, today's formula over ``theta``
+        self.rope_scaled = None
+        if _rope_type(lm) != "default":
+            rot = lm.model.rotary_emb
+            self.rope_scaled = (rot.inv_freq.detach().float().clone(), float(getattr(rot, "attention_scaling", 1.0)))
         # fused projection weights (one GEMM for q|k|v, one for gate|up): fewer, larger launches per token
         self.layers = []
+        biases = []
+
+        def cat_bias(*mods):      # fp32 [sum of the outputs] (widening is exact; never quantised), or None when none of them has a bias
+            bs = [getattr(m, "bias", None) for m in mods]
+            if all(b is None for b in bs):
+                return None
+            return torch.cat([m.weight.new_zeros(m.weight.shape[0], dtype=torch.float32) if b is None else b.detach().float()
+                              for m, b in zip(mods, bs)]).contiguous()
         for l in lm.model.layers:
             a, m = l.self_attn, l.mlp
             wqkv = torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], dim=0).contiguous()
             wgu = torch.cat([m.gate_proj.weight, m.up_proj.weight], dim=0).contiguous()
             self.layers.append((l.input_layernorm.weight, prep(wqkv), prep(a.o_proj.weight), l.post_attention_layernorm.weight, prep(wgu),
                                 prep(m.down_proj.weight)))
+            biases.append((cat_bias(a.q_proj, a.k_proj, a.v_proj), cat_bias(a.o_proj), cat_bias(m.gate_proj, m.up_proj), cat_bias(m.down_proj)))
+        # per layer the fp32 biases of (q|k|v, o, gate|up, down), None where a projection has none; None: a model without biases, for which
+        # nothing is allocated and every path launches what it launched before
+        self.bias = biases if any(b is not None for t in biases for b in t) else None
         self.head_w = prep(lm.lm_head.weight)
         self.inter = cfg.intermediate_size
         # LoRA adapters (train.LoraLinear on q / k / v), UNMERGED: per layer the (col0, A, B, scaling) segments of the fused q|k|v output that
@@ -535,27 +616,40 @@ class GreedyDecoder(_GraphDecoder):
     def _lora_of(self, li: int):
         return self.lora[li] if self.lora is not None else ()
 
+    def _bias_of(self, li: int):
+        """The layer's fp32 biases of (q|k|v, o, gate|up, down), None where there is none."""
+        return self.bias[li] if self.bias is not None else (None, None, None, None)
+
     def _use_skinny(self, B: int, dtype) -> bool:
         H, I = self.cfg.hidden_size, self.inter
         return self.fused and dtype == torch.bfloat16 and B <= self.SKINNY_MAX_BATCH and H % 64 == 0 and I % 64 == 0 and (self.nh * self.hd) % 64 == 0
 
     def _rope(self, tmax: int, device, dtype):
+        """cos / sin [tmax, hd] of rotary rows 0 .. tmax-1, operands of every consumer (append, prefill, beam tables).  A scaled type: the
+        model's frequencies and factor, as LlamaRotaryEmbedding.forward -- (emb.cos() * attention_scaling).to(dtype)."""
+        if self.rope_scaled is not None:
+            inv, factor = self.rope_scaled
+            fr = torch.arange(tmax, device=device, dtype=torch.float32)[:, None] * inv.to(device)[None]
+            emb = torch.cat((fr, fr), dim=-1)
+            return (emb.cos() * factor).to(dtype), (emb.sin() * factor).to(dtype)
         inv = 1.0 / (self.theta ** (torch.arange(0, self.hd, 2, device=device, dtype=torch.float32) / self.hd))
         fr = torch.arange(tmax, device=device, dtype=torch.float32)[:, None] * inv[None]
         emb = torch.cat((fr, fr), dim=-1)
         return emb.cos().to(dtype), emb.sin().to(dtype)
 
-    def _layer(self, x, w, cos, sin, kc, vc, pos_idx, mask, codes=None, lora=()):
+    def _layer(self, x, w, cos, sin, kc, vc, pos_idx, mask, codes=None, lora=(), bias=(None, None, None, None)):
         """x [B, S, H]; cos/sin [S, hd] (padded batches: [B, 1, S, hd], per-row positions); kc/vc [B, nkv, Tmax, hd]; pos_idx [S] cache rows
         to write; mask additive, broadcast to [B, 1, S, Tmax].  kv_cache="fp8": k and v pass through dq(q(.)) before the cache write and
         the attention -- the kernel-independent statement of the model.  ``codes`` = (kc8, vc8, ks, vs) of an fp8 state (prefill only,
         pos_idx = 0 .. S-1; kc / vc None): codes and scales go to the cache and the attention runs over the prompt's own dequantised K/V.
-        ``lora``: the layer's adapter segments (``self.lora[li]``), added to q|k|v as train.LoraLinear.forward adds them."""
+        ``lora``: the layer's adapter segments (``self.lora[li]``), added to q|k|v as train.LoraLinear.forward adds them -- behind the base
+        projection's bias.  ``bias``: the layer's biases (``_bias_of``), F.linear's in the model's dtype."""
         ln1, wqkv, wo, ln2, wgu, wd = w
+        bqkv, bo, bgu, bd = (None if b is None else b.to(x.dtype) for b in bias)
         B, S, _ = x.shape
         nq, nkv, hd = self.nh, self.nkv, self.hd
         h = _rms(x, ln1, self.eps)
-        qkv = F.linear(h, wqkv)
+        qkv = F.linear(h, wqkv, bqkv)
         for c0, la, lb, scaling in lora:      # result + (lora_B(lora_A(x.float())) * scaling).to(result.dtype), per adapted projection
             n = lb.shape[0]
             qkv = torch.cat((qkv[..., :c0], qkv[..., c0: c0 + n] + (F.linear(F.linear(h.to(la.dtype), la), lb) * scaling).to(qkv.dtype),
@@ -583,10 +677,10 @@ class GreedyDecoder(_GraphDecoder):
             rep = nq // nkv
             kk, vv = kk.repeat_interleave(rep, 1), vv.repeat_interleave(rep, 1)
         a = F.scaled_dot_product_attention(q, kk, vv, attn_mask=mask)
-        x = x + F.linear(a.transpose(1, 2).reshape(B, S, nq * hd), wo)
+        x = x + F.linear(a.transpose(1, 2).reshape(B, S, nq * hd), wo, bo)
         h = _rms(x, ln2, self.eps)
-        gu = F.linear(h, wgu)
-        return x + F.linear(F.silu(gu[..., : self.inter]) * gu[..., self.inter:], wd)
+        gu = F.linear(h, wgu, bgu)
+        return x + F.linear(F.silu(gu[..., : self.inter]) * gu[..., self.inter:], wd, bd)
 
     # Prefill on libvtgb.so: the four projections of a layer through vtgb_gemm (bf16: the persistent MFMA kernel, M = B*P rows; fp32:
     # the FMA kernel), the causal attention through ops.attention (bf16: vtgb_attention with the whole K/V of a head in LDS up to 288
@@ -629,8 +723,9 @@ class GreedyDecoder(_GraphDecoder):
         act = torch.empty(M, self.inter, dtype=x.dtype, device=x.device)
         delta = None
         for li, (ln1, wqkv, wo, ln2, wgu, wd) in enumerate(self.layers):
+            bqkv, bo, bgu, bd = self._bias_of(li)
             L.check(lib.vtgb_llm_rmsnorm(code, _ptr(x), _ptr(delta), _ptr(ln1), _ptr(h), M, H, self.eps, stream))
-            qkv = ops.gemm(h, wqkv)
+            qkv = ops.gemm(h, wqkv, bias=bqkv)
             if self.lora is not None and self.lora[li]:      # the adapters act on q|k|v before rotary and before K/V are quantised, as in the model
                 ops.lora_update(h, qkv, self.lora[li])
             qkv = qkv.view(B, P, nh + 2 * nkv, hd)
@@ -652,11 +747,11 @@ class GreedyDecoder(_GraphDecoder):
                 k_ = k_.reshape(B, P, nkv, 1, hd).expand(B, P, nkv, rep, hd).reshape(B, P, nh * hd)
                 v_ = v_.reshape(B, P, nkv, 1, hd).expand(B, P, nkv, rep, hd).reshape(B, P, nh * hd)
             a = ops.attention(q_, k_, v_, nh, float(hd) ** -0.5, key_mask=key_mask, causal=True, kv_heads=nkv if x.dtype == torch.bfloat16 else None)
-            o = ops.gemm(a.view(M, nh * hd), wo)
+            o = ops.gemm(a.view(M, nh * hd), wo, bias=bo)
             L.check(lib.vtgb_llm_rmsnorm(code, _ptr(x), _ptr(o), _ptr(ln2), _ptr(h), M, H, self.eps, stream))
-            gu = ops.gemm(h, wgu)
+            gu = ops.gemm(h, wgu, bias=bgu)
             L.check(lib.vtgb_llm_silu_mul(code, _ptr(gu), _ptr(act), M, self.inter, stream))
-            delta = ops.gemm(act, wd)
+            delta = ops.gemm(act, wd, bias=bd)
         return x.view(B, P, H)[:, -1] + delta.view(B, P, H)[:, -1]
 
     # Chunked prefill: a bf16 prompt past PREFILL_MAX_TOKENS goes through the layer stack in chunks of at most PREFILL_CHUNK_TOKENS rows, one
@@ -701,8 +796,9 @@ class GreedyDecoder(_GraphDecoder):
             cos, sin = (st["cos"], st["sin"]) if pid is not None else (st["cos"][q0:], st["sin"][q0:])
             delta = None
             for li, (ln1, wqkv, wo, ln2, wgu, wd) in enumerate(self.layers):
+                bqkv, bo, bgu, bd = self._bias_of(li)
                 L.check(lib.vtgb_llm_rmsnorm(code, _ptr(xc), _ptr(delta), _ptr(ln1), _ptr(h), M, H, self.eps, stream))
-                qkv = ops.gemm(h, wqkv)
+                qkv = ops.gemm(h, wqkv, bias=bqkv)
                 if self.lora is not None and self.lora[li]:
                     ops.lora_update(h, qkv, self.lora[li])
                 qkv = qkv.view(B, n, (nh + 2 * nkv) * hd)
@@ -718,11 +814,11 @@ class GreedyDecoder(_GraphDecoder):
                     else:
                         L.check(lib.vtgb_llm_rope_cache_prefill_pos(code, *cache, _ptr(pid), B, n, nh, nkv, hd, tmax, stream))
                 a = ops.attention_cached(qkv[:, :, : nh * hd], kc, vc, q0, nh, scale, key_valid=key_valid, scales=sc)
-                o = ops.gemm(a.view(M, nh * hd), wo)
+                o = ops.gemm(a.view(M, nh * hd), wo, bias=bo)
                 L.check(lib.vtgb_llm_rmsnorm(code, _ptr(xc), _ptr(o), _ptr(ln2), _ptr(h), M, H, self.eps, stream))
-                gu = ops.gemm(h, wgu)
+                gu = ops.gemm(h, wgu, bias=bgu)
                 L.check(lib.vtgb_llm_silu_mul(code, _ptr(gu), _ptr(act), M, self.inter, stream))
-                delta = ops.gemm(act, wd)
+                delta = ops.gemm(act, wd, bias=bd)
             last = xc.view(B, n, H)[:, -1] + delta.view(B, n, H)[:, -1]
         return last
 
@@ -811,13 +907,14 @@ class GreedyDecoder(_GraphDecoder):
             sw, ws = self._skinny_weights(), st["sk_ws"]
 
             def lin(xin, li, which, buf):      # which: 0 qkv, 1 o, 2 gate|up, 3 down
-                return ops.gemm_skinny(xin, sw[li][which], out=st[buf], workspace=ws)
+                return ops.gemm_skinny(xin, sw[li][which], out=st[buf], workspace=ws, bias=self._bias_of(li)[which])
         elif self._gemm_ok(x.dtype):
             def lin(xin, li, which, buf):      # fp32 (exactness mode) and batches beyond the skinny kernel: libvtgb.so's own GEMM, no BLAS
-                return ops.gemm(xin, self.layers[li][(1, 2, 4, 5)[which]])
+                return ops.gemm(xin, self.layers[li][(1, 2, 4, 5)[which]], bias=self._bias_of(li)[which])
         else:
             def lin(xin, li, which, buf):
-                return F.linear(xin, self.layers[li][(1, 2, 4, 5)[which]])
+                b_ = self._bias_of(li)[which]
+                return F.linear(xin, self.layers[li][(1, 2, 4, 5)[which]], None if b_ is None else b_.to(xin.dtype))
         # skinny path (bf16, batch <= 128): the split-K projections (qkv, o, down) leave their fp32 fragments in the workspace and the kernel that
         # consumes them (rotary + cache / RMSNorm + residual) adds them itself: 10 launches per layer instead of 13, the same values bit for bit
         defer = skinny and H in (2048, 4096)
@@ -825,7 +922,7 @@ class GreedyDecoder(_GraphDecoder):
         def lin_d(xin, li, which, buf):        # -> (tensor, n_splits): n_splits > 1 means "fragments in ws, tensor not written"
             if not defer:
                 return lin(xin, li, which, buf), 1
-            o_, S_, _ = ops.gemm_skinny(xin, sw[li][which], out=st[buf], workspace=ws, defer_reduce=True)
+            o_, S_, _ = ops.gemm_skinny(xin, sw[li][which], out=st[buf], workspace=ws, defer_reduce=True, bias=self._bias_of(li)[which])
             return o_, S_
 
         def norm(delta_t, delta_S, wt):
@@ -894,7 +991,7 @@ class GreedyDecoder(_GraphDecoder):
             cos, sin = st["cos"].index_select(0, pos), st["sin"].index_select(0, pos)
             mask = torch.where(st["ar"][None, None, None, :] <= pos, 0.0, neg).to(x.dtype)
         for li, w in enumerate(self.layers):
-            x = self._layer(x, w, cos, sin, st["kc"][li], st["vc"][li], pos, mask, lora=self._lora_of(li))
+            x = self._layer(x, w, cos, sin, st["kc"][li], st["vc"][li], pos, mask, lora=self._lora_of(li), bias=self._bias_of(li))
         (self._beam_emit if "beam" in st else self._emit)(st, self._head(x[:, -1]))
 
     # ---- beam search (opt-in at the interfaces: beam_search="graph").  R = B * K rows run the decode step.  On the device (fused) the state keeps
@@ -1040,12 +1137,12 @@ class GreedyDecoder(_GraphDecoder):
             cos, sin, causal = torch_operands()
             for li, w in enumerate(self.layers):
                 x = self._layer(x, w, cos, sin, None, None, pidx, causal, codes=(st["kc8"][li], st["vc8"][li], st["ks"][li], st["vs"][li]),
-                                lora=self._lora_of(li))
+                                lora=self._lora_of(li), bias=self._bias_of(li))
             last = x[:, -1]
         else:
             cos, sin, causal = torch_operands()
             for li, w in enumerate(self.layers):
-                x = self._layer(x, w, cos, sin, st["kc"][li], st["vc"][li], pidx, causal, lora=self._lora_of(li))
+                x = self._layer(x, w, cos, sin, st["kc"][li], st["vc"][li], pidx, causal, lora=self._lora_of(li), bias=self._bias_of(li))
             last = x[:, -1]
         return last
 
@@ -1577,7 +1674,8 @@ def generated_length(lm, request: dict, P: int) -> Optional[Tuple[int, Optional[
 def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: Envelope) -> Optional[dict]:
     """The keyword arguments of ``decoder_for(owner, lm).generate(inputs_embeds, max_new_tokens, **plan)`` for a request HF ``generate`` would get
     as ``generate(inputs_embeds=..., attention_mask=..., **request)``, or None when it is outside what the graph decoders reproduce (then HF
-    ``generate`` runs it).  Inside: a Llama / T5 language model on the device, only keys ``env`` knows, one beam, neutral penalties (or, where
+    ``generate`` runs it).  Inside: a Llama the decoder states (``llama_state``) or a T5 language model on the device, at most one distinct eos
+    id, only keys ``env`` knows, one beam, neutral penalties (or, where
     ``env.beams`` -- for a T5 ``env.t5_beams`` -- says so, deterministic beam search with a positive repetition penalty), a 0 / 1
     attention mask with a token in every row (a padded mask goes into the plan as its host copy); greedy, or -- Llama, where ``env`` serves it --
     sampling with temperature / top_k / top_p; ``stopping_criteria`` None or (Llama) KeywordsStoppingCriteria objects (eval/utils/builder_utils.py:
@@ -1588,6 +1686,8 @@ def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: E
     if set(request) - env.keys or (env.need_max_new and "max_new_tokens" not in request and not (env.beams and request.get("max_length") is not None)):
         return None
     if lora_state(lm) not in (None, "ok"):      # adapters the decoders do not apply: HF generate runs the modules' own forward
+        return None
+    if "llama" in mt and llama_state(lm) is not None:      # a Llama the decoder does not state (rope type, lm_head bias, ...): HF generate
         return None
     do_sample = bool(request.get("do_sample", False))
     crit = list(request["stopping_criteria"]) if request.get("stopping_criteria") is not None else []
@@ -1608,7 +1708,12 @@ def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: E
     if padded is None:
         return None
     gc = getattr(lm, "generation_config", None)     # HF generate's defaults come from the generation config
-    plan = dict(eos_token_id=request.get("eos_token_id", getattr(gc, "eos_token_id", None)),
+    eos = request.get("eos_token_id", getattr(gc, "eos_token_id", None))
+    if isinstance(eos, (list, tuple)) and len(set(eos)) > 1:      # several distinct eos ids (Llama-3.1-Instruct ships three): HF generate
+        return None
+    if isinstance(eos, (list, tuple)) and len(eos) > 1:      # (one id, repeated)
+        eos = [eos[0]]
+    plan = dict(eos_token_id=eos,
                 pad_token_id=request.get("pad_token_id", getattr(gc, "pad_token_id", None)), min_new_tokens=int(request.get("min_new_tokens", 0) or 0))
     if padded:
         plan["attention_mask"] = host_mask      # (the host copy: the decoder classifies it again without reading the device)

@@ -265,12 +265,14 @@ def gemm_skinny_workspace_bytes(M: int, N: int, K: int, n_splits: int = 0) -> in
 
 
 def gemm_skinny(x: Tensor, w: Tensor, out: Optional[Tensor] = None, n_splits: int = 0, out_dtype: Optional[torch.dtype] = None,
-                workspace: Optional[Tensor] = None, defer_reduce: bool = False):
+                workspace: Optional[Tensor] = None, defer_reduce: bool = False, bias: Optional[Tensor] = None):
     """``defer_reduce``: returns (out, n_splits, workspace) and leaves the K-split fragments to the consumer (see below).
     x [M <= 128, K] bf16, w [N, K] bf16 (nn.Linear.weight, or its SkinnyWeight) -> x @ w.T [M, N]: the decode step's projections (vtgb_gemm_skinny:
     the weights stream once, K split over workgroups, fp32 partials added in a fixed order).  A ``SkinnyWeightFp8`` streams e4m3 codes instead
     (vtgb_gemm_skinny_fp8): the result is that of the bf16 weights ``dequantize_fp8_rows(*quantize_fp8_rows(w))``, bit for bit.  ``out`` may be a preallocated
-    [M, N] tensor and ``workspace`` a preallocated uint8 scratch (hipGraph capture: fixed addresses, no allocation)."""
+    [M, N] tensor and ``workspace`` a preallocated uint8 scratch (hipGraph capture: fixed addresses, no allocation).  ``bias`` [N] fp32 (a projection
+    bias; never quantised): x @ w.T + bias through vtgb_gemm_skinny_bias, either stream -- added in fp32 to K split 0, so the fragments a
+    ``defer_reduce`` call leaves already hold it; None takes the entries above, unchanged."""
     fp8 = isinstance(w, SkinnyWeightFp8)
     tiled = fp8 or isinstance(w, SkinnyWeight)
     _need_cuda(x, w.data if tiled else w)
@@ -286,7 +288,11 @@ def gemm_skinny(x: Tensor, w: Tensor, out: Optional[Tensor] = None, n_splits: in
     if need:
         ws = workspace if workspace is not None else _ws.get(need, x.device)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-    if fp8:
+    if bias is not None:
+        _need_cuda(bias)
+        assert bias.dtype == torch.float32 and tuple(bias.shape) == (N,) and bias.stride(0) == 1
+        L.check(L.lib().vtgb_gemm_skinny_bias(C.byref(a), w.scale.data_ptr() if fp8 else None, bias.data_ptr(), _stream()))
+    elif fp8:
         L.check(L.lib().vtgb_gemm_skinny_fp8(C.byref(a), w.scale.data_ptr(), _stream()))
     else:
         L.check(L.lib().vtgb_gemm_skinny(C.byref(a), _stream()))
