@@ -987,6 +987,25 @@ int vtgb_gemm_skinny_fp8(const vtgb_gemm_skinny_args* a, const float* w_scale, v
 int vtgb_gemm_skinny_bias(const vtgb_gemm_skinny_args* a, const float* w_scale /* NULL: bf16 stream */, const float* bias /* [N] fp32 */,
                           vtgb_stream_t stream);
 
+/* The same weight stream in MXFP4 (opt-in: decode_weights = "mxfp4"; OCP Microscaling v1.0).  Along K every block of 32 consecutive weights of a
+ * row shares one E8M0 scale 2^e: e = floor(log2(amax of the block)) - 2 (0 for an all-zero block), clamped to [-120, 125], stored as the byte
+ * e + 127.  An element is w * 2^-e rounded to the nearest e2m1 number (sign; magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6 = codes 0 .. 7), ties to the
+ * even code, saturating at 6; the sign bit is the weight's own.  code * 2^e is exactly a normal bf16 number, so the entries below compute what
+ * vtgb_gemm_skinny computes from the bf16 matrix dq = code * 2^e, bit for bit (the definition, on the host: ops.quantize_mxfp4_rows):
+ *   vtgb_pack_skinny_weight_mxfp4: quantises a bf16 [N, K] matrix into the kernel's stream -- per (128-row tile, 64-deep k-tile) one block of
+ *     4096 + 256 bytes.  Codes: 16 bytes per (wave v = row / 32, f = row % 16, 8-deep k chunk g = 0 .. 3) at ((v * 16 + f) * 4 + g) * 16, four
+ *     dwords [fragment i = (row / 16) % 2][32-deep half h], each the 8 codes of row v * 32 + i * 16 + f at k = 32 h + 8 g .. + 7, two per byte,
+ *     the lower k in the low nibble.  Scales: 4 bytes per (v, f) at 4096 + (v * 16 + f) * 4, byte 2 i + h = the E8M0 byte of that row's block h.
+ *     Rows beyond N are zero codes under the byte 127.  17 / 32 of the bytes of vtgb_pack_skinny_weight_fp8's form.
+ *   vtgb_gemm_skinny_mxfp4: out = x . dq^T (+ bias[n]); the codes are widened to bf16 under their block scale in registers.  `w` is the packed
+ *     stream, w_tiled must be 1 and ldw is ignored.  bias NULL, or fp32 [N] as vtgb_gemm_skinny_bias takes it (added to K split 0).  n_splits,
+ *     the workspace and defer_reduce are vtgb_gemm_skinny's, and so are the consumers of a deferred split.  Only the 16-row blocks of x that
+ *     hold rows < M are staged and multiplied.  Errors, before any launch: vtgb_gemm_skinny's for `a`; VTGB_EINVAL for a NULL x / w / out and
+ *     for w_tiled != 1; VTGB_EUNSUPPORTED for a bias that is not 4-byte aligned. */
+size_t vtgb_pack_skinny_weight_mxfp4_bytes(int32_t N, int32_t K);
+int vtgb_pack_skinny_weight_mxfp4(const void* w, int64_t ldw, int32_t N, int32_t K, void* dst, vtgb_stream_t stream);
+int vtgb_gemm_skinny_mxfp4(const vtgb_gemm_skinny_args* a, const float* bias /* NULL: none */, vtgb_stream_t stream);
+
 /* ---- attention for the TRAINABLE stages (config C5, SF flavours): forward + backward, fp32 ---------------------------
  * Replaces, with its autograd, the matmul / softmax / dropout / matmul sequence of InstructBlipQFormerMultiHeadAttention.forward
  * (xinstructblip.py:611-694; BLIP-2 twin xblip2.py) and RopeBertSelfAttention.forward (xropebert.py:243-332; the rotary

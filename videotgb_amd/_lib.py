@@ -47,6 +47,7 @@ EXPORTS = [
     "vtgb_llm_decode_attention_split_fp8", "vtgb_llm_rope_cache_fp8", "vtgb_llm_rope_cache_prefill_fp8",
     "vtgb_raft_lookup_convc1", "vtgb_raft_gru_half", "vtgb_llm_lora", "vtgb_conv_launch", "vtgb_attention_cached",
     "vtgb_llm_decode_attention_beam", "vtgb_llm_beam_candidates", "vtgb_llm_attention_rows_beam",
+    "vtgb_pack_skinny_weight_mxfp4_bytes", "vtgb_pack_skinny_weight_mxfp4", "vtgb_gemm_skinny_mxfp4",
 ]
 COMM_ID_BYTES = 128
 
@@ -376,6 +377,12 @@ def lib() -> C.CDLL:
     L.vtgb_gemm_skinny_fp8.restype = C.c_int
     L.vtgb_gemm_skinny_bias.argtypes = [C.POINTER(GemmSkinnyArgs), vp, vp, vp]
     L.vtgb_gemm_skinny_bias.restype = C.c_int
+    L.vtgb_pack_skinny_weight_mxfp4_bytes.argtypes = [i32, i32]
+    L.vtgb_pack_skinny_weight_mxfp4_bytes.restype = sz
+    L.vtgb_pack_skinny_weight_mxfp4.argtypes = [vp, i64, i32, i32, vp, vp]
+    L.vtgb_pack_skinny_weight_mxfp4.restype = C.c_int
+    L.vtgb_gemm_skinny_mxfp4.argtypes = [C.POINTER(GemmSkinnyArgs), vp, vp]
+    L.vtgb_gemm_skinny_mxfp4.restype = C.c_int
     for fn in (L.vtgb_attn_train_forward, L.vtgb_attn_train_backward):
         fn.argtypes = [C.POINTER(AttnTrainArgs), vp]
         fn.restype = C.c_int

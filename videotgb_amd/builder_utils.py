@@ -19,7 +19,8 @@ def load_pretrained_model(ckpt_path, base_model_path, base_sampler_path, device,
                           decode_weights="bf16", kv_cache="bf16", beam_search="hf", **model_kwargs):
     """eval/utils/builder_utils.py:169-187.  ``compute_dtype`` / ``load_processors`` / ``decode_weights`` / ``kv_cache`` / ``model_kwargs`` are keyword extensions
     (the processors need tokenizer files next to the config; tests that only have a config.json pass ``load_processors=False``;
-    ``decode_weights="fp8"``: the opt-in fp8 weight stream of the Llama graph decoder, ``kv_cache="fp8"``: its opt-in fp8 K/V cache, ``beam_search="graph"``: its opt-in
+    ``decode_weights="fp8"``: the opt-in fp8 weight stream of the Llama graph decoder, ``"mxfp4"``: its opt-in MXFP4 weight stream (the ids are the
+    quantised model's, not the reference's; answer quality on a trained checkpoint is not measured by this project), ``kv_cache="fp8"``: its opt-in fp8 K/V cache, ``beam_search="graph"``: its opt-in
     beam search, ``"graph+t5"``: that and the T5 graph decoder's, models.LSTP)."""
     from .decode import check_beam_search, check_decode_weights, check_kv_cache
     check_decode_weights(decode_weights)

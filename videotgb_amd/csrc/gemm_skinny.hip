@@ -1,4 +1,5 @@
-// gemm_skinny.hip -- the decode step's projections: one weight-streaming kernel, two weight streams (bf16, and e4m3 codes with a row scale).
+// gemm_skinny.hip -- the decode step's projections: one weight-streaming kernel, three weight streams (bf16, e4m3 codes with a row scale, and MXFP4:
+// e2m1 codes with an E8M0 scale per 32-deep block).
 #include "common.h"
 #include "fp8_code.h"
 
@@ -40,9 +41,17 @@
 // half of the fp32) and multiplied by the SAME v_mfma_f32_16x16x32_bf16 in the same k order; the scale is applied to the fp32 accumulators
 // before a fragment leaves the registers (a power of two: exact), so fragments, the reduce launch and the deferred consumers see what the
 // bf16 stream would have produced from dq -- bit for bit.
+//
+// mxfp4 (opt-in: decode_weights="mxfp4"; OCP Microscaling v1.0, the definition is ops.quantize_mxfp4_rows).  Every 32 consecutive weights of a row
+// share one E8M0 scale 2^e (e = floor(log2(amax)) - 2, clamped to [-120, 125]) and are stored as e2m1 codes, two per byte.  code * 2^e is exactly
+// a normal bf16 number, so here too "the mxfp4 model" is an ordinary bf16 model with the weights dq = code * 2^e.  A lane's 8-deep k chunk of a
+// 32-deep MFMA half lies inside one block: v_cvt_scalef32_pk_bf16_fp4 widens a byte of two codes under the block's scale straight to the bf16
+// pair (exact), the operands feed the SAME v_mfma_f32_16x16x32_bf16 in the same k order and nothing is left for the epilogue -- fragments and
+// outputs are the bf16 stream's on dq, bit for bit.
 // ---------------------------------------------------------------------------------------
 constexpr int SK_BN = 128, SK_BK = 64, SK_TILE = 128 * 128;   // SK_TILE: bytes of one bf16 operand tile (128 rows x 64 bf16)
 constexpr int SK8_TILE = 128 * 64;                             // bytes of one fp8 weight block (128 rows x 64 codes)
+constexpr int SK4_CODES = 128 * 32, SK4_TILE = SK4_CODES + 256; // bytes of one mxfp4 weight block: 128 rows x 64 codes, then 128 rows x 2 scale bytes
 constexpr int SK_XSLOTS = 9, SK_XD = 8;                        // x ring (LDS) and how far ahead the loaders run
 constexpr int SK_THREADS = 384;
 typedef __attribute__((address_space(3))) void* sk_lptr_t;
@@ -82,7 +91,24 @@ __device__ __forceinline__ bf16x8 sk8_widen(int lo, int hi) {
 #endif
 }
 
-// ---- the two weight streams.  D: k-tiles in flight per multiplying wave (registers); LOADS: 16-byte loads per lane per k-tile.  base / range /
+// 8 e2m1 codes (one dword, the lower k in the low nibble) under the E8M0 scale byte of their block -> 8 bf16, exact.  The scale operand is the
+// fp32 2^e: the byte in the exponent field (bytes 7 .. 252 in a packed stream; 0 -- an out-of-range load -- is 0.0 and meets zero codes)
+__device__ __forceinline__ bf16x8 sk4_widen(int codes, unsigned e8m0) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_;
+    const float scale = __uint_as_float(e8m0 << 23);
+    const bf16x2_ a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4((unsigned)codes, scale, 0), b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4((unsigned)codes, scale, 1);
+    const bf16x2_ c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4((unsigned)codes, scale, 2), d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4((unsigned)codes, scale, 3);
+    const sk_i32x4 p = {__builtin_bit_cast(int, a), __builtin_bit_cast(int, b), __builtin_bit_cast(int, c), __builtin_bit_cast(int, d)};
+    return __builtin_bit_cast(bf16x8, p);
+#else
+    return bf16x8{};
+#endif
+}
+
+// ---- the weight streams.  D: k-tiles in flight per multiplying wave (registers); LOADS: 16-byte loads per lane per k-tile; SLOADS: 4-byte
+// loads per lane per k-tile beside them (block scales; the counted wait covers LOADS + SLOADS instructions per k-tile); BY_XB: whether the entry
+// launches the instantiation of the x row blocks that hold rows < M (else always all 8).  base / range /
 // kstep: the tile's buffer descriptor and the k-tile step in bytes; offset(l, row, fg): the byte offset of load l for the lane whose fragment
 // row is `row` of the tile's first 16 (wave * 32 + lane & 15) and whose 8-deep k chunk is fg; frag(r, i, half): the operand of 16-row fragment i,
 // 32-deep half `half`, from the k-tile's LOADS registers.
@@ -91,8 +117,8 @@ __device__ __forceinline__ bf16x8 sk8_widen(int lo, int hi) {
 // (vtgb_pack_skinny_weight): the tile's nk blocks of 16 KiB, rows in the LDS swizzle of rounds 1-2 (chunk q of row r holds k-chunk
 // q ^ ((r >> 1) & 7)).  Load 2 i + h: fragment i, half h.
 struct SkinnyBf16 {
-    static constexpr int D = 8, LOADS = 4;
-    static constexpr bool SCALED = false, BIASED = false;
+    static constexpr int D = 8, LOADS = 4, SLOADS = 0;
+    static constexpr bool SCALED = false, BIASED = false, BY_XB = false;
     static constexpr const char* ENTRY = "gemm_skinny";
     const bf16_t* w;
     int ldw, tiled;
@@ -113,8 +139,8 @@ struct SkinnyBf16 {
 // slot g = [8 codes of k 8g .. 8g+7 | 8 codes of k 32+8g ..], i.e. ONE 16-byte load per lane per 16-row fragment holds the lane's operands of
 // both 32-deep MFMAs of the k-tile (a wave reads 1 KiB contiguous per fragment).  Load i: fragment i.
 struct SkinnyFp8 {
-    static constexpr int D = 16, LOADS = 2;
-    static constexpr bool SCALED = true, BIASED = false;
+    static constexpr int D = 16, LOADS = 2, SLOADS = 0;
+    static constexpr bool SCALED = true, BIASED = false, BY_XB = true;
     static constexpr const char* ENTRY = "gemm_skinny_fp8";
     const uint8_t* w;
     const float* scale;
@@ -123,6 +149,31 @@ struct SkinnyFp8 {
     __device__ int kstep() const { return SK8_TILE; }
     __device__ unsigned offset(int l, int row, int fg) const { return (unsigned)((row + l * 16) * 64 + fg * 16); }
     static __device__ __forceinline__ bf16x8 frag(const sk_i32x4 (&r)[LOADS], int i, int half) { return sk8_widen(r[i][2 * half], r[i][2 * half + 1]); }
+};
+
+// e2m1 codes and E8M0 block scales (vtgb_pack_skinny_weight_mxfp4).  4096 + 256 bytes per (128-row tile, 64-deep k-tile).  Codes: the 16 bytes
+// at ((v * 16 + f) * 4 + g) * 16 belong to the lane of wave v with fragment row f and k chunk g -- dword 2 i + h = the 8 codes of row
+// v * 32 + i * 16 + f at k 32 h + 8 g .., i.e. ONE 16-byte load per lane holds the lane's operands of both fragments and both 32-deep MFMAs of
+// the k-tile (a wave reads 1 KiB contiguous).  Scales: the dword at 4096 + (v * 16 + f) * 4, byte 2 i + h = the scale byte of that row's block h
+// (the four lanes g of a row read the same dword).  The scale is applied by the conversion: SCALED = false, the bf16 epilogue.
+// D = 16: 16 KiB of codes + 1 KiB of scales in flight per wave, 64 + 4 KiB per workgroup, in 16 x 5 ring registers; the counted wait is
+// vmcnt(30).  Registers and the 6-bit vmcnt would allow D = 24 (96 + 6 KiB, vmcnt(46); D = 32 -- 128 KiB -- needs 160 ring registers and no
+// longer fits beside the XB = 8 accumulators at two waves per SIMD), and D = 24 was built and MEASURED SLOWER: the multiplying waves run whole
+// groups of D straight-line steps, so a split of 16 or 25 k-tiles (o and down at Vicuna-7B) pays 24 and 48 steps instead of 16 and 32
+// ("MXFP4 weight stream").
+struct SkinnyMxfp4 {
+    static constexpr int D = 16, LOADS = 1, SLOADS = 1;
+    static constexpr bool SCALED = false, BIASED = false, BY_XB = true;
+    static constexpr const char* ENTRY = "gemm_skinny_mxfp4";
+    const uint8_t* w;
+    __device__ uint64_t base(int b, int nk) const { return reinterpret_cast<uint64_t>(w + (int64_t)b * nk * SK4_TILE); }
+    __device__ unsigned range(int, int, int nk) const { return (unsigned)nk * SK4_TILE; }
+    __device__ int kstep() const { return SK4_TILE; }
+    __device__ unsigned offset(int, int row, int fg) const { return (unsigned)((((row >> 5) * 16 + (row & 15)) * 4 + fg) * 16); }
+    __device__ unsigned scale_offset(int row) const { return (unsigned)(SK4_CODES + ((row >> 5) * 16 + (row & 15)) * 4); }
+    static __device__ __forceinline__ bf16x8 frag(const sk_i32x4 (&r)[LOADS], int sc, int i, int half) {
+        return sk4_widen(r[0][2 * i + half], ((unsigned)sc >> (8 * (2 * i + half))) & 0xFFu);
+    }
 };
 
 // Either stream with a projection bias (vtgb_gemm_skinny_bias): bias[n] fp32 is added to the fp32 accumulators of split 0 alone, behind the row
@@ -186,6 +237,9 @@ __global__ __launch_bounds__(SK_THREADS) void gemm_skinny_kernel(const bf16_t* _
 #pragma unroll
     for (int l = 0; l < WS::LOADS; l++) wv[l] = ws.offset(l, wave * 32 + fr, fg);
     sk_i32x4 wreg[WS::D][WS::LOADS];
+    unsigned wsv = 0;                  // a stream with block scales (WS::SLOADS = 1): their per-lane byte offset and their ring, one dword per k-tile
+    int wsc[WS::D];
+    if constexpr (WS::SLOADS != 0) wsv = ws.scale_offset(wave * 32 + fr);
     // The ring's loads are inline asm and its waits are written by hand: with the builtin, hipcc's own vmcnt bookkeeping drained
     // the whole ring (vmcnt(0)) at the top of every group of WS::D steps -- it cannot see that a register loaded in one trip of the
     // loop is consumed in the next -- which halves the bytes in flight.  SK_WAIT_W(u): everything but the WS::D - 1 younger k-tiles
@@ -195,11 +249,14 @@ __global__ __launch_bounds__(SK_THREADS) void gemm_skinny_kernel(const bf16_t* _
         const int so_ = __builtin_amdgcn_readfirstlane((t) < ns ? (k0 + (t)) * kstep : 0x7FFFFF00);   /* past the split: out of range, no traffic */ \
         _Pragma("unroll") for (int l = 0; l < WS::LOADS; l++)                                                \
             asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=&v"(wreg[u][l]) : "v"(wv[l]), "s"(wrsrc), "s"(so_) : "memory"); \
+        if constexpr (WS::SLOADS != 0)                                                                       \
+            asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "=&v"(wsc[u]) : "v"(wsv), "s"(wrsrc), "s"(so_) : "memory"); \
     }
 #define SK_WAIT_W(u)                                                                                         \
     {                                                                                                        \
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WS::LOADS * (WS::D - 1)) : "memory");                       \
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((WS::LOADS + WS::SLOADS) * (WS::D - 1)) : "memory");        \
         _Pragma("unroll") for (int l = 0; l < WS::LOADS; l++) asm volatile("" : "+v"(wreg[u][l]));           \
+        if constexpr (WS::SLOADS != 0) asm volatile("" : "+v"(wsc[u]));                                      \
     }
     f32x4 acc[2][XB];
 #pragma unroll
@@ -236,7 +293,10 @@ __global__ __launch_bounds__(SK_THREADS) void gemm_skinny_kernel(const bf16_t* _
 #pragma unroll
             for (int i = 0; i < 2; i++)
 #pragma unroll
-                for (int h = 0; h < 2; h++) wf[i][h] = WS::frag(wreg[u], i, h);
+                for (int h = 0; h < 2; h++) {
+                    if constexpr (WS::SLOADS != 0) wf[i][h] = WS::frag(wreg[u], wsc[u], i, h);
+                    else wf[i][h] = WS::frag(wreg[u], i, h);
+                }
 #pragma unroll
             for (int g = 0; g < NG; g++) {
                 if (g < NG - 1) { SK_READ_X((g + 1) & 1, xs, g + 1) } else { SK_READ_X(0, xs_next, 0) }
@@ -252,6 +312,9 @@ __global__ __launch_bounds__(SK_THREADS) void gemm_skinny_kernel(const bf16_t* _
             SK_ISSUE_W(u, t + WS::D)
         }
     }
+    // The last group's re-issues (out of range: zeros, no traffic) may still be in flight, and hipcc, which does not know of them, hands their
+    // registers to the epilogue.  The streams above have run that way since they were written and keep their code; a stream added since drains.
+    if constexpr (WS::SLOADS != 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #undef SK_READ_X
 #undef SK_ISSUE_W
 #undef SK_WAIT_W
@@ -411,6 +474,62 @@ extern "C" int vtgb_pack_skinny_weight_fp8(const void* w, int64_t ldw, int32_t N
     return VTGB_OK;
 }
 
+// One workgroup per (128-row tile, k-tile) block of the stream, one thread per 16-byte code slot (wave v, fragment row f, k chunk g): the four
+// lanes g of a row hold its two 32-blocks of the k-tile between them (amax by two shuffles); lane g = 0 writes the row pair's four scale bytes.
+// ops.quantize_mxfp4_rows in integer and exact fp32 arithmetic: e from the exponent field of the block's largest |w|, the element times 2^-e
+// (a power of two: exact, or below 2^-126 where the code is 0 either way) against the grid's midpoints, which go to the even code.
+__global__ __launch_bounds__(256) void skinny_mxfp4_pack_kernel(const bf16_t* __restrict__ src, int64_t ld, int N, int nk, uint8_t* __restrict__ dst) {
+    const int tid = threadIdx.x, g = tid & 3, f = (tid >> 2) & 15, v = tid >> 6;
+    const int64_t blk = blockIdx.x, b = blk / nk, kt = blk - b * nk;
+    uint32_t o[4] = {0, 0, 0, 0}, sc = 0;
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        const int64_t n = b * 128 + v * 32 + i * 16 + f;
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            uint4 raw = make_uint4(0, 0, 0, 0);                // (rows beyond N: zero codes under e = 0)
+            if (n < N) raw = *reinterpret_cast<const uint4*>(src + n * ld + kt * 64 + h * 32 + g * 8);
+            const uint32_t rw[4] = {raw.x, raw.y, raw.z, raw.w};
+            uint32_t bits[8], amax = 0;
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+                bits[e] = (rw[e >> 1] >> (16 * (e & 1))) & 0xFFFFu;
+                amax = max(amax, bits[e] & 0x7FFFu);           // (|bf16| compares as its bits)
+            }
+            amax = max(amax, (uint32_t)__shfl_xor((int)amax, 1));
+            amax = max(amax, (uint32_t)__shfl_xor((int)amax, 2));
+            int ex = (int)(amax >> 7) - 127 - 2;               // floor(log2(amax)) - 2; a subnormal amax lands below the clamp
+            ex = amax == 0 ? 0 : ex < -120 ? -120 : ex > 125 ? 125 : ex;
+            const float down = __uint_as_float((uint32_t)(127 - ex) << 23);      // 2^-e
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+                const float a = __uint_as_float((bits[e] & 0x7FFFu) << 16) * down;
+                const uint32_t code = (uint32_t)(a > 0.25f) + (uint32_t)(a >= 0.75f) + (uint32_t)(a > 1.25f) + (uint32_t)(a >= 1.75f) + (uint32_t)(a > 2.5f) +
+                                      (uint32_t)(a >= 3.5f) + (uint32_t)(a > 5.f);
+                o[2 * i + h] |= (code | ((bits[e] >> 15) << 3)) << (4 * e);
+            }
+            sc |= (uint32_t)(ex + 127) << (8 * (2 * i + h));
+        }
+    }
+    uint8_t* const out = dst + blk * SK4_TILE;
+    *reinterpret_cast<uint4*>(out + tid * 16) = make_uint4(o[0], o[1], o[2], o[3]);
+    if (g == 0) *reinterpret_cast<uint32_t*>(out + SK4_CODES + (v * 16 + f) * 4) = sc;
+}
+
+extern "C" size_t vtgb_pack_skinny_weight_mxfp4_bytes(int32_t N, int32_t K) {
+    if (N <= 0 || K <= 0 || (K % SK_BK) != 0) return 0;
+    return (size_t)((N + SK_BN - 1) / SK_BN) * (K / SK_BK) * SK4_TILE;
+}
+
+extern "C" int vtgb_pack_skinny_weight_mxfp4(const void* w, int64_t ldw, int32_t N, int32_t K, void* dst, vtgb_stream_t s) {
+    VTGB_REQUIRE(w && dst && N > 0 && K > 0 && (K % SK_BK) == 0 && (ldw % 8) == 0 && ldw >= K, VTGB_EINVAL, "pack_skinny_weight_mxfp4: N=%d K=%d ldw=%lld", N, K,
+                 (long long)ldw);
+    const int64_t blocks = (int64_t)((N + SK_BN - 1) / SK_BN) * (K / SK_BK);
+    hipLaunchKernelGGL(skinny_mxfp4_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const bf16_t*)w, ldw, N, K / SK_BK, (uint8_t*)dst);
+    VTGB_HIP(hipGetLastError());
+    return VTGB_OK;
+}
+
 // ---- host side
 
 // splits.  Measured (tools/exp/skinny_bench.py, hipGraph replay, M = 124; profiles/r03_skinny_experiments.md): a workgroup streams
@@ -477,7 +596,7 @@ static int skinny_run(const vtgb_gemm_skinny_args* a, const WS& ws, vtgb_stream_
     const int S = skinny_splits(a);
     const size_t need = skinny_part_bytes(a, S);
     VTGB_REQUIRE(need == 0 || (a->workspace && a->workspace_bytes >= need), VTGB_EWORKSPACE, "%s: workspace %zu < %zu bytes", WS::ENTRY, a->workspace_bytes, need);
-    if constexpr (!WS::SCALED) {
+    if constexpr (!WS::BY_XB) {
         // bf16 always runs all 8 x row blocks: specialising it on XB as fp8 does would change what the default mode launches at small batch
         VTGB_TRY((skinny_launch<WS, 8>(a, ws, S, s)));
     } else {
@@ -518,4 +637,13 @@ extern "C" int vtgb_gemm_skinny_bias(const vtgb_gemm_skinny_args* a, const float
     if (!w_scale) return skinny_run(a, SkinnyBiased<SkinnyBf16>{{(const bf16_t*)a->w, (int)a->ldw, a->w_tiled}, bias}, s);
     VTGB_REQUIRE(a->w_tiled == 1, VTGB_EINVAL, "gemm_skinny_bias: fp8 weights are a vtgb_pack_skinny_weight_fp8 stream (w_tiled = 1)");
     return skinny_run(a, SkinnyBiased<SkinnyFp8>{{(const uint8_t*)a->w, w_scale}, bias}, s);
+}
+
+extern "C" int vtgb_gemm_skinny_mxfp4(const vtgb_gemm_skinny_args* a, const float* bias, vtgb_stream_t s) {
+    VTGB_TRY(skinny_check(a));
+    VTGB_REQUIRE(a->x && a->w && a->out, VTGB_EINVAL, "gemm_skinny_mxfp4: NULL operand");
+    VTGB_REQUIRE(a->w_tiled == 1, VTGB_EINVAL, "gemm_skinny_mxfp4: the weights are a vtgb_pack_skinny_weight_mxfp4 stream (w_tiled = 1)");
+    if (!bias) return skinny_run(a, SkinnyMxfp4{(const uint8_t*)a->w}, s);
+    VTGB_REQUIRE((reinterpret_cast<uintptr_t>(bias) & 3) == 0, VTGB_EUNSUPPORTED, "gemm_skinny_mxfp4: bias %p is not 4-byte aligned", (const void*)bias);
+    return skinny_run(a, SkinnyBiased<SkinnyMxfp4>{{(const uint8_t*)a->w}, bias}, s);
 }

@@ -59,11 +59,12 @@ def _rot_half(x: Tensor) -> Tensor:
     return torch.cat((-x[..., h:], x[..., :h]), dim=-1)
 
 
-DECODE_WEIGHTS = ("bf16", "fp8")
+DECODE_WEIGHTS = ("bf16", "fp8", "mxfp4")
 
 
 def check_decode_weights(weights) -> str:
-    """The decode-weight mode as the decoders take it: "bf16" (the model's own weights) or "fp8" (Llama: per-row e4m3 weight stream); ValueError otherwise."""
+    """The decode-weight mode as the decoders take it: "bf16" (the model's own weights), "fp8" (Llama: per-row e4m3 weight stream) or "mxfp4" (Llama:
+    e2m1 codes under an E8M0 scale per 32 weights); ValueError otherwise."""
     if weights not in DECODE_WEIGHTS:
         raise ValueError(f"decode_weights must be one of {DECODE_WEIGHTS}, got {weights!r}")
     return weights
@@ -525,6 +526,12 @@ class GreedyDecoder(_GraphDecoder):
     numbers, so every path decodes the same model: an ordinary Llama whose projection weights are q * scale.  Embeddings and norms are the
     model's own.  The fused path takes a bf16 model; the torch path (``fused=False``) also an fp32 one, quantised from its bf16 cast.
 
+    ``weights="mxfp4"`` (opt-in): the same arrangement on OCP MXFP4 -- e2m1 codes under one E8M0 scale per 32 weights along K
+    (ops.quantize_mxfp4_rows; the decode step streams ops.SkinnyWeightMxfp4, 17 / 64 of the bf16 bytes per token).  code * 2^e is exactly a bf16
+    number, so ``self.layers`` / ``self.head_w`` hold the dequantised weights and every path decodes that one model.  Its ids are the quantised
+    model's, not the reference's (the format's weight error is 11.5 % rel-RMS on Gaussian rows, fp8's 2.66 %); answer quality on a trained
+    checkpoint is not measured by this project.  Same conditions on the model's dtype as fp8.
+
     ``kv_cache="fp8"`` (opt-in, orthogonal to ``weights``): every K row (after rotary) and every V row -- one token of one K/V head -- is rounded
     once, as it is produced, to e4m3 codes with a power-of-two row scale (ops.quantize_fp8_kv), and the prefill attention, every decode step and
     every fallback attend over the dequantised values, which are exactly bf16 numbers: the mode is an ordinary bf16 Llama whose K/V pass
@@ -548,12 +555,14 @@ class GreedyDecoder(_GraphDecoder):
         wdt = lm.lm_head.weight.dtype
         if self.kv_cache == "fp8" and wdt != torch.bfloat16 and (fused or wdt != torch.float32):
             raise ValueError(f"kv_cache='fp8' needs a bf16 language model, got {wdt}")
-        if self.weights == "fp8" and wdt != torch.bfloat16 and (fused or wdt != torch.float32):
-            raise ValueError(f"decode_weights='fp8' needs a bf16 language model, got {wdt}")
+        if self.weights != "bf16" and wdt != torch.bfloat16 and (fused or wdt != torch.float32):
+            raise ValueError(f"decode_weights={self.weights!r} needs a bf16 language model, got {wdt}")
 
-        def prep(w):      # the matrix every path multiplies by: the model's own, or (fp8) its dequantised copy
+        def prep(w):      # the matrix every path multiplies by: the model's own, or (fp8, mxfp4) its dequantised copy
             if self.weights == "bf16":
                 return w
+            if self.weights == "mxfp4":
+                return ops.dequantize_mxfp4_rows(*ops.quantize_mxfp4_rows(w.detach().bfloat16()), dtype=w.dtype)
             return ops.dequantize_fp8_rows(*ops.quantize_fp8_rows(w.detach().bfloat16()), dtype=w.dtype)
         self.nh, self.nkv = cfg.num_attention_heads, cfg.num_key_value_heads
         self.hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
@@ -590,7 +599,7 @@ class GreedyDecoder(_GraphDecoder):
         self.inter = cfg.intermediate_size
         # LoRA adapters (train.LoraLinear on q / k / v), UNMERGED: per layer the (col0, A, B, scaling) segments of the fused q|k|v output that
         # ops.lora_update (vtgb_llm_lora) and ``_layer`` add after the base projection -- references to the model's own fp32 parameters, so the
-        # base stream stays the packed weights above (bf16, or fp8's q * scale).  None: no adapters, nothing below changes.
+        # base stream stays the packed weights above (bf16, or the quantised modes' dequantised values).  None: no adapters, nothing below changes.
         self.lora = None
         if has_lora:
             col0 = dict(q_proj=0, k_proj=self.nh * self.hd, v_proj=(self.nh + self.nkv) * self.hd)
@@ -607,8 +616,9 @@ class GreedyDecoder(_GraphDecoder):
     def _skinny_weights(self):
         if self._skinny is None:
             # (fp8: re-quantising the dequantised weights gives the same q * scale -- a row whose largest code rounded down to 224 comes back
-            # as twice the codes under half the scale, the same numbers)
-            pack = ops.SkinnyWeightFp8 if self.weights == "fp8" else ops.SkinnyWeight
+            # as twice the codes under half the scale, the same numbers; mxfp4: a block's largest element dequantises to 4 or 6 times 2^e, which
+            # gives the same e, the same codes and the same numbers -- ops.quantize_mxfp4_rows)
+            pack = {"bf16": ops.SkinnyWeight, "fp8": ops.SkinnyWeightFp8, "mxfp4": ops.SkinnyWeightMxfp4}[self.weights]
             self._skinny = [tuple(pack(w) for w in (wqkv, wo, wgu, wd)) for (_, wqkv, wo, _, wgu, wd) in self.layers]
             self._skinny.append(pack(self.head_w))
         return self._skinny
@@ -1223,7 +1233,7 @@ class T5GreedyDecoder(_GraphDecoder):
         if getattr(cfg, "model_type", "") != "t5":
             raise NotImplementedError("T5GreedyDecoder handles T5ForConditionalGeneration")
         if check_decode_weights(weights) != "bf16":
-            raise NotImplementedError("decode_weights='fp8' is implemented for the Llama decoder only")
+            raise NotImplementedError(f"decode_weights={weights!r} is implemented for the Llama decoder only")
         if check_kv_cache(kv_cache) != "bf16":
             raise NotImplementedError("kv_cache='fp8' is implemented for the Llama decoder only")
         _lora_servable(lm)      # (a T5 with adapters is never servable: NotImplementedError)
@@ -1585,7 +1595,7 @@ def keyword_stop_plan(criteria) -> dict:
 
 def make_decoder(lm, weights: str = "bf16", kv_cache: str = "bf16"):
     """The graph decoder for a language model: Llama-architecture causal LMs and T5 seq2seq LMs; NotImplementedError otherwise.
-    ``weights`` / ``kv_cache``: "bf16", or "fp8" (Llama only: GreedyDecoder)."""
+    ``weights``: "bf16", or "fp8" / "mxfp4" (Llama only: GreedyDecoder); ``kv_cache``: "bf16", or "fp8" (likewise)."""
     if getattr(lm.config, "model_type", "") == "t5":
         return T5GreedyDecoder(lm, weights=weights, kv_cache=kv_cache)
     return GreedyDecoder(lm, weights=weights, kv_cache=kv_cache)

@@ -450,7 +450,9 @@ class _LSTPBase(nn.Module):
         same accuracy class, 1.2 x slower); "bf16" = the fast REDUCED-PRECISION RAFT; "f32" = the fp32 FMA chain), ``lm_dtype`` of the built LLM
         (default: bf16 with compute_dtype "bf16", else fp32), ``tgb_cfg`` to size the TGB differently from BERT-base (tests), ``decode_weights``
         ("bf16"; "fp8" = opt-in: the graph decoder streams the Llama projections and lm_head as per-row e4m3 codes -- half the weight bytes per
-        token, and the ids are those of the quantised model, not the reference's; see decode.GreedyDecoder), ``kv_cache`` ("bf16"; "fp8" =
+        token, and the ids are those of the quantised model, not the reference's; "mxfp4" = opt-in: the same as OCP MXFP4, e2m1 codes under
+        one E8M0 scale per 32 weights -- 17 / 64 of the weight bytes per token; the ids are those of the quantised model, not the reference's, and
+        answer quality on a trained checkpoint is not measured by this project; see decode.GreedyDecoder), ``kv_cache`` ("bf16"; "fp8" =
         opt-in: the graph decoder keeps the Llama K/V cache as per-row e4m3 codes -- half the cache bytes per token and per state; the ids are
         those of the model whose K/V are rounded that way, not the reference's; see decode.GreedyDecoder), ``beam_search`` ("hf": requests with
         ``num_beams`` > 1 run on HF generate, as before; "graph" = opt-in: the Llama graph decoder runs HF's deterministic beam search --
@@ -473,8 +475,8 @@ class _LSTPBase(nn.Module):
                 if lm_dtype is None:
                     lm_dtype = torch.bfloat16 if ops.dtype_code(compute_dtype) == ops.BF16 else torch.float32
                 language_model = build_language_model(hf_config, lm_dtype)
-        if self.decode_weights == "fp8" and getattr(getattr(language_model, "config", None), "model_type", "") == "t5":
-            raise NotImplementedError("decode_weights='fp8' is implemented for the Llama decoder only")
+        if self.decode_weights != "bf16" and getattr(getattr(language_model, "config", None), "model_type", "") == "t5":
+            raise NotImplementedError(f"decode_weights={self.decode_weights!r} is implemented for the Llama decoder only")
         if self.kv_cache == "fp8" and getattr(getattr(language_model, "config", None), "model_type", "") == "t5":
             raise NotImplementedError("kv_cache='fp8' is implemented for the Llama decoder only")
         self.cfg = cfg

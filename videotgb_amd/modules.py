@@ -188,8 +188,8 @@ class _LSTPLightningBase(_Base):
         self.temperature = temperature
         self.generate_configs = dict(generate_configs or {})
         self.model = path_model_from_pretrained(model_name_or_path, self.ARCH, compute_dtype)
-        if self.decode_weights == "fp8" and getattr(self.model.language_model.config, "model_type", "") == "t5":
-            raise NotImplementedError("decode_weights='fp8' is implemented for the Llama decoder only")
+        if self.decode_weights != "bf16" and getattr(self.model.language_model.config, "model_type", "") == "t5":
+            raise NotImplementedError(f"decode_weights={self.decode_weights!r} is implemented for the Llama decoder only")
         if self.kv_cache == "fp8" and getattr(self.model.language_model.config, "model_type", "") == "t5":
             raise NotImplementedError("kv_cache='fp8' is implemented for the Llama decoder only")
         if processor is None:

@@ -259,6 +259,84 @@ class SkinnyWeightFp8:
         return t[: self.N].contiguous().view(torch.float8_e4m3fn)
 
 
+MXFP4_BLOCK = 32                                   # weights along K that share one E8M0 scale
+MXFP4_EMIN, MXFP4_EMAX = -120, 125                 # the clamp of the block exponent e (scale byte = e + 127)
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)   # magnitude of code c & 7; bit 3 is the sign
+
+
+def _pow2(e: Tensor) -> Tensor:
+    """2^e in fp32 for integer e in [-126, 127], built in the exponent field (exact on every backend)."""
+    return ((e.to(torch.int32) + 127) << 23).view(torch.float32)
+
+
+def quantize_mxfp4_rows(w: Tensor) -> Tuple[Tensor, Tensor]:
+    """nn.Linear.weight [N, K] -> (codes [N, K / 2] uint8, scales [N, K / 32] uint8): THE definition of the MXFP4 weight format (decode_weights="mxfp4";
+    vtgb_pack_skinny_weight_mxfp4 computes the same on the device, bit for bit).  OCP Microscaling v1.0, MXFP4: along K every block of 32
+    consecutive weights of a row shares one E8M0 scale 2^e, e = floor(log2(amax of the block)) - 2 (from the binary exponent: exact; 0 for an
+    all-zero block), clamped to [-120, 125] and stored as the byte e + 127.  An element is w * 2^-e rounded to the nearest e2m1 number (sign;
+    magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6 = codes 0 .. 7), ties to the even code, saturating at +-6; the sign bit (code bit 3) is the weight's
+    own, so a weight that rounds to zero keeps its sign.  Two codes per byte, the lower k in the low nibble.  Two properties follow.  Exactness:
+    code * 2^e has at most two mantissa bits and an exponent within [-121, 127], so it is exactly a normal (finite) bf16 number, and the mxfp4
+    model is an ordinary bf16 model whose weights are ``dequantize_mxfp4_rows(codes, scales)``.  Idempotence: the largest element of a block
+    scales into [4, 8) and rounds to 4 or 6, which gives the same e again, so quantising the dequantised matrix returns the same codes and scale
+    bytes (the decoder re-packs from its dequantised copy).  The one exception is a block under the lower clamp whose every element rounds to
+    zero (amax <= 2^-122, bf16 subnormals among them): its byte is 7 (e = -120), and the all-zero block it dequantises to has byte 127 -- the
+    same (zero) values.  The ids of the mode are the quantised model's, not the reference's, and answer quality on a trained checkpoint is not
+    measured by this project.  Runs on any device; a non-finite weight and a non-2-D input raise ValueError, K % 64 != 0 NotImplementedError
+    (the weight streams' k-tile)."""
+    if w.dim() != 2 or not w.is_floating_point():
+        raise ValueError(f"quantize_mxfp4_rows: a floating-point [N, K] matrix, got {w.dtype} {tuple(w.shape)}")
+    N, K = w.shape
+    if K == 0 or K % 64 != 0:
+        raise NotImplementedError(f"quantize_mxfp4_rows: K={K} must be a multiple of 64")
+    wf = w.detach().float()
+    if not bool(torch.isfinite(wf).all()):
+        raise ValueError("quantize_mxfp4_rows: the weights hold Inf or NaN")
+    a = wf.abs().view(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = a.amax(dim=2)
+    _, x = torch.frexp(amax)                                     # amax = m * 2^x with 0.5 <= m < 1: floor(log2(amax)) = x - 1
+    e = torch.where(amax > 0, x - 3, torch.zeros_like(x)).clamp_(MXFP4_EMIN, MXFP4_EMAX)
+    v = a * _pow2(-e)[:, :, None]                                # exact (or below 2^-126, where the code is 0 either way)
+    mag = ((v > 0.25).to(torch.uint8) + (v >= 0.75).to(torch.uint8) + (v > 1.25).to(torch.uint8) + (v >= 1.75).to(torch.uint8)
+           + (v > 2.5).to(torch.uint8) + (v >= 3.5).to(torch.uint8) + (v > 5.0).to(torch.uint8))      # midpoints go to the even code
+    c = (mag | (torch.signbit(wf).view_as(mag).to(torch.uint8) << 3)).view(N, K // 2, 2)
+    return (c[:, :, 0] | (c[:, :, 1] << 4)).contiguous(), (e + 127).to(torch.uint8)
+
+
+def dequantize_mxfp4_rows(codes: Tensor, scales: Tensor, dtype: torch.dtype = torch.bfloat16) -> Tensor:
+    """code * 2^e [N, K]: exact in bf16 (and so in fp32) for the pairs ``quantize_mxfp4_rows`` returns."""
+    N, K = codes.shape[0], codes.shape[1] * 2
+    c = torch.stack((codes & 15, codes >> 4), dim=2).view(N, K).long()
+    mag = torch.tensor(_E2M1, dtype=torch.float32, device=codes.device)[c & 7]
+    val = torch.where((c & 8) != 0, -mag, mag).view(N, K // MXFP4_BLOCK, MXFP4_BLOCK) * _pow2(scales.to(torch.int32) - 127)[:, :, None]
+    return val.view(N, K).to(dtype)
+
+
+class SkinnyWeightMxfp4:
+    """nn.Linear.weight [N, K] (bf16) quantised to MXFP4 (``quantize_mxfp4_rows``) and re-laid for vtgb_gemm_skinny_mxfp4's weight stream
+    (vtgb_pack_skinny_weight_mxfp4; one-time): ``data`` = per (128-row tile, 64-deep k-tile) 4 KiB of codes and 256 scale bytes, 17 / 32 of
+    SkinnyWeightFp8's bytes."""
+
+    def __init__(self, w: Tensor):
+        w = _skinny_stream_init(self, w, L.lib().vtgb_pack_skinny_weight_mxfp4_bytes, finite=True)
+        L.check(L.lib().vtgb_pack_skinny_weight_mxfp4(w.data_ptr(), w.stride(0), self.N, self.K, self.data.data_ptr(), _stream()))
+
+    def _blocks(self) -> Tensor:
+        return self.data.view((self.N + 127) // 128, self.K // 64, 4096 + 256)
+
+    def codes(self) -> Tensor:
+        """codes [N, K / 2] uint8, un-tiled (tests): the inverse of the stream's layout -- [tile][k-tile][wave][row & 15][k chunk][fragment][half][4 bytes]."""
+        nt, nk = (self.N + 127) // 128, self.K // 64
+        t = self._blocks()[:, :, :4096].reshape(nt, nk, 4, 16, 4, 2, 2, 4).permute(0, 2, 5, 3, 1, 6, 4, 7).reshape(nt * 128, self.K // 2)
+        return t[: self.N].contiguous()
+
+    def scales(self) -> Tensor:
+        """scale bytes [N, K / 32] uint8, un-tiled (tests): [tile][k-tile][wave][row & 15][fragment][half]."""
+        nt, nk = (self.N + 127) // 128, self.K // 64
+        t = self._blocks()[:, :, 4096:].reshape(nt, nk, 4, 16, 2, 2).permute(0, 2, 4, 3, 1, 5).reshape(nt * 128, self.K // 32)
+        return t[: self.N].contiguous()
+
+
 def gemm_skinny_workspace_bytes(M: int, N: int, K: int, n_splits: int = 0) -> int:
     a = L.GemmSkinnyArgs(M, N, K, n_splits, None, K, None, K, None, N, BF16, 0, None, 0)
     return int(L.lib().vtgb_gemm_skinny_workspace_bytes(C.byref(a)))
@@ -269,12 +347,13 @@ def gemm_skinny(x: Tensor, w: Tensor, out: Optional[Tensor] = None, n_splits: in
     """``defer_reduce``: returns (out, n_splits, workspace) and leaves the K-split fragments to the consumer (see below).
     x [M <= 128, K] bf16, w [N, K] bf16 (nn.Linear.weight, or its SkinnyWeight) -> x @ w.T [M, N]: the decode step's projections (vtgb_gemm_skinny:
     the weights stream once, K split over workgroups, fp32 partials added in a fixed order).  A ``SkinnyWeightFp8`` streams e4m3 codes instead
-    (vtgb_gemm_skinny_fp8): the result is that of the bf16 weights ``dequantize_fp8_rows(*quantize_fp8_rows(w))``, bit for bit.  ``out`` may be a preallocated
+    (vtgb_gemm_skinny_fp8): the result is that of the bf16 weights ``dequantize_fp8_rows(*quantize_fp8_rows(w))``, bit for bit; a ``SkinnyWeightMxfp4``
+    streams MXFP4 codes and block scales (vtgb_gemm_skinny_mxfp4), likewise equal to the bf16 kernel on ``dequantize_mxfp4_rows(*quantize_mxfp4_rows(w))``.  ``out`` may be a preallocated
     [M, N] tensor and ``workspace`` a preallocated uint8 scratch (hipGraph capture: fixed addresses, no allocation).  ``bias`` [N] fp32 (a projection
     bias; never quantised): x @ w.T + bias through vtgb_gemm_skinny_bias, either stream -- added in fp32 to K split 0, so the fragments a
-    ``defer_reduce`` call leaves already hold it; None takes the entries above, unchanged."""
-    fp8 = isinstance(w, SkinnyWeightFp8)
-    tiled = fp8 or isinstance(w, SkinnyWeight)
+    ``defer_reduce`` call leaves already hold it (the mxfp4 entry takes it itself); None takes the entries above, unchanged."""
+    fp8, mxfp4 = isinstance(w, SkinnyWeightFp8), isinstance(w, SkinnyWeightMxfp4)
+    tiled = fp8 or mxfp4 or isinstance(w, SkinnyWeight)
     _need_cuda(x, w.data if tiled else w)
     assert x.dtype == torch.bfloat16 and x.stride(1) == 1 and (tiled or (w.dtype == torch.bfloat16 and w.stride(1) == 1))
     M, K = x.shape
@@ -291,6 +370,9 @@ def gemm_skinny(x: Tensor, w: Tensor, out: Optional[Tensor] = None, n_splits: in
     if bias is not None:
         _need_cuda(bias)
         assert bias.dtype == torch.float32 and tuple(bias.shape) == (N,) and bias.stride(0) == 1
+    if mxfp4:
+        L.check(L.lib().vtgb_gemm_skinny_mxfp4(C.byref(a), _ptr(bias), _stream()))
+    elif bias is not None:
         L.check(L.lib().vtgb_gemm_skinny_bias(C.byref(a), w.scale.data_ptr() if fp8 else None, bias.data_ptr(), _stream()))
     elif fp8:
         L.check(L.lib().vtgb_gemm_skinny_fp8(C.byref(a), w.scale.data_ptr(), _stream()))
