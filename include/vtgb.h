@@ -890,6 +890,37 @@ typedef struct {
     void* workspace;
 } vtgb_llm_decode_attention_beam_args;
 int vtgb_llm_decode_attention_beam(const vtgb_llm_decode_attention_beam_args* a, vtgb_stream_t stream);
+/* vtgb_llm_decode_attention_beam_fp8 (opt-in: beam_search = "graph+kv8" with kv_cache = "fp8"; added at version 601 without a bump):
+ *   vtgb_llm_decode_attention_beam over fp8 K/V caches in vtgb_llm_decode_attention_split_fp8's format.  kp8 / vp8 [B, nkv, tmax_p, hd] uint8
+ *   e4m3 codes with kps / vps [B, nkv, tmax_p] fp32 power-of-two row scales: the prompt cache, as vtgb_llm_rope_cache_prefill_fp8 writes it on
+ *   B = R / K rows.  kg8 / vg8 [R, nkv, tmax_g, hd] with kgs / vgs [R, nkv, tmax_g]: what the beams generate, row r appending at slot = the step
+ *   (vtgb_llm_rope_cache_fp8).  src_row, *n_prompt, *pos, key_valid, the clamps, the workspace and pass 2 are vtgb_llm_decode_attention_beam's:
+ *   key t of row r is row t of item r / K's prompt cache for t < *n_prompt, else row t - *n_prompt of generated-cache row
+ *   clamp(src_row[r, t - *n_prompt], 0, R - 1), codes and scales from the same row.  An invisible key is loaded from row 0 of the item's prompt
+ *   cache, its codes replaced by zeros and its scales by 1 before any product: nothing past *pos, no masked slot and no prompt slot >= *n_prompt
+ *   reaches an output, whatever it holds (the e4m3 NaN code, a NaN scale, a table entry outside [0, R)).
+ *   The partition of every sum is vtgb_llm_decode_attention_split_fp8's on the global key index: the output equals, BIT FOR BIT,
+ *   vtgb_llm_decode_attention_beam(VTGB_BF16) on the dequantised caches, and so vtgb_llm_decode_attention_split on the gathered dequantised cache.
+ *   VTGB_EINVAL: NULL args / operand, a dtype other than VTGB_BF16, a non-positive size, R % K != 0, nq % nkv != 0; VTGB_EUNSUPPORTED: hd outside
+ *   {64, 128}, tmax_p or tmax_g not a multiple of 64, tmax_p + tmax_g > 16384, a misaligned operand (q / codes / out / workspace 16 bytes;
+ *   scales and src_row 4) -- on the host, before any launch. */
+typedef struct {
+    int32_t dtype;                       /* VTGB_BF16: q, out */
+    int32_t R, K, nq, nkv, hd, tmax_p, tmax_g;
+    float scale;
+    const void* q;                       /* [R, nq * hd] */
+    const uint8_t* kp8; const uint8_t* vp8;  /* [R / K, nkv, tmax_p, hd] */
+    const float* kps; const float* vps;  /* [R / K, nkv, tmax_p] */
+    const uint8_t* kg8; const uint8_t* vg8;  /* [R, nkv, tmax_g, hd] */
+    const float* kgs; const float* vgs;  /* [R, nkv, tmax_g] */
+    const int32_t* src_row;              /* [R, tmax_g] */
+    void* out;                           /* [R, nq * hd] */
+    const int64_t* n_prompt;             /* device */
+    const int64_t* pos;                  /* device: the last visible key */
+    const uint8_t* key_valid;            /* [R / K, tmax_p] or NULL */
+    void* workspace;
+} vtgb_llm_decode_attention_beam_fp8_args;
+int vtgb_llm_decode_attention_beam_fp8(const vtgb_llm_decode_attention_beam_fp8_args* a, vtgb_stream_t stream);
 typedef struct {
     int32_t dtype;                       /* of logits */
     int32_t R, K, V, N;

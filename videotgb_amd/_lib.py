@@ -46,7 +46,7 @@ EXPORTS = [
     "vtgb_llm_decode_attention_split_workspace_bytes", "vtgb_llm_decode_attention_split",
     "vtgb_llm_decode_attention_split_fp8", "vtgb_llm_rope_cache_fp8", "vtgb_llm_rope_cache_prefill_fp8",
     "vtgb_raft_lookup_convc1", "vtgb_raft_gru_half", "vtgb_llm_lora", "vtgb_conv_launch", "vtgb_attention_cached",
-    "vtgb_llm_decode_attention_beam", "vtgb_llm_beam_candidates", "vtgb_llm_attention_rows_beam",
+    "vtgb_llm_decode_attention_beam", "vtgb_llm_beam_candidates", "vtgb_llm_attention_rows_beam", "vtgb_llm_decode_attention_beam_fp8",
     "vtgb_pack_skinny_weight_mxfp4_bytes", "vtgb_pack_skinny_weight_mxfp4", "vtgb_gemm_skinny_mxfp4",
 ]
 COMM_ID_BYTES = 128
@@ -219,6 +219,13 @@ class LlmDecodeAttentionBeamArgs(C.Structure):
                 ("key_valid", vp), ("workspace", vp)]
 
 
+class LlmDecodeAttentionBeamFp8Args(C.Structure):
+    """vtgb_llm_decode_attention_beam_fp8_args: LlmDecodeAttentionBeamArgs over fp8 K/V caches (codes and row scales of the prompt and the generated cache)."""
+    _fields_ = [("dtype", i32), ("R", i32), ("K", i32), ("nq", i32), ("nkv", i32), ("hd", i32), ("tmax_p", i32), ("tmax_g", i32), ("scale", f32),
+                ("q", vp), ("kp8", vp), ("vp8", vp), ("kps", vp), ("vps", vp), ("kg8", vp), ("vg8", vp), ("kgs", vp), ("vgs", vp), ("src_row", vp),
+                ("out", vp), ("n_prompt", vp), ("pos", vp), ("key_valid", vp), ("workspace", vp)]
+
+
 class LlmBeamCandidatesArgs(C.Structure):
     """vtgb_llm_beam_candidates_args: one beam-search step's logits -> the 2 K best continuations of every batch item."""
     _fields_ = [("dtype", i32), ("R", i32), ("K", i32), ("V", i32), ("N", i32), ("eos", i32), ("min_new", i32), ("penalty", f32), ("logits", vp),
@@ -351,6 +358,8 @@ def lib() -> C.CDLL:
     L.vtgb_llm_rope_cache_fp8.restype = C.c_int
     L.vtgb_llm_decode_attention_beam.argtypes = [C.POINTER(LlmDecodeAttentionBeamArgs), vp]
     L.vtgb_llm_decode_attention_beam.restype = C.c_int
+    L.vtgb_llm_decode_attention_beam_fp8.argtypes = [C.POINTER(LlmDecodeAttentionBeamFp8Args), vp]
+    L.vtgb_llm_decode_attention_beam_fp8.restype = C.c_int
     L.vtgb_llm_beam_candidates.argtypes = [C.POINTER(LlmBeamCandidatesArgs), vp]
     L.vtgb_llm_beam_candidates.restype = C.c_int
     L.vtgb_llm_attention_rows_beam.argtypes = [C.POINTER(LlmAttnRowsArgs), vp, i64, i32, vp]

@@ -1,10 +1,11 @@
 // attn_decode.hip -- split-KV ("flash-decoding") single-query attention over the static K/V cache of the decode step, for caches the
 // one-wave-per-head kernel of llm.hip cannot hold (its scores live in LDS: 2048 keys) or serves badly (8 workgroups at batch 1).
-// Two launches, no atomics.  Pass 1 is written once (decode_attn_pass1) and reads its keys through a key source; three entries, one source each:
+// Two launches, no atomics.  Pass 1 is written once (decode_attn_pass1) and reads its keys through a key source; four entries, one source each:
 //   vtgb_llm_decode_attention_split      DenseKV   one cache kc / vc [B, nkv, tmax, hd] of bf16 or fp32
 //   vtgb_llm_decode_attention_split_fp8  Fp8KV     e4m3 codes and one power-of-two scale per row (kv_cache="fp8")
 //   vtgb_llm_decode_attention_beam       BeamKV    a prompt cache per batch item + a generated cache read through src_row (beam_search="graph")
-// The later two compute, bit for bit, what the first computes on the cache they stand for (see the sources below).
+//   vtgb_llm_decode_attention_beam_fp8   BeamFp8KV BeamKV's two caches and table over Fp8KV's codes and scales (beam_search="graph+kv8")
+// The later three compute, bit for bit, what the first computes on the cache they stand for (see the sources below).
 //
 // Pass 1.  Grid (key chunk, K/V head x query-head block, row), fixed by tmax, so one captured graph serves every step: a workgroup whose
 // chunk starts past *pos leaves after reading *pos.  A chunk is DEC_SPLIT_CHUNK = 256 keys, 64 per wave.  A wave holds its 64 K rows in
@@ -64,7 +65,7 @@ __device__ __forceinline__ float group_sum(float v) {
 //   HD, EPL, Reg       head_dim; elements per lane and row; the register that holds them
 //   SCALED             whether a row carries scales (scales() below)
 //   walk_pos, pos      the clamped positions: pass 2 walks the chunks 0 .. walk_pos / 256, the last visible key is pos <= walk_pos
-//   seat<MASKED>(r, kvh, c)   this workgroup's row and K/V head, this lane's piece of a row
+//   seat<MASKED>(r, kvh, c)   this workgroup's row and K/V head, this lane's piece of a row (called once, before any load: BeamFp8KV starts its scale loads here)
 //   visible<MASKED>(key)
 //   row(key, ok)       where the key's row lies (Row; ok = visible): an invisible key gets a safe in-bounds row, one for the whole grid
 //   k(), v()           the K and the V cache (Cache), handed to load()
@@ -256,7 +257,107 @@ struct BeamKV {
     static __device__ __forceinline__ void widen(const Reg& v, float (&f)[EPL]) { DenseKV<T, HD_>::widen(v, f); }
 };
 
-// ---- pass 1, for the workgroup (blockIdx.x = chunk, blockIdx.y = K/V head x head block, blockIdx.z = row); ``rows`` = gridDim.z
+// Beam search over the fp8 K/V cache (opt-in: beam_search="graph+kv8" with kv_cache="fp8").  BeamKV's two caches, visibility and ancestry
+// table over Fp8KV's storage: kp8 / vp8 [B, nkv, tmax_p, hd] codes with kps / vps [B, nkv, tmax_p] scales (the fp8 prefill's, on B rows),
+// kg8 / vg8 [R, nkv, tmax_g, hd] with kgs / vgs [R, nkv, tmax_g] (vtgb_llm_rope_cache_fp8 at slot = the step).  A key resolves to ONE cache
+// row (Row: its index in rows of HD codes, into the prompt or the generated cache), which serves its codes (row * HD) and its scales (row)
+// alike; an invisible key resolves to row 0 of the item's prompt cache, its codes selected to zeros and its scales to 1.
+// Contract: the partition is Fp8KV's (EPL = 8, 8-byte loads, scales applied in the softmax stage) on the global key index, so the output equals,
+// bit for bit, vtgb_llm_decode_attention_beam on the dequantised caches -- and so vtgb_llm_decode_attention_split on the gathered one.
+template <int HD_>
+struct BeamFp8KV {
+    static constexpr int HD = HD_, EPL = 8;
+    static constexpr bool SCALED = true;
+    typedef uint2 Reg;
+    typedef int64_t Row;
+    const uint8_t* __restrict__ kp8;
+    const uint8_t* __restrict__ vp8;
+    const float* __restrict__ kps;
+    const float* __restrict__ vps;
+    const uint8_t* __restrict__ kg8;
+    const uint8_t* __restrict__ vg8;
+    const float* __restrict__ kgs;
+    const float* __restrict__ vgs;
+    const int32_t* __restrict__ src_row;
+    const uint8_t* key_valid;
+    const uint8_t* kvr;
+    int R, K, nkv, tmax_p, tmax_g, np, pos, walk_pos, r, kvh, c, softmax_waves;
+    int64_t prow0;      // row 0 of the item's prompt cache (this K/V head)
+    float psk[4], psv[4];      // the scales of this lane's four softmax keys, fetched in seat() (indexed by constants only: registers)
+    __device__ __forceinline__ BeamFp8KV(const vtgb_llm_decode_attention_beam_fp8_args& a)
+        : kp8(a.kp8), vp8(a.vp8), kps(a.kps), vps(a.vps), kg8(a.kg8), vg8(a.vg8), kgs(a.kgs), vgs(a.vgs), src_row(a.src_row), key_valid(a.key_valid),
+          kvr(nullptr), R(a.R), K(a.K), nkv(a.nkv), tmax_p(a.tmax_p), tmax_g(a.tmax_g), softmax_waves(min(DEC_SPLIT_HEADS, a.nq / a.nkv)) {
+        const int tmax = tmax_p + tmax_g;
+        const int64_t np64 = *a.n_prompt, pos64 = *a.pos;
+        np = (int)(np64 < 0 ? 0 : np64 > tmax_p ? tmax_p : np64);
+        walk_pos = (int)(pos64 < -1 ? -1 : pos64 > tmax - 1 ? tmax - 1 : pos64);
+        pos = min(walk_pos, np + tmax_g - 1);
+    }
+    template <bool MASKED>
+    __device__ __forceinline__ void seat(int r_, int kvh_, int c_) {
+        r = r_, kvh = kvh_, c = c_;
+        const int b = r / K;
+        prow0 = ((int64_t)b * nkv + kvh) * tmax_p;
+        if (MASKED) kvr = key_valid + (int64_t)b * tmax_p;
+        // A generated key's scale lies behind two dependent loads (the table, then the row's scale).  Pass 1 asks for the scales in its softmax
+        // stage, behind a barrier, where that chain would be on the workgroup's critical path (measured: the kernel 9 % slower than the bf16
+        // beam kernel on half the bytes); so the waves that can take part in that stage (wave < min(DEC_SPLIT_HEADS, nq / nkv) >= nh) fetch the
+        // scales of their four softmax keys -- key = chunk * 256 + lane + 64 j, chunk = blockIdx.x, as pass 1 defines them -- here, where
+        // the loads fly behind the K loads.  scales() hands them out and checks nothing but the key's j.
+#pragma unroll
+        for (int j = 0; j < 4; j++) psk[j] = psv[j] = 1.f;
+        if ((int)(threadIdx.x >> 6) < softmax_waves) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int key = blockIdx.x * DEC_SPLIT_CHUNK + (threadIdx.x & 63) + 64 * j;
+                const bool ok = visible<MASKED>(key), gen = ok && key >= np;
+                const Row o = row(key, ok);
+                psk[j] = (gen ? kgs : kps)[o];
+                psv[j] = (gen ? vgs : vps)[o];
+            }
+        }
+    }
+    template <bool MASKED>
+    __device__ __forceinline__ bool visible(int key) const {
+        bool ok = key <= pos;
+        if (MASKED && ok && key < np) ok = kvr[key] != 0;
+        return ok;
+    }
+    __device__ __forceinline__ Row row(int key, bool ok) const {
+        int64_t o = prow0;
+        if (ok && key < np) {
+            o = prow0 + key;
+        } else if (ok) {
+            const int g = key - np;      // < tmax_g: key <= pos <= np + tmax_g - 1
+            int sr = src_row[(int64_t)r * tmax_g + g];
+            sr = sr < 0 ? 0 : sr >= R ? R - 1 : sr;
+            o = ((int64_t)sr * nkv + kvh) * tmax_g + g;
+        }
+        return o;
+    }
+    struct Cache {
+        const uint8_t* __restrict__ p;
+        const uint8_t* __restrict__ g;
+    };
+    __device__ __forceinline__ Cache k() const { return Cache{kp8, kg8}; }
+    __device__ __forceinline__ Cache v() const { return Cache{vp8, vg8}; }
+    static __device__ __forceinline__ Reg zero() { return make_uint2(0u, 0u); }
+    __device__ __forceinline__ Reg load(Cache cache, Row row, int key, bool ok, const Reg&) const {
+        const uint8_t* p = (ok && key >= np) ? cache.g : cache.p;
+        const uint2 v = *reinterpret_cast<const uint2*>(p + row * HD + c * EPL);
+        return ok ? v : make_uint2(0u, 0u);      // (an immediate, as in Fp8KV::load)
+    }
+    static __device__ __forceinline__ void widen(const Reg& v, float (&f)[EPL]) { Fp8KV<HD_>::widen(v, f); }
+    __device__ __forceinline__ void scales(int key, bool ok, float& sk, float& sv) const {
+        const int j = key >> 6 & 3;      // (key = chunk * 256 + lane + 64 j)
+        const float a = j == 0 ? psk[0] : j == 1 ? psk[1] : j == 2 ? psk[2] : psk[3];
+        const float v = j == 0 ? psv[0] : j == 1 ? psv[1] : j == 2 ? psv[2] : psv[3];
+        sk = ok ? a : 1.f;
+        sv = ok ? v : 1.f;
+    }
+};
+
+// ---- pass 1, for the workgroup (blockIdx.x = chunk,blockIdx.y = K/V head x head block, blockIdx.z = row); ``rows`` = gridDim.z
 template <bool MASKED, typename Src, typename TQ>
 __device__ __forceinline__ void decode_attn_pass1(Src src, const TQ* __restrict__ q, float* __restrict__ ws, int rows, int nq, int nkv, int tmax,
                                                   float scale) {
@@ -426,6 +527,13 @@ __global__ __launch_bounds__(256) void llm_decode_attn_beam_kernel(const T* __re
                               tmax_p + tmax_g, scale);
 }
 
+template <int HD, bool MASKED>
+__global__ __launch_bounds__(256) void llm_decode_attn_beam_fp8_kernel(const vtgb_llm_decode_attention_beam_fp8_args a) {
+    const bf16_t* __restrict__ q = (const bf16_t*)a.q;
+    float* __restrict__ ws = (float*)a.workspace;
+    decode_attn_pass1<MASKED>(BeamFp8KV<HD>(a), q, ws, a.R, a.nq, a.nkv, a.tmax_p + a.tmax_g, a.scale);
+}
+
 // One workgroup of hd threads per (row, query head).
 template <typename T>
 __global__ __launch_bounds__(128) void llm_decode_attn_combine_kernel(const float* __restrict__ ws, T* __restrict__ out, const int64_t* __restrict__ pos_p,
@@ -560,4 +668,25 @@ extern "C" int vtgb_llm_decode_attention_beam(const vtgb_llm_decode_attention_be
     hipStream_t s = (hipStream_t)stream;
     if (a->dtype == VTGB_BF16) return a->hd == 128 ? launch_beam<bf16_t, 128>(a, s) : launch_beam<bf16_t, 64>(a, s);
     return a->hd == 128 ? launch_beam<float, 128>(a, s) : launch_beam<float, 64>(a, s);
+}
+
+template <int HD>
+static int launch_beam_fp8(const vtgb_llm_decode_attention_beam_fp8_args* a, hipStream_t s) {
+    return launch_decode_attn<bf16_t>(llm_decode_attn_beam_fp8_kernel<HD, true>, llm_decode_attn_beam_fp8_kernel<HD, false>, a->key_valid, a->R, a->nq, a->nkv,
+                                      HD, a->tmax_p + a->tmax_g, a->pos, a->workspace, a->out, s, *a);
+}
+
+extern "C" int vtgb_llm_decode_attention_beam_fp8(const vtgb_llm_decode_attention_beam_fp8_args* a, vtgb_stream_t stream) {
+    VTGB_REQUIRE(a, VTGB_EINVAL, "llm_decode_attention_beam_fp8: NULL args");
+    VTGB_REQUIRE(a->q && a->kp8 && a->vp8 && a->kps && a->vps && a->kg8 && a->vg8 && a->kgs && a->vgs && a->src_row && a->out && a->n_prompt && a->pos &&
+                     a->workspace,
+                 VTGB_EINVAL, "llm_decode_attention_beam_fp8: NULL operand");
+    VTGB_REQUIRE(a->dtype == VTGB_BF16 && a->R > 0 && a->K > 0 && a->nq > 0 && a->nkv > 0 && a->tmax_p > 0 && a->tmax_g > 0, VTGB_EINVAL,
+                 "llm_decode_attention_beam_fp8: bad argument (activations are VTGB_BF16)");
+    VTGB_REQUIRE(a->R % a->K == 0, VTGB_EINVAL, "llm_decode_attention_beam_fp8: R=%d rows are not a multiple of K=%d beams", a->R, a->K);
+    VTGB_TRY(check_decode_attn({"llm_decode_attention_beam_fp8", "R", a->R, a->nq, a->nkv, a->hd, a->tmax_p, a->tmax_g},
+                               {a->q, a->kp8, a->vp8, a->kg8, a->vg8, a->out, a->workspace}, {a->kps, a->vps, a->kgs, a->vgs, a->src_row},
+                               "q / kp8 / vp8 / kg8 / vg8 / out / workspace need 16-byte, kps / vps / kgs / vgs / src_row 4-byte alignment"));
+    hipStream_t s = (hipStream_t)stream;
+    return a->hd == 128 ? launch_beam_fp8<128>(a, s) : launch_beam_fp8<64>(a, s);
 }

@@ -22,7 +22,8 @@ decode (the bench's "no EOS stopping, fixed work per clip" mode).
 Greedy ids are checked token-for-token against HF generate at fp32 (tests/test_decode.py, test_gpu_e2e.py).
 Opt-in (an owner's ``beam_search="graph"``): HF's deterministic beam search on the Llama decoder -- ``GreedyDecoder.generate(num_beams=...,
 repetition_penalty=..., length_penalty=...)``; by default such requests go to HF generate as before (tests/test_beam_decode.py,
-test_gpu_beam_decode.py).
+test_gpu_beam_decode.py).  ``beam_search="graph+kv8"`` / ``"graph+t5+kv8"``: the same, and the beams of a ``kv_cache="fp8"`` Llama run over
+the fp8 cache (``GreedyDecoder(fp8_beams=True)``; tests/test_beam_kv8.py, test_gpu_beam_kv8.py).
 
 Structure: ``_GraphDecoder`` owns everything that is not the model -- the state cache (LRU, MAX_STATES), the emission state (token / position
 feedback, finished flags, lengths, sampling and stopping data), token selection, capture, the replay loop and the truncation of the returned ids;
@@ -80,13 +81,14 @@ def check_kv_cache(kv_cache) -> str:
     return kv_cache
 
 
-BEAM_SEARCH = ("hf", "graph", "graph+t5")
+BEAM_SEARCH = ("hf", "graph", "graph+t5", "graph+kv8", "graph+t5+kv8")
 
 
 def check_beam_search(beam_search) -> str:
     """Who runs a beam-search request: "hf" (HF generate, the default), "graph" (opt-in: the Llama graph decoder; a T5's beam requests stay
-    on HF) or "graph+t5" (opt-in: that, and the T5 graph decoder); ValueError otherwise."""
-    if beam_search not in BEAM_SEARCH:
+    on HF), "graph+t5" (opt-in: that, and the T5 graph decoder) or either with "+kv8" (opt-in: that, and the beams of a ``kv_cache="fp8"`` Llama
+    run over the fp8 cache -- ``GreedyDecoder(fp8_beams=True)`` -- instead of being refused); ValueError otherwise."""
+    if not isinstance(beam_search, str) or beam_search not in BEAM_SEARCH:
         raise ValueError(f"beam_search must be one of {BEAM_SEARCH}, got {beam_search!r}")
     return beam_search
 
@@ -496,7 +498,7 @@ class _GraphDecoder:
     def _replay_beams(self, st, use_graph: bool) -> Tensor:
         """Steps 1 .. N-1 (the first selection came from the prefill), one graph replay each; ``done`` is read once per 16 steps."""
         N = st["run_seq"].shape[2]
-        use_graph = use_graph and st["tok"].is_cuda and st["attn"] == "beam"
+        use_graph = use_graph and st["tok"].is_cuda and st["attn"] in ("beam", "beam_fp8")
         if N > 1:
             if use_graph and st["graph"] is None:
                 self._capture(st)
@@ -535,7 +537,7 @@ class GreedyDecoder(_GraphDecoder):
     ``kv_cache="fp8"`` (opt-in, orthogonal to ``weights``): every K row (after rotary) and every V row -- one token of one K/V head -- is rounded
     once, as it is produced, to e4m3 codes with a power-of-two row scale (ops.quantize_fp8_kv), and the prefill attention, every decode step and
     every fallback attend over the dequantised values, which are exactly bf16 numbers: the mode is an ordinary bf16 Llama whose K/V pass
-    through ``ops.fp8_kv_round``.  On the device, fused, with a cache the split-KV kernel takes (head_dim 64 / 128, up to 16384 slots) the state
+    through ``ops.fp8_kv_round``.  ``fp8_beams=True`` (opt-in): beam search runs over that cache as well (``_beam_state``) instead of being refused.  On the device, fused, with a cache the split-KV kernel takes (head_dim 64 / 128, up to 16384 slots) the state
     holds the codes and scales (half the bytes: ``st["attn"] == "split_fp8"``, vtgb_llm_rope_cache{,_prefill}_fp8 +
     vtgb_llm_decode_attention_split_fp8); otherwise it keeps bf16 caches of dequantised values and decodes on the torch step (``_layer`` states
     the model; no memory is saved).  The fused path takes a bf16 model; the torch path also an fp32 one.
@@ -545,13 +547,14 @@ class GreedyDecoder(_GraphDecoder):
     epilogue -- ops.gemm_skinny(bias=), vtgb_gemm_skinny_bias --, prefill and large batches through vtgb_gemm's bias, ``_layer`` through
     F.linear).  Anything else raises NotImplementedError with the reason."""
 
-    def __init__(self, lm, fused: bool = True, weights: str = "bf16", kv_cache: str = "bf16"):
+    def __init__(self, lm, fused: bool = True, weights: str = "bf16", kv_cache: str = "bf16", fp8_beams: bool = False):
         cfg = lm.config
         if "llama" not in cfg.model_type:
             raise NotImplementedError("GreedyDecoder handles Llama-architecture models; use HF generate otherwise")
         _llama_servable(lm)
         has_lora = _lora_servable(lm)
         super().__init__(lm, fused, weights, kv_cache)
+        self.fp8_beams = bool(fp8_beams)      # opt-in (beam_search="...+kv8"): num_beams > 1 over the fp8 K/V cache; inert with a bf16 cache
         wdt = lm.lm_head.weight.dtype
         if self.kv_cache == "fp8" and wdt != torch.bfloat16 and (fused or wdt != torch.float32):
             raise ValueError(f"kv_cache='fp8' needs a bf16 language model, got {wdt}")
@@ -910,7 +913,9 @@ class GreedyDecoder(_GraphDecoder):
         # a beam state (st["attn"] == "beam"): the rows are the B * K beams; a row appends its K/V at slot = the step of the generated caches
         # kg / vg (rotary row = slot + rope_off[r] of the state's tables) and attends through the ancestry table over the prompt cache of its
         # batch item (B rows: the key mask is the batch item's) and the generated caches (vtgb_llm_decode_attention_beam)
-        beam = st["attn"] == "beam"
+        # ("beam_fp8": the same over fp8 caches -- kg8 / vg8 / kgs / vgs, a prompt state of code caches, vtgb_llm_decode_attention_beam_fp8)
+        beam_fp8 = st["attn"] == "beam_fp8"
+        beam = st["attn"] == "beam" or beam_fp8
         row_off = padded or beam
         h, q, a, act = st["h"], st["q"], st["a"], st["act"]
         if skinny:
@@ -945,7 +950,7 @@ class GreedyDecoder(_GraphDecoder):
         # (its workspace exists exactly where the split kernel serves it)
         rope = (_ptr(st["cos"]), _ptr(st["sin"]), _ptr(st["slot"] if beam else st["pos"])) + ((_ptr(st["rope_off"]),) if row_off else ())
         attn_ws, key_valid = st.get("attn_ws"), st.get("key_valid")
-        fp8_kv = st["attn"] == "split_fp8"      # kv_cache="fp8": the append quantises the K / V rows, the attention reads codes and scales
+        fp8_kv = st["attn"] == "split_fp8" or beam_fp8      # kv_cache="fp8": the append quantises the K / V rows, the attention reads codes and scales
         delta, dS = None, 1
         for li, (ln1, wqkv, wo, ln2, wgu, wd) in enumerate(self.layers):
             norm(delta, dS, ln1)
@@ -954,11 +959,16 @@ class GreedyDecoder(_GraphDecoder):
             else:
                 qkv, qS = lin_d(h, li, 0, "sk_qkv")
             if fp8_kv:
-                kv8 = (st["kc8"][li], st["vc8"][li], st["ks"][li], st["vs"][li])
-                ra = L.LlmRopeCacheFp8Args(code, B, nq, nkv, hd, tmax, qS if qS > 1 else 0, None if qS > 1 else _ptr(qkv), _ptr(ws) if qS > 1 else None,
-                                           _ptr(q), *(_ptr(t) for t in kv8), *rope[:3], rope[3] if padded else None)
+                kv8 = tuple(st[n][li] for n in (("kg8", "vg8", "kgs", "vgs") if beam else ("kc8", "vc8", "ks", "vs")))
+                ra = L.LlmRopeCacheFp8Args(code, B, nq, nkv, hd, st["tmax_g"] if beam else tmax, qS if qS > 1 else 0, None if qS > 1 else _ptr(qkv),
+                                           _ptr(ws) if qS > 1 else None, _ptr(q), *(_ptr(t) for t in kv8), *rope[:3], rope[3] if row_off else None)
                 L.check(lib.vtgb_llm_rope_cache_fp8(ctypes.byref(ra), stream))
-                ops.decode_attention_fp8(q, *kv8, st["pos"], float(hd) ** -0.5, key_valid=key_valid, out=a, workspace=attn_ws)
+                if beam:
+                    pst = st["prompt"]
+                    ops.decode_attention_beam_fp8(q, pst["kc8"][li], pst["vc8"][li], pst["ks"][li], pst["vs"][li], *kv8, st["src_row"], st["nprompt"],
+                                                  st["pos"], float(hd) ** -0.5, key_valid=key_valid, out=a, workspace=attn_ws)
+                else:
+                    ops.decode_attention_fp8(q, *kv8, st["pos"], float(hd) ** -0.5, key_valid=key_valid, out=a, workspace=attn_ws)
             else:
                 kc, vc = (st["kg"][li], st["vg"][li]) if beam else (st["kc"][li], st["vc"][li])
                 rope_cache = getattr(lib, "vtgb_llm_rope_cache" + ("_parts" if qS > 1 else "") + ("_pos" if row_off else ""))
@@ -1012,6 +1022,9 @@ class GreedyDecoder(_GraphDecoder):
     # written before every call to start at the batch's first generated position (cos / sin [tmax_g, hd]; tmax_g covers N plus the spread of
     # the rows' first positions in a ragged batch).  Elsewhere (CPU, fused=False) the rows keep whole caches, re-ordered by index_select as
     # HF re-orders its cache: the torch statement of the same search.
+    # kv_cache="fp8" under ``fp8_beams``: on the device the prompt state is an fp8 prefill state (attn "split_fp8": kc8 / vc8 / ks / vs on B rows)
+    # and the generated caches are kg8 / vg8 [R, nkv, tmax_g, hd] uint8 with kgs / vgs [R, nkv, tmax_g] fp32 (attn "beam_fp8":
+    # vtgb_llm_rope_cache_fp8 appends, vtgb_llm_decode_attention_beam_fp8 reads); elsewhere ``_layer`` rounds K/V into the whole caches.
     def _beam_state(self, B: int, K: int, P: int, N: int, device, dtype, eos, fill: int, min_new: int, rep_pen: float, len_pen: float, padded: bool,
                     spread: int):
         R = B * K
@@ -1020,29 +1033,38 @@ class GreedyDecoder(_GraphDecoder):
         tmax_p, tmax_g = -(-P // 64) * 64, -(-(N + spread) // 64) * 64
         if not kernel:
             tmax_p, tmax_g = -(-(P + N) // 64) * 64, 0      # (one cache per row, as the plain decoder's)
-        elif not (ops.decode_attention_beam_ok(tmax_p, tmax_g, hd) and self.nh % nkv == 0):
+        elif not ((ops.decode_attention_beam_fp8_ok if self.kv_cache == "fp8" else ops.decode_attention_beam_ok)(tmax_p, tmax_g, hd) and self.nh % nkv == 0):
             raise NotImplementedError(f"num_beams > 1 on the device needs head_dim 64 or 128 and a cache up to {ops.DECODE_SPLIT_MAX_KEYS} slots "
                                       f"(head_dim {hd}, {tmax_p} + {tmax_g} slots)")
         elif K > ops.BEAM_MAX_BEAMS or 2 * K > self.head_w.shape[0]:
             raise NotImplementedError(f"num_beams={K}: up to {ops.BEAM_MAX_BEAMS} beams, 2 x num_beams <= vocab_size")
         tmax = tmax_p + tmax_g
+        fp8 = kernel and self.kv_cache == "fp8"      # the code caches (the fused device path takes a bf16 model: the constructor); elsewhere ``_layer`` rounds
 
         def z(*shape, dtype=dtype):
             return torch.zeros(*shape, device=device, dtype=dtype)
 
+        def caches(rows, slots):      # per layer: codes, codes, scales, scales (fp8) or K, V
+            def per_layer(*tail, dtype=dtype):
+                return [z(rows, nkv, slots, *tail, dtype=dtype) for _ in self.layers]
+            if fp8:
+                return (per_layer(hd, dtype=torch.uint8), per_layer(hd, dtype=torch.uint8), per_layer(dtype=torch.float32), per_layer(dtype=torch.float32))
+            return per_layer(hd), per_layer(hd)
+
         def buffers():
             cos, sin = self._rope(tmax, device, dtype)
-            pst = dict(ar=torch.arange(tmax_p, device=device), cos=cos[:tmax_p], sin=sin[:tmax_p], tmax=tmax_p, attn="split" if kernel else None,
-                       kc=[z(B, nkv, tmax_p, hd) for _ in self.layers], vc=[z(B, nkv, tmax_p, hd) for _ in self.layers])
+            pst = dict(ar=torch.arange(tmax_p, device=device), cos=cos[:tmax_p], sin=sin[:tmax_p], tmax=tmax_p,
+                       attn=("split_fp8" if fp8 else "split") if kernel else None)
+            pst.update(zip(("kc8", "vc8", "ks", "vs") if fp8 else ("kc", "vc"), caches(B, tmax_p)))
             if padded:
                 pst.update(key_valid=torch.ones(B, tmax_p, dtype=torch.uint8, device=device), rope_off=z(B, dtype=torch.long))
-            st = dict(tmax=tmax, tmax_g=tmax_g, prompt=pst, attn="beam" if kernel else None,
+            st = dict(tmax=tmax, tmax_g=tmax_g, prompt=pst, attn=("beam_fp8" if fp8 else "beam") if kernel else None,
                       beam=dict(K=K, fill=fill, repetition_penalty=rep_pen, length_penalty=len_pen, kernel=kernel))
             st.update(self._beam_book(B, K, N, device, fill))
             if kernel:
                 V = self.head_w.shape[0]
+                st.update(zip(("kg8", "vg8", "kgs", "vgs") if fp8 else ("kg", "vg"), caches(R, tmax_g)))
                 st.update(cos_full=cos, sin_full=sin, cos=z(tmax_g, hd), sin=z(tmax_g, hd), x=z(R, H), h=z(R, H), q=z(R, HD), a=z(R, HD), act=z(R, inter),
-                          kg=[z(R, nkv, tmax_g, hd) for _ in self.layers], vg=[z(R, nkv, tmax_g, hd) for _ in self.layers],
                           src_row=z(R, tmax_g, dtype=torch.int32), row_id=torch.arange(R, dtype=torch.int32, device=device)[:, None],
                           slot=z(1, dtype=torch.long), nprompt=z(1, dtype=torch.long), rope_off=z(R, dtype=torch.long),
                           attn_ws=z(ops.decode_attention_workspace_bytes(R, self.nh, hd, tmax), dtype=torch.uint8),
@@ -1068,7 +1090,7 @@ class GreedyDecoder(_GraphDecoder):
         """``_emit`` of a beam state: the selection, then the beams' K/V follow their parents -- the ancestry table on the device
         (src_row' = src_row[parent], and the slot the new tokens will be appended at is the row's own), whole caches elsewhere."""
         rows = self._beam_select(st, logits)
-        if st["attn"] == "beam":
+        if st["attn"] in ("beam", "beam_fp8"):
             st["src_row"].copy_(st["src_row"].index_select(0, rows))
             st["src_row"].index_copy_(1, st["step"], st["row_id"])
             st["slot"].add_(1)
@@ -1095,7 +1117,7 @@ class GreedyDecoder(_GraphDecoder):
                               int(first.max()) - lo)
         pst = st["prompt"]
         logits = self._head(self._prefill(pst, inputs_embeds, pmask))      # [B, V]: the prompt runs once per batch item
-        if st["attn"] == "beam":
+        if st["attn"] in ("beam", "beam_fp8"):
             st["cos"].copy_(st["cos_full"][lo: lo + st["tmax_g"]])
             st["sin"].copy_(st["sin_full"][lo: lo + st["tmax_g"]])
             st["rope_off"].copy_((first - lo).repeat_interleave(K).to(dev))
@@ -1171,14 +1193,15 @@ class GreedyDecoder(_GraphDecoder):
         at position ``position_ids[b, P-1] + s`` in cache slot P-1+s, pad keys masked for the whole decode.
         ``num_beams`` > 1: HF's deterministic beam search (``_beam_search``, early_stopping False) with ``length_penalty`` and
         ``repetition_penalty`` -- per batch item the best finished beam, cropped to the longest, finished rows filled with ``pad_token_id or
-        eos_token_id``; greedy only, no stopping criteria, the bf16 K/V cache (NotImplementedError otherwise)."""
+        eos_token_id``; greedy only, no stopping criteria, the bf16 K/V cache -- or the fp8 one of a decoder built with ``fp8_beams=True`` --
+        (NotImplementedError otherwise)."""
         num_beams = int(num_beams)
         if num_beams < 1 or not float(repetition_penalty) > 0.0:
             raise ValueError(f"num_beams={num_beams} / repetition_penalty={repetition_penalty}: at least one beam, a positive penalty")
         if num_beams > 1:
             if do_sample or stop_ids or text_stop is not None:
                 raise NotImplementedError("num_beams > 1 with sampling or stopping criteria: use HF generate")
-            if self.kv_cache != "bf16":
+            if self.kv_cache != "bf16" and not self.fp8_beams:
                 raise NotImplementedError("num_beams > 1 with kv_cache='fp8': use HF generate")
             return self._generate_beams(inputs_embeds, max_new_tokens, use_graph, eos_token_id, pad_token_id, min_new_tokens, attention_mask, num_beams,
                                         1.0 if length_penalty is None else float(length_penalty), float(repetition_penalty))
@@ -1593,12 +1616,13 @@ def keyword_stop_plan(criteria) -> dict:
     return dict(stop_ids=[[int(v) for v in t.tolist()] for c in crit for t in c.keyword_ids], text_stop=text_stop)
 
 
-def make_decoder(lm, weights: str = "bf16", kv_cache: str = "bf16"):
+def make_decoder(lm, weights: str = "bf16", kv_cache: str = "bf16", fp8_beams: bool = False):
     """The graph decoder for a language model: Llama-architecture causal LMs and T5 seq2seq LMs; NotImplementedError otherwise.
-    ``weights``: "bf16", or "fp8" / "mxfp4" (Llama only: GreedyDecoder); ``kv_cache``: "bf16", or "fp8" (likewise)."""
+    ``weights``: "bf16", or "fp8" / "mxfp4" (Llama only: GreedyDecoder); ``kv_cache``: "bf16", or "fp8" (likewise); ``fp8_beams``: GreedyDecoder's
+    (a T5 decoder has no fp8 cache and does not take it)."""
     if getattr(lm.config, "model_type", "") == "t5":
         return T5GreedyDecoder(lm, weights=weights, kv_cache=kv_cache)
-    return GreedyDecoder(lm, weights=weights, kv_cache=kv_cache)
+    return GreedyDecoder(lm, weights=weights, kv_cache=kv_cache, **(dict(fp8_beams=True) if fp8_beams else {}))
 
 
 def prompt_padding(attention_mask: Tensor) -> Tuple[Optional[bool], Tensor]:
@@ -1614,14 +1638,16 @@ def prompt_padding(attention_mask: Tensor) -> Tuple[Optional[bool], Tensor]:
 def decoder_for(owner, lm):
     """The graph decoder for ``lm``, cached on ``owner`` (attribute ``_decoder``): the cached one when it was built for this ``lm`` and the
     weights it re-packed are still the model's (``weights_key``) and in the owner's modes (attributes ``decode_weights`` and ``kv_cache``,
-    "bf16" when it has none), else a new one (``make_decoder``)."""
+    "bf16" when it has none; ``fp8_beams`` = "kv8" in its ``beam_search``), else a new one (``make_decoder``)."""
     mode = check_decode_weights(getattr(owner, "decode_weights", "bf16"))
     kv = check_kv_cache(getattr(owner, "kv_cache", "bf16"))
+    kv8 = "kv8" in check_beam_search(getattr(owner, "beam_search", "hf"))
     dec = getattr(owner, "_decoder", None)
     if (dec is None or dec.lm is not lm or dec.key != weights_key(lm) or getattr(dec, "weights", "bf16") != mode
-            or getattr(dec, "kv_cache", "bf16") != kv):
+            or getattr(dec, "kv_cache", "bf16") != kv or getattr(dec, "fp8_beams", kv8) != kv8):      # (a T5 decoder has no such flag)
         kw = ({} if mode == "bf16" else dict(weights=mode))
         kw.update({} if kv == "bf16" else dict(kv_cache=kv))
+        kw.update(dict(fp8_beams=True) if kv8 else {})
         dec = owner._decoder = make_decoder(lm, **kw)      # (the default modes: the positional lm alone)
     return dec
 
@@ -1658,8 +1684,8 @@ MODULE_ENVELOPE_T5_BEAMS = MODULE_ENVELOPE_BEAMS._replace(t5_beams=True)
 
 def envelope_for(owner, module: bool) -> Envelope:
     """The envelope a caller plans with: today's, or its beam twin when the owner opted in (attribute ``beam_search``, "hf" when it has none;
-    "graph+t5": the twin with ``t5_beams``)."""
-    mode = check_beam_search(getattr(owner, "beam_search", "hf"))
+    "graph+t5": the twin with ``t5_beams``; "+kv8" changes the decoder, not the envelope)."""
+    mode = check_beam_search(getattr(owner, "beam_search", "hf")).replace("+kv8", "")
     if mode == "graph+t5":
         return MODULE_ENVELOPE_T5_BEAMS if module else GENERATE_ENVELOPE_T5_BEAMS
     if module:

@@ -457,7 +457,8 @@ class _LSTPBase(nn.Module):
         those of the model whose K/V are rounded that way, not the reference's; see decode.GreedyDecoder), ``beam_search`` ("hf": requests with
         ``num_beams`` > 1 run on HF generate, as before; "graph" = opt-in: the Llama graph decoder runs HF's deterministic beam search --
         num_beams, repetition_penalty, length_penalty -- on its own kernels, a T5's beam requests stay on HF generate; "graph+t5" = opt-in: that,
-        and the T5 graph decoder of the BLIP-2 flavours does the same; see decode.GreedyDecoder.generate, decode.T5GreedyDecoder.generate)."""
+        and the T5 graph decoder of the BLIP-2 flavours does the same; "graph+kv8" / "graph+t5+kv8" = opt-in: those, and with ``kv_cache="fp8"``
+        the Llama's beams run over the fp8 cache instead of being refused; see decode.GreedyDecoder.generate, decode.T5GreedyDecoder.generate)."""
         super().__init__()
         from .decode import check_beam_search, check_decode_weights, check_kv_cache
         self.decode_weights = check_decode_weights(decode_weights)      # (decode.decoder_for reads it from its owner)

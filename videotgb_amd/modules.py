@@ -182,7 +182,7 @@ class _LSTPLightningBase(_Base):
         from .decode import check_beam_search, check_decode_weights, check_kv_cache
         self.decode_weights = check_decode_weights(decode_weights)      # "fp8": models.LSTP's opt-in decode mode (decode.decoder_for reads it)
         self.kv_cache = check_kv_cache(kv_cache)                        # "fp8": models.LSTP's opt-in K/V cache mode (likewise)
-        self.beam_search = check_beam_search(beam_search)               # "graph" / "graph+t5": models.LSTP's opt-in beam search (decode.graph_generate reads it)
+        self.beam_search = check_beam_search(beam_search)               # "graph" / "graph+t5" (/ "+kv8"): models.LSTP's opt-in beam search (decode.graph_generate reads it)
         if not hasattr(self.hparams, "optimizer"):      # the stand-in base: keep what configure_optimizers reads
             self.hparams.optimizer, self.hparams.scheduler, self.hparams.scheduler_params = optimizer, scheduler, scheduler_params or {}
         self.temperature = temperature

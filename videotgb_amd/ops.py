@@ -626,6 +626,35 @@ def decode_attention_beam(q: Tensor, kp: Tensor, vp: Tensor, kg: Tensor, vg: Ten
     return out
 
 
+def decode_attention_beam_fp8_ok(tmax_p: int, tmax_g: int, hd: int) -> bool:
+    """Whether vtgb_llm_decode_attention_beam_fp8 takes these cache lengths and head_dim (``decode_attention_beam_ok``: the same kernel body)."""
+    return decode_attention_beam_ok(tmax_p, tmax_g, hd)
+
+
+def decode_attention_beam_fp8(q: Tensor, kp8: Tensor, vp8: Tensor, kps: Tensor, vps: Tensor, kg8: Tensor, vg8: Tensor, kgs: Tensor, vgs: Tensor,
+                              src_row: Tensor, n_prompt: Tensor, pos: Tensor, scale: float, key_valid: Optional[Tensor] = None,
+                              out: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
+    """``decode_attention_beam`` over fp8 K/V caches (vtgb_llm_decode_attention_beam_fp8): q [R, nq*hd] bf16; kp8 / vp8 [B, nkv, tmax_p, hd]
+    uint8 (or float8_e4m3fn) codes with kps / vps [B, nkv, tmax_p] fp32 row scales, the prompt cache; kg8 / vg8 [R, nkv, tmax_g, hd] with
+    kgs / vgs [R, nkv, tmax_g], what the beams generated; src_row, n_prompt, pos, key_valid as there.  The result is
+    ``decode_attention_beam`` on the dequantised caches (``dequantize_fp8_kv``), bit for bit."""
+    _need_cuda(q, kp8, vp8, kps, vps, kg8, vg8, kgs, vgs, src_row, n_prompt, pos)
+    B, nkv, tmax_p, hd = kp8.shape
+    R, _, tmax_g, _ = kg8.shape
+    nq = q.numel() // (R * hd)
+    assert R % B == 0 and kg8.shape == (R, nkv, tmax_g, hd) and vp8.shape == kp8.shape and vg8.shape == kg8.shape
+    assert all(t.element_size() == 1 for t in (kp8, vp8, kg8, vg8)) and all(t.dtype == torch.float32 for t in (kps, vps, kgs, vgs))
+    assert kps.shape == vps.shape == (B, nkv, tmax_p) and kgs.shape == vgs.shape == (R, nkv, tmax_g)
+    assert all(t.is_contiguous() for t in (q, kp8, vp8, kps, vps, kg8, vg8, kgs, vgs, src_row))
+    assert src_row.dtype == torch.int32 and src_row.shape == (R, tmax_g) and pos.dtype == torch.int64 and n_prompt.dtype == torch.int64
+    out, workspace = _decode_attention_buffers("decode_attention_beam_fp8", q, R, nq, hd, tmax_p + tmax_g, key_valid, (B, tmax_p), out, workspace)
+    a = L.LlmDecodeAttentionBeamFp8Args(dtype_code(q.dtype), R, R // B, nq, nkv, hd, tmax_p, tmax_g, float(scale), _ptr(q), _ptr(kp8), _ptr(vp8),
+                                        _ptr(kps), _ptr(vps), _ptr(kg8), _ptr(vg8), _ptr(kgs), _ptr(vgs), _ptr(src_row), _ptr(out), _ptr(n_prompt),
+                                        _ptr(pos), _ptr(key_valid), _ptr(workspace))
+    L.check(L.lib().vtgb_llm_decode_attention_beam_fp8(C.byref(a), _stream()))
+    return out
+
+
 def beam_candidates_workspace_bytes(R: int, K: int, V: int) -> int:
     """vtgb_llm_beam_candidates' workspace: the rows' fp32 log-probabilities and their 2 K candidates each."""
     return R * V * 4 + R * 2 * K * 8
