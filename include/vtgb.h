@@ -639,6 +639,36 @@ typedef struct {
 } vtgb_conv_launch_args;
 int vtgb_conv_launch(const vtgb_conv_launch_args* a, vtgb_stream_t stream);
 
+/* Unit-level surface of vtgb_raft_encoder's stem (extractor.py:128-130: 7x7, stride 2, 3 -> 64 channels on x - 127.5 as a bf16 pair) at VTGB_BF16X3 --
+ * also the stem of VTGB_F16C8 -- launched by the function the encoder itself calls (csrc/raft_enc.hip enc_stem_x3), through the caller's workspace.
+ *   variant 1: the fused kernel the encoder launches at the sizes it takes (H, W even, 16 <= W / 2 <= 112, H / 2 >= 4): the packed rows are built in LDS
+ *              from the raw frames and multiplied there (csrc/conv64.hip stem7x7_kernel, split-operand form); VTGB_EUNSUPPORTED for other sizes;
+ *   variant 2: what the encoder launches for fnet (VTGB_CONV_OUT_F32, H/2 * W/2 >= 256, variant 1's sizes): variant 1's rows, and the moments added per
+ *              256-row tile in the order of variant 0's GEMM epilogue by a pass of their own -- variant 0's moments bit for bit;
+ *   variant 0: the route it replaced and the encoder's fallback for other sizes: raft_stem_pack_kernel (a 128-channel hi | lo image in the workspace) +
+ *              the 4 x 1 implicit GEMM over it (+ the pair pass for pair rows).
+ * All accumulate every output element in the same order (bias, then K in the table's order): their fp32 rows are bit-identical.
+ * frames [n_images, 3, H, W] fp32; weights = the encoder table's entry [0] at VTGB_BF16X3, [64, 768] bf16 ([Wh | Wh | Wl] chunks of 4 x 64), bias = [1].
+ * out_kind VTGB_CONV_OUT_F32 (fnet): out = fp32 rows [n_images * H/2 * W/2, 64], moments [n_images, 64, 2] = per image and channel the (sum, sum of
+ *   squares) of the stored values, added in a fixed order (variant 1: per run of rows; variants 0, 2: per 256-row tile -- the last bits of 1 may differ);
+ * VTGB_CONV_OUT_PAIR_BF16 / _PAIR_F16C8 (cnet, BatchNorm folded): out = relu(.) as pair rows [., 128 16-bit units] (vtgb_pair_pack's layout, lo half at unit 64).
+ * VTGB_EINVAL on the host, before any launch, for NULL args, bad dims / variant / out_kind, a NULL operand or one that is not 16-byte aligned;
+ * VTGB_EWORKSPACE for a NULL or short workspace.  What tests/test_gpu_stem_x3.py checks. */
+typedef struct {
+    int32_t n_images, H, W;
+    int32_t variant;            /* 0: pack + implicit GEMM, 1: fused, 2: fused + tile-order moments */
+    int32_t out_kind;           /* VTGB_CONV_OUT_F32, VTGB_CONV_OUT_PAIR_BF16 or VTGB_CONV_OUT_PAIR_F16C8 */
+    const float* images;        /* [n_images, 3, H, W] */
+    const void* weights;        /* [64, 768] bf16 */
+    const float* bias;          /* [64] */
+    void* out;
+    float* moments;             /* VTGB_CONV_OUT_F32: [n_images, 64, 2]; else ignored (may be NULL) */
+    void* workspace;
+    size_t workspace_bytes;
+} vtgb_raft_stem_args;
+size_t vtgb_raft_stem_workspace_bytes(const vtgb_raft_stem_args* a);
+int vtgb_raft_stem(const vtgb_raft_stem_args* a, vtgb_stream_t stream);
+
 /* CorrBlock.__init__ (raft_utils/corr.py:12-27; the all-pairs product :52-60): for every pair the correlation of each
  * pixel of image 1 with every pixel of image 2 over the `dim` = 256 features, divided by sqrt(dim), and its three
  * avg_pool2d(2, stride 2) -- one kernel, the four levels are its only output.  Pair n uses the feature maps of images

@@ -48,6 +48,7 @@ EXPORTS = [
     "vtgb_raft_lookup_convc1", "vtgb_raft_gru_half", "vtgb_llm_lora", "vtgb_conv_launch", "vtgb_attention_cached",
     "vtgb_llm_decode_attention_beam", "vtgb_llm_beam_candidates", "vtgb_llm_attention_rows_beam", "vtgb_llm_decode_attention_beam_fp8",
     "vtgb_pack_skinny_weight_mxfp4_bytes", "vtgb_pack_skinny_weight_mxfp4", "vtgb_gemm_skinny_mxfp4",
+    "vtgb_raft_stem_workspace_bytes", "vtgb_raft_stem",
 ]
 COMM_ID_BYTES = 128
 
@@ -174,6 +175,12 @@ class ConvLaunchArgs(C.Structure):
                 ("Hi", i32), ("Wi", i32), ("C1", i32), ("C2", i32), ("N", i32), ("act", i32), ("post_relu", i32), ("out_scale", f32), ("a", vp), ("a2", vp),
                 ("weights", vp), ("bias", vp), ("out", vp), ("ld_out", i64), ("moments", vp), ("stats_part", vp), ("stats_part_floats", i64), ("resid", vp),
                 ("ld_resid", i64), ("tail_w", vp), ("tail_out", vp)]
+
+
+class RaftStemArgs(C.Structure):
+    """vtgb_raft_stem_args: the encoders' bf16x3 stem alone (variant 0: pack + implicit GEMM, 1: fused) through the caller's workspace."""
+    _fields_ = [("n_images", i32), ("H", i32), ("W", i32), ("variant", i32), ("out_kind", i32), ("images", vp), ("weights", vp), ("bias", vp), ("out", vp),
+                ("moments", vp), ("workspace", vp), ("workspace_bytes", sz)]
 
 
 class RaftCorrArgs(C.Structure):
@@ -315,6 +322,10 @@ def lib() -> C.CDLL:
     L.vtgb_raft_gru_half.restype = C.c_int
     L.vtgb_conv_launch.argtypes = [C.POINTER(ConvLaunchArgs), vp]
     L.vtgb_conv_launch.restype = C.c_int
+    L.vtgb_raft_stem.argtypes = [C.POINTER(RaftStemArgs), vp]
+    L.vtgb_raft_stem.restype = C.c_int
+    L.vtgb_raft_stem_workspace_bytes.argtypes = [C.POINTER(RaftStemArgs)]
+    L.vtgb_raft_stem_workspace_bytes.restype = sz
     L.vtgb_raft_update.argtypes = [C.POINTER(RaftUpdateArgs), vp]
     L.vtgb_raft_update.restype = C.c_int
     L.vtgb_raft_update_workspace_bytes.argtypes = [C.POINTER(RaftUpdateArgs)]

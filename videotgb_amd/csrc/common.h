@@ -252,6 +252,10 @@ bool stem7x7_supported(int H, int W);
 // stats_part: scratch for the per-run partial moments (stats_part_floats(n_img)); the moments land in `stats` [n_img, 64, 2] in a fixed order
 int launch_stem7x7(const float* img, const void* w, const float* bias, float* out_f32, float* stats, float* stats_part, void* out_bf16, int n_img, int H, int W,
                    int relu, hipStream_t s);
+// the same against the bf16x3 table's split weights [64, 768] with the pack + implicit-GEMM route's bits: fp32 rows + moments (out_f32) or
+// relu(.) as pair rows [., 128 16-bit units] (out_pair; h8: f16c8 pairs) -- exactly one of the two; stats == NULL with out_f32: the rows alone
+int launch_stem7x7_x3(const float* img, const void* w, const float* bias, float* out_f32, float* stats, float* stats_part, void* out_pair, int h8, int n_img, int H,
+                      int W, hipStream_t s);
 size_t conv64_stats_part_floats(int n_img);
 // InstanceNorm moments from per-tile / per-part partial sums, added in a fixed order (raft_enc.hip)
 int launch_stats_finish_tiles(const float* part, float* stats, int n_img, int HW, int N, int64_t M, hipStream_t s);

@@ -20,6 +20,7 @@
 // atomic per channel and run -- stored without atomics when a workgroup owns the image), or bf16 output with ReLU / skip + ReLU
 // (cnet, BatchNorm folded into the weights).
 #include "common.h"
+#include "pair_h8.h"
 
 namespace {
 
@@ -251,22 +252,32 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const Conv64Params p) 
 // row ahead of the row whose 4 vertical taps it multiplies; the wave's 32 x 512 weights live in registers (128 VGPRs) as in
 // conv3x3_c64_kernel.  16-byte chunks of a pixel's 256 bytes are XOR-swizzled by (X & 15): the 16 pixels of a fragment read hit 16
 // different chunk positions.
+// X3 (VTGB_BF16X3 / VTGB_F16C8 encoders): the same rows against the table's split weights [Wh | Wh | Wl] (K = 3 chunks x 4 tY x 64), i.e. the
+// contraction [hi | lo | hi] x [Wh | Wh | Wl] of the pack + implicit-GEMM route it replaces, with THAT route's arithmetic per output element:
+// the accumulator starts at the bias and takes one in-order MFMA chain in the GEMM's K order (gemm.hip: 64-channel chunk major, tap minor --
+// hi.Wh over tY = 0..3, then lo.Wh, then hi.Wl, each k-tile as its two 32-deep halves), so the fp32 output has the GEMM's bits.  The wave
+// keeps Wh and Wl of its 32 channels (2 x 8 k-steps x 2 blocks: the 128 VGPRs of the bf16 form's hi | lo table) and reads the hi fragments
+// twice (96 MFMAs per row step on 48 fragment reads: the bf16 form's ratio).  MODE 2 (cnet: BatchNorm folded, no moments) applies ReLU and
+// stores the pair row [hi(64) | lo(64)] -- bf16 pair or f16c8 (pair_h8.h) -- straight from the accumulators: what x3_pair_pass_kernel wrote
+// from the fp32 rows, without the fp32 rows.
 // ---------------------------------------------------------------------------------------
 constexpr int ST_R = 5;
 struct StemParams {
     const float* img;      // [n_img, 3, H, W] raw 0..255 (or CLIP-normalised floats: see raft_enc.hip)
-    const bf16_t* w;       // [64, 512]: k = chunk (hi | lo) * 256 + tY * 64 + (dX * 12 + py * 6 + px * 3 + c)
+    const bf16_t* w;       // [64, 512]: k = chunk (hi | lo) * 256 + tY * 64 + (dX * 12 + py * 6 + px * 3 + c); X3: [64, 768], chunks Wh | Wh | Wl
     const float* bias;
     float* out_f32;        // MODE 0: [n_img * H2 * W2, 64] + moments
     float* stats;
     float* stats_part;
-    bf16_t* out_bf16;      // MODE 1: relu -> bf16
+    bf16_t* out_bf16;      // MODE 1: relu -> bf16; MODE 2: relu -> pair rows [n_img * H2 * W2, 128 16-bit units]
     int n_img, H, W, relu;
     int parts, rows_per_part;
+    int h8;                // MODE 2: f16c8 pair instead of a bf16 pair
 };
 
-template <int MODE>
+template <int MODE, bool X3>
 __global__ __launch_bounds__(512) void stem7x7_kernel(const StemParams p) {
+    static_assert(X3 ? (MODE == 0 || MODE == 2) : (MODE == 0 || MODE == 1), "stem7x7: bf16 stores fp32 / bf16 rows, the split form fp32 / pair rows");
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) char ring[];
     const int tid = threadIdx.x, lane = tid & 63, fr = lane & 15, fg = lane >> 4;
@@ -282,12 +293,14 @@ __global__ __launch_bounds__(512) void stem7x7_kernel(const StemParams p) {
         const int pxl = i >> 2, X = pxl % W2, c = 6 + (i & 1) + ((i & 2) << 2);      // 6, 7, 14, 15
         *reinterpret_cast<uint4*>(ring + pxl * 256 + ((c ^ (X & 15)) << 4)) = make_uint4(0, 0, 0, 0);
     }
-    // ---- weights: 16 k-steps of 32 (s = chunk * 8 + tY * 2 + half) x two 16-channel blocks
+    // ---- weights: 16 k-steps of 32 (s = chunk * 8 + tY * 2 + half) x two 16-channel blocks; X3: chunk = Wh (table chunk 0) | Wl (table chunk 2)
+    constexpr int W_LD = X3 ? 768 : 512;
     bf16x8 wf[16][2];
 #pragma unroll
     for (int s_ = 0; s_ < 16; s_++)
 #pragma unroll
-        for (int i = 0; i < 2; i++) wf[s_][i] = *reinterpret_cast<const bf16x8*>(p.w + (wn * 32 + i * 16 + fr) * 512 + s_ * 32 + fg * 8);
+        for (int i = 0; i < 2; i++)
+            wf[s_][i] = *reinterpret_cast<const bf16x8*>(p.w + (wn * 32 + i * 16 + fr) * W_LD + (X3 ? (s_ >> 3) * 512 + (s_ & 7) * 32 : s_ * 32) + fg * 8);
     // ---- building a packed row: thread = (pixel X, column pair dX): 12 values (2 rows x 2 columns x 3 channels) as hi / lo bf16
     const bool builder = tid < W2 * 4;
     const int bX = tid >> 2, bdX = tid & 3, bcol = 2 * (bX + bdX - 2);        // first of the two input columns
@@ -312,11 +325,12 @@ __global__ __launch_bounds__(512) void stem7x7_kernel(const StemParams p) {
     typedef __attribute__((__vector_size__(2 * sizeof(unsigned)))) unsigned u32x2_t;
     constexpr unsigned OOB = 0x80000000u;
     constexpr int ES = MODE == 0 ? 4 : 2;
+    constexpr int PXU = MODE == 2 ? 128 : 64;             // output elements per pixel (pair rows: hi | lo)
     unsigned o_off[2][2];
 #pragma unroll
     for (int i = 0; i < 2; i++)
 #pragma unroll
-        for (int j = 0; j < 2; j++) o_off[i][j] = px[j] < W2 ? (unsigned)(px[j] * 64 + wn * 32 + i * 16 + fg * 4) * ES : OOB;
+        for (int j = 0; j < 2; j++) o_off[i][j] = px[j] < W2 ? (unsigned)(px[j] * PXU + wn * 32 + i * 16 + fg * 4) * ES : OOB;
 
     const int n_units = p.n_img * p.parts;
     for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
@@ -324,8 +338,8 @@ __global__ __launch_bounds__(512) void stem7x7_kernel(const StemParams p) {
         if (y0 >= H2) continue;
         const int y1 = y0 + p.rows_per_part < H2 ? y0 + p.rows_per_part : H2;
         const float* const ibase = p.img + (int64_t)img * 3 * H * W;
-        const auto orsrc = __builtin_amdgcn_make_buffer_rsrc(MODE == 0 ? (void*)(p.out_f32 + (int64_t)img * H2 * W2 * 64) : (void*)(p.out_bf16 + (int64_t)img * H2 * W2 * 64),
-                                                             0, H2 * W2 * 64 * ES, 0x00020000);
+        const auto orsrc = __builtin_amdgcn_make_buffer_rsrc(MODE == 0 ? (void*)(p.out_f32 + (int64_t)img * H2 * W2 * 64) : (void*)(p.out_bf16 + (int64_t)img * H2 * W2 * PXU),
+                                                             0, H2 * W2 * PXU * ES, 0x00020000);
         float2 ld[6];
         // packed row Yp <- input rows 2 Yp, 2 Yp + 1 (zeros outside the image)
 #define ST_LOAD(Yp)      /* unconditional loads from clamped addresses (conditional ones are serialised by hipcc: one vmcnt(0) each) */ \
@@ -366,44 +380,75 @@ __global__ __launch_bounds__(512) void stem7x7_kernel(const StemParams p) {
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
             ST_LOAD(y + 2)                                     // in flight under this row's MFMAs
-            f32x4 acc[2][2];
-#pragma unroll
-            for (int i = 0; i < 2; i++)
-#pragma unroll
-                for (int j = 0; j < 2; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int tY = 0; tY < 4; tY++) {
-                const char* const rowp = ring + ((y + tY - 2 + ST_R) % ST_R) * row_bytes;
-#pragma unroll
-                for (int hl = 0; hl < 2; hl++)
-#pragma unroll
-                    for (int half = 0; half < 2; half++) {
-                        const int s_ = hl * 8 + tY * 2 + half;
-                        const unsigned cx = (unsigned)((hl * 8 + half * 4) << 4);      // chunk index bits above fg: XORed in (16-byte units)
-                        const bf16x8 x0 = *reinterpret_cast<const bf16x8*>(rowp + (x_off[0] ^ cx));
-                        const bf16x8 x1 = *reinterpret_cast<const bf16x8*>(rowp + (x_off[1] ^ cx));
-#pragma unroll
-                        for (int i = 0; i < 2; i++) {
-                            acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s_][i], x0, acc[i][0], 0, 0, 0);
-                            acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s_][i], x1, acc[i][1], 0, 0, 0);
-                        }
-                    }
+            f32x4 acc[2][2], b4[2];
+            // one 32-deep k-step: the hi (hl = 0) or lo (hl = 1) half-chunk `half` of packed row y + tY - 2 against weight k-step s_
+#define ST_STEP(tY, hl, half, s_)                                                                            \
+            {                                                                                                \
+                const char* const rowp = ring + ((y + (tY) - 2 + ST_R) % ST_R) * row_bytes;                  \
+                const unsigned cx = (unsigned)(((hl) * 8 + (half) * 4) << 4);      /* chunk index bits above fg: XORed in (16-byte units) */ \
+                const bf16x8 x0 = *reinterpret_cast<const bf16x8*>(rowp + (x_off[0] ^ cx));                  \
+                const bf16x8 x1 = *reinterpret_cast<const bf16x8*>(rowp + (x_off[1] ^ cx));                  \
+                _Pragma("unroll") for (int i = 0; i < 2; i++) {                                              \
+                    acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s_][i], x0, acc[i][0], 0, 0, 0);  \
+                    acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s_][i], x1, acc[i][1], 0, 0, 0);  \
+                }                                                                                            \
             }
-            f32x4 b4[2];
+            if constexpr (X3) {
+                // the GEMM's chain: bias first (+ its zero start value), then K in table order -- chunk (hi.Wh, lo.Wh, hi.Wl) major, tY minor
 #pragma unroll
-            for (int i = 0; i < 2; i++) b4[i] = *reinterpret_cast<const f32x4*>(bias_s + wn * 32 + i * 16 + fg * 4);
+                for (int i = 0; i < 2; i++) b4[i] = *reinterpret_cast<const f32x4*>(bias_s + wn * 32 + i * 16 + fg * 4);
+#pragma unroll
+                for (int i = 0; i < 2; i++)
+#pragma unroll
+                    for (int j = 0; j < 2; j++) acc[i][j] = b4[i] + f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+#pragma unroll
+                    for (int tY = 0; tY < 4; tY++)
+#pragma unroll
+                        for (int half = 0; half < 2; half++) ST_STEP(tY, c == 1 ? 1 : 0, half, (c == 2 ? 8 : 0) + tY * 2 + half)
+                    // (fragment reads stay inside their chunk: hoisted across all 24 k-steps they cost 9 spilled registers next to the 128 of the weights)
+                    if (c < 2) __builtin_amdgcn_sched_barrier(0);
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 2; i++)
+#pragma unroll
+                    for (int j = 0; j < 2; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int tY = 0; tY < 4; tY++)
+#pragma unroll
+                    for (int hl = 0; hl < 2; hl++)
+#pragma unroll
+                        for (int half = 0; half < 2; half++) ST_STEP(tY, hl, half, hl * 8 + tY * 2 + half)
+#pragma unroll
+                for (int i = 0; i < 2; i++) b4[i] = *reinterpret_cast<const f32x4*>(bias_s + wn * 32 + i * 16 + fg * 4);
+            }
+#undef ST_STEP
 #pragma unroll
             for (int i = 0; i < 2; i++)
 #pragma unroll
                 for (int j = 0; j < 2; j++) {
                     const bool ok = o_off[i][j] != OOB;
-                    const unsigned off = ok ? o_off[i][j] + (unsigned)(y * W2 * 64 * ES) : OOB;
-                    f32x4 v = acc[i][j] + b4[i];
+                    const unsigned off = ok ? o_off[i][j] + (unsigned)(y * W2 * PXU * ES) : OOB;
+                    f32x4 v = X3 ? acc[i][j] : acc[i][j] + b4[i];
                     if constexpr (MODE == 0) {
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), orsrc, off, 0, 0);
                         const f32x4 vz = {ok ? v[0] : 0.f, ok ? v[1] : 0.f, ok ? v[2] : 0.f, ok ? v[3] : 0.f};
                         s1[i] += vz;
                         s2[i] += vz * vz;
+                    } else if constexpr (MODE == 2) {
+                        if (p.relu) v = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+                        u32x2_t hu, lu;                   // (x3_pair_pass_kernel's split: the pair row it wrote from the fp32 rows)
+                        if (p.h8) {
+                            h8_split4(v, hu, lu);
+                        } else {
+                            bf16x4 hi, lo;
+                            pair_split4(v, hi, lo);
+                            hu = __builtin_bit_cast(u32x2_t, hi); lu = __builtin_bit_cast(u32x2_t, lo);
+                        }
+                        __builtin_amdgcn_raw_buffer_store_b64(hu, orsrc, off, 0, 0);
+                        __builtin_amdgcn_raw_buffer_store_b64(lu, orsrc, ok ? off + 128u : OOB, 0, 0);      // lo half: 64 units further
                     } else {
                         if (p.relu) v = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
                         const bf16x4 pk = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
@@ -414,6 +459,9 @@ __global__ __launch_bounds__(512) void stem7x7_kernel(const StemParams p) {
         }
 #undef ST_LOAD
 #undef ST_WRITE
+        if constexpr (X3) {
+            if (!p.stats) continue;                            // rows only: the caller adds the moments in an association of its own (raft_enc.hip)
+        }
         if constexpr (MODE == 0) {
 #pragma unroll
             for (int i = 0; i < 2; i++)
@@ -486,36 +534,59 @@ int launch_conv3x3_c64(const void* in, const void* w, const float* bias, float* 
     return VTGB_OK;
 }
 
-// the stem on raw frames: img [n_img, 3, H, W] fp32 -> [n_img, H/2, W/2, 64]; packed weights [64, 512] (vtgb.h: vtgb_raft_encoder)
+// the stem on raw frames: img [n_img, 3, H, W] fp32 -> [n_img, H/2, W/2, 64]; packed weights [64, 512] (vtgb.h: vtgb_raft_encoder), x3: the
+// bf16x3 table's [64, 768]; out16: bf16 rows (relu; bf16 form) or pair rows (relu; x3 form, h8: f16c8 instead of bf16 pairs)
 bool stem7x7_supported(int H, int W) { return (H % 2) == 0 && (W % 2) == 0 && W / 2 >= 16 && W / 2 <= 112 && H / 2 >= 4; }
 
-int launch_stem7x7(const float* img, const void* w, const float* bias, float* out_f32, float* stats, float* stats_part, void* out_bf16, int n_img, int H, int W,
-                   int relu, hipStream_t s) {
+static int stem7x7_launch(bool x3, const float* img, const void* w, const float* bias, float* out_f32, float* stats, float* stats_part, void* out16, int h8, int n_img,
+                          int H, int W, int relu, hipStream_t s) {
     VTGB_REQUIRE(stem7x7_supported(H, W), VTGB_EUNSUPPORTED, "stem7x7: %d x %d unsupported", H, W);
     const int H2 = H / 2, W2 = W / 2;
+    VTGB_REQUIRE((int64_t)H2 * W2 * 256 < 0x7FFFFF00ll, VTGB_EUNSUPPORTED, "stem7x7: image too large");
     StemParams p;
-    p.img = img; p.w = (const bf16_t*)w; p.bias = bias; p.out_f32 = out_f32; p.stats = stats; p.stats_part = stats_part; p.out_bf16 = (bf16_t*)out_bf16;
-    p.n_img = n_img; p.H = H; p.W = W; p.relu = relu;
+    p.img = img; p.w = (const bf16_t*)w; p.bias = bias; p.out_f32 = out_f32; p.stats = stats; p.stats_part = stats_part; p.out_bf16 = (bf16_t*)out16;
+    p.n_img = n_img; p.H = H; p.W = W; p.relu = relu; p.h8 = h8;
     int parts = 1;
     while ((int64_t)n_img * parts < 4 * cu_count() && H2 / (parts * 2) >= 14) parts *= 2;
     p.rows_per_part = (H2 + parts - 1) / parts;
     p.parts = (H2 + p.rows_per_part - 1) / p.rows_per_part;
     const int64_t units = (int64_t)n_img * p.parts;
     const int grid = units < cu_count() ? (int)units : cu_count();
-    if (out_f32 && p.parts > 1) VTGB_REQUIRE(stats_part && (size_t)units * 128 <= conv64_stats_part_floats(n_img), VTGB_EINVAL, "stem7x7: partial-moment scratch missing");
+    if (out_f32 && stats && p.parts > 1)
+        VTGB_REQUIRE(stats_part && (size_t)units * 128 <= conv64_stats_part_floats(n_img), VTGB_EINVAL, "stem7x7: partial-moment scratch missing");
     const int lds = ST_R * W2 * 256 + 8 * 32 * 2 * 4 + 64 * 4;
-    const double flops = 2.0 * n_img * H2 * W2 * 64.0 * 147.0, exec = 2.0 * n_img * H2 * W2 * 64.0 * 512.0;
+    constexpr int lds_max = ST_R * 112 * 256 + 8 * 32 * 2 * 4 + 64 * 4;
+    const double flops = 2.0 * n_img * H2 * W2 * 64.0 * 147.0, exec = 2.0 * n_img * H2 * W2 * 64.0 * (x3 ? 768.0 : 512.0);
     ProfScope prof(VTGB_PROF_CONV, flops, s, exec);
-    static DeviceOnce a0, a1;
+    static DeviceOnce a0, a1, a2, a3;
     if (out_f32) {
-        VTGB_REQUIRE(stats, VTGB_EINVAL, "stem7x7: fp32 output needs the moments buffer");
-        VTGB_FUNC_LDS_ONCE(a0, stem7x7_kernel<0>, ST_R * 112 * 256 + 8 * 32 * 2 * 4 + 64 * 4);
-        hipLaunchKernelGGL(stem7x7_kernel<0>, dim3(grid), dim3(512), lds, s, p);
-        if (p.parts > 1) VTGB_TRY(launch_stats_finish_parts(stats_part, stats, n_img, p.parts, 64, s));
+        VTGB_REQUIRE(stats || x3, VTGB_EINVAL, "stem7x7: fp32 output needs the moments buffer");      // (x3: NULL = rows only)
+        if (x3) {
+            VTGB_FUNC_LDS_ONCE(a2, (stem7x7_kernel<0, true>), lds_max);
+            hipLaunchKernelGGL((stem7x7_kernel<0, true>), dim3(grid), dim3(512), lds, s, p);
+        } else {
+            VTGB_FUNC_LDS_ONCE(a0, (stem7x7_kernel<0, false>), lds_max);
+            hipLaunchKernelGGL((stem7x7_kernel<0, false>), dim3(grid), dim3(512), lds, s, p);
+        }
+        if (stats && p.parts > 1) VTGB_TRY(launch_stats_finish_parts(stats_part, stats, n_img, p.parts, 64, s));
+    } else if (x3) {
+        VTGB_FUNC_LDS_ONCE(a3, (stem7x7_kernel<2, true>), lds_max);
+        hipLaunchKernelGGL((stem7x7_kernel<2, true>), dim3(grid), dim3(512), lds, s, p);
     } else {
-        VTGB_FUNC_LDS_ONCE(a1, stem7x7_kernel<1>, ST_R * 112 * 256 + 8 * 32 * 2 * 4 + 64 * 4);
-        hipLaunchKernelGGL(stem7x7_kernel<1>, dim3(grid), dim3(512), lds, s, p);
+        VTGB_FUNC_LDS_ONCE(a1, (stem7x7_kernel<1, false>), lds_max);
+        hipLaunchKernelGGL((stem7x7_kernel<1, false>), dim3(grid), dim3(512), lds, s, p);
     }
     VTGB_HIP(hipGetLastError());
     return VTGB_OK;
+}
+
+int launch_stem7x7(const float* img, const void* w, const float* bias, float* out_f32, float* stats, float* stats_part, void* out_bf16, int n_img, int H, int W,
+                   int relu, hipStream_t s) {
+    return stem7x7_launch(false, img, w, bias, out_f32, stats, stats_part, out_bf16, 0, n_img, H, W, relu, s);
+}
+// the split-operand form: fp32 rows + moments (out_f32; fnet) or relu(.) as pair rows (out_pair; cnet)
+int launch_stem7x7_x3(const float* img, const void* w, const float* bias, float* out_f32, float* stats, float* stats_part, void* out_pair, int h8, int n_img, int H,
+                      int W, hipStream_t s) {
+    VTGB_REQUIRE((out_f32 != nullptr) != (out_pair != nullptr), VTGB_EINVAL, "stem7x7 x3: exactly one of the fp32 rows and the pair rows");
+    return stem7x7_launch(true, img, w, bias, out_f32, stats, stats_part, out_pair, h8, n_img, H, W, out_pair ? 1 : 0, s);
 }

@@ -23,6 +23,16 @@ constexpr float H8_LO_SCALE = 2048.0f;       // 2^11: |x - fp16(x)| 2^11 <= |x|,
 constexpr float H8_MAX = 57344.0f;           // largest finite e5m2
 
 #if defined(__HIPCC__)
+// fp32 x 4 -> the bf16 pair of the VTGB_BF16X3 mode (raft_x3.hip): hi = bf16(v), lo = bf16(v - hi); shared by the pair pass and the epilogues that
+// write either format
+__device__ __forceinline__ void pair_split4(const f32x4 v, bf16x4& hi, bf16x4& lo) {
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        const float hf = bf16_round(v[e]);
+        hi[e] = (bf16_t)hf;
+        lo[e] = (bf16_t)(v[e] - hf);
+    }
+}
 // fp32 x 4 -> (hi: 4 fp16, lo: 4 e5m2 residuals | 4 e5m2 values)
 __device__ __forceinline__ void h8_split4(f32x4 v, h8_u32x2& hi, h8_u32x2& lo) {
 #pragma unroll

@@ -155,6 +155,54 @@ int launch_stats_finish_tiles(const float* part, float* stats, int n_img, int HW
     return VTGB_OK;
 }
 
+// ---- the per-tile slots of fp32 rows x [M, 64] that were NOT written by the implicit GEMM, in the association of its epilogue (gemm.hip, EPI_STORE_F32 +
+// col_stats on the 256 x 64 tile: wave wm owns rows 32 wm .. 32 wm + 31 of the tile, lane (rl, cl) adds rows 4 rr + rl, rr = 0..7, of columns 4 cl .. 4 cl + 3
+// in that order, split by image; the four row groups fold by xor 16, xor 32; 64 threads add the waves' partials in wave order) -- the same additions in the same
+// order, so launch_stats_finish_tiles gives the moments the GEMM route gives, bit for bit.  For the fused bf16x3 stem of fnet: its rows have the GEMM's bits, and
+// with these moments so has everything behind it (a per-run association moved the normalised features by an ulp, and one TGB frame selection of the
+// benchmark's 124 clips with them).  One workgroup per 256-row tile; a pass over the rows at HBM rate.
+__global__ __launch_bounds__(512) void stats_tiles_c64_kernel(const float* __restrict__ x, float* __restrict__ part, int M, int stats_rows) {
+    __shared__ f32x4 pr[8][64];
+    const int tid = threadIdx.x, lane = tid & 63, wm = tid >> 6, rl = lane >> 4, cl = lane & 15;
+    const int mt = blockIdx.x, m0 = mt * 256;
+    const int img_a = m0 / stats_rows, m_b = (img_a + 1) * stats_rows;      // first row of image b
+    f32x4 sa = {0.f, 0.f, 0.f, 0.f}, qa = sa, sb = sa, qb = sa;
+    f32x4 vv[8];
+#pragma unroll
+    for (int rr = 0; rr < 8; rr++) {
+        const int m = m0 + wm * 32 + rr * 4 + rl;
+        vv[rr] = m < M ? *reinterpret_cast<const f32x4*>(x + (int64_t)m * 64 + cl * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int rr = 0; rr < 8; rr++) {
+        const f32x4 v = vv[rr];
+        const int m = m0 + wm * 32 + rr * 4 + rl;
+        if (m < M) {
+            if (m < m_b) { sa += v; qa += v * v; }
+            else { sb += v; qb += v * v; }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        sa[e] += __shfl_xor(sa[e], 16); sa[e] += __shfl_xor(sa[e], 32);
+        qa[e] += __shfl_xor(qa[e], 16); qa[e] += __shfl_xor(qa[e], 32);
+        sb[e] += __shfl_xor(sb[e], 16); sb[e] += __shfl_xor(sb[e], 32);
+        qb[e] += __shfl_xor(qb[e], 16); qb[e] += __shfl_xor(qb[e], 32);
+    }
+    if (rl == 0) { pr[wm][cl] = sa; pr[wm][16 + cl] = qa; pr[wm][32 + cl] = sb; pr[wm][48 + cl] = qb; }
+    __syncthreads();
+    if (tid < 64) {
+        float t[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int wm_ = 0; wm_ < 8; wm_++) {
+            if (m0 + wm_ * 32 >= M) break;
+            const float* w_ = reinterpret_cast<const float*>(pr[wm_]);
+#pragma unroll
+            for (int e = 0; e < 4; e++) t[e] += w_[e * 64 + tid];
+        }
+        *reinterpret_cast<float4*>(part + ((int64_t)mt * 64 + tid) * 4) = make_float4(t[0], t[1], t[2], t[3]);
+    }
+}
+
 // ---- y = [relu]((x - mean) * rstd); out = [relu](resid + y); bf16 NHWC with Cpad channels (pad = 0).
 // mean = sum / HW, rstd = 1 / sqrt(biased var + 1e-5) from the accumulated moments; 4 channels per thread.
 // r4: a workgroup belongs to ONE image (blockIdx.y) and a thread keeps its four channels over NA_PASS pixels: the statistics are
@@ -222,6 +270,44 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const float* __restrict
 // (enc_conv / enc_stem_conv, the builders of this file's convolution launches: conv_descs.h)
 int launch_x3_pair_pass(const float* x, int64_t ldx, const float* stats, int HW, const void* resid, int64_t ldr, int r_lo, void* out, int64_t ldo, int o_lo,
                         int C, int Cpad, int relu_in, int relu_out, int64_t M, hipStream_t s, int h8 = 0, int resid_h8 = 0);   // raft_x3.hip
+
+// ---- the stem at VTGB_BF16X3 (and under VTGB_F16C8, whose stem stays bf16x3) -- the ONE place that builds these launches (enc_impl and the unit entry
+// vtgb_raft_stem).  fnet (pair == NULL): fp32 rows cf [M2, 64] + the InstanceNorm moments, complete in `stats`; cnet (BatchNorm folded: no moments):
+// relu(.) as pair rows [M2, 128 16-bit units], bf16 pairs or (h8) f16c8.
+//   variant 1: conv64.hip's stem7x7_kernel in its split-operand form, on the raw frames (stem7x7_supported sizes);
+//   variant 2 (fnet, images of >= 256 pixels): variant 1's rows without its moments + stats_tiles_c64_kernel: the moments per 256-row tile, variant 0's bits;
+//   variant 0: raft_stem_pack_kernel (a 128-channel hi | lo image, 256 B per half-resolution pixel, into `packed`) + the 4 x 1 implicit GEMM that reads it
+//              back as [hi | lo | hi] x [Wh | Wh | Wl] (+ per-tile moments, or the separate pass below 256 pixels per image); cnet: fp32 rows to cf, then the pair pass.
+// All give the same fp32 convolution bits (conv64.hip); fnet's moments are added per run of rows (1) or per 256-row tile (0, 2).
+struct StemX3 {
+    const float* images; const void* w; const float* bias;
+    int n, H, W;
+    float* cf; float* stats; float* spart;
+    void* pair; int h8;
+    void* packed; void* pad_page;      // variant 0 only
+};
+static int enc_stem_x3(const StemX3& t, int variant, hipStream_t s) {
+    const int H2 = t.H / 2, W2 = t.W / 2, HW = H2 * W2;
+    const int64_t M2 = (int64_t)t.n * HW;
+    if (variant == 1) return launch_stem7x7_x3(t.images, t.w, t.bias, t.pair ? nullptr : t.cf, t.stats, t.spart, t.pair, t.h8, t.n, t.H, t.W, s);
+    if (variant == 2) {      // fnet in production: the fused rows, then the moments in the GEMM epilogue's association (variant 0's bits)
+        VTGB_REQUIRE(!t.pair && HW >= 256, VTGB_EINVAL, "raft_stem: tile-order moments belong to fp32 rows of images of >= 256 pixels");
+        VTGB_TRY(launch_stem7x7_x3(t.images, t.w, t.bias, t.cf, nullptr, nullptr, nullptr, 0, t.n, t.H, t.W, s));
+        hipLaunchKernelGGL(stats_tiles_c64_kernel, dim3((unsigned)((M2 + 255) / 256)), dim3(512), 0, s, t.cf, t.spart, (int)M2, HW);
+        return launch_stats_finish_tiles(t.spart, t.stats, t.n, HW, 64, M2, s);
+    }
+    hipLaunchKernelGGL(raft_stem_pack_kernel<bf16_t>, dim3((unsigned)((M2 * 4 + 255) / 256)), dim3(256), 0, s, t.images, (bf16_t*)t.packed, (bf16_t*)t.pad_page, M2, t.H,
+                       t.W);
+    float* sf = (!t.pair && HW >= 256) ? t.spart : nullptr;      // (smaller images: the two-images-per-tile bookkeeping of the epilogue does not hold)
+    GemmDesc d = enc_stem_conv(VTGB_BF16X3, (int)M2, 64, H2, W2, 64, t.packed, t.w, t.bias, t.cf, 64, t.pad_page, sf);      // the packed image read as a pair of 64
+    d.algo_flops = 2.0 * (double)M2 * 64 * 147;
+    VTGB_TRY(launch_conv_gemm(d, s));
+    if (t.pair) return launch_x3_pair_pass(t.cf, 64, nullptr, HW, nullptr, 128, 64, t.pair, 128, 64, 64, 64, 1, 0, M2, s, t.h8);
+    if (sf) return launch_stats_finish_tiles(sf, t.stats, t.n, HW, 64, M2, s);
+    const int splits = HW >= 4096 ? 16 : HW >= 1024 ? 4 : 1;
+    hipLaunchKernelGGL(inorm_stats_kernel, dim3(t.n, splits), dim3(256), 0, s, t.cf, t.spart, HW, 64, 64);
+    return launch_stats_finish_parts(t.spart, t.stats, t.n, splits, 64, s);
+}
 
 static int enc_impl(const vtgb_raft_encoder_args* a, Workspace& ws, hipStream_t s) {
     VTGB_REQUIRE(a, VTGB_EINVAL, "raft_encoder: NULL args");
@@ -310,6 +396,13 @@ static int enc_impl(const vtgb_raft_encoder_args* a, Workspace& ws, hipStream_t 
         } else {
             VTGB_TRY(launch_stem7x7(a->images, w[0], F(w[1]), nullptr, nullptr, nullptr, act0, n, a->H, a->W, 1, s));     // relu(bn1(conv1(x))) straight to bf16
         }
+    } else if (x3) {
+        // bf16x3 / f16c8: the same kernel in its split-operand form (the GEMM route's bits; no packed image, and for cnet neither cf nor a pair pass);
+        // other sizes: pack + implicit GEMM.  fnet keeps its pair pass behind the stem: it needs the moments of the whole image
+        const StemX3 t{a->images, w[0], F(w[1]), n, a->H, a->W, cf, stats, spart, inorm ? nullptr : act0, h8l1, act1, pad_page};
+        // (fnet: variant 2 -- the moments re-added per 256-row tile, so that the features keep the bits the GEMM route gave them)
+        VTGB_TRY(enc_stem_x3(t, stem_on && stem7x7_supported(a->H, a->W) ? (inorm ? 2 : 1) : 0, s));
+        if (inorm) VTGB_TRY(norm(cf, M2, H2 * W2, 64, 64, 64, nullptr, act0, 1, 0, stats, true, h8l1));      // (f16c8: layer1 reads f16c8 pairs)
     } else {
         if (dt != VTGB_F32)
             hipLaunchKernelGGL(raft_stem_pack_kernel<bf16_t>, dim3((unsigned)((M2 * 4 + 255) / 256)), dim3(256), 0, s, a->images, (bf16_t*)act1, (bf16_t*)pad_page, M2,
@@ -319,12 +412,11 @@ static int enc_impl(const vtgb_raft_encoder_args* a, Workspace& ws, hipStream_t 
                                a->H, a->W);
         {
             float* sf = stats_for(stats, H2 * W2, 64);
-            const int cp = dt == VTGB_BF16 ? 128 : 64;            // bf16: hi | lo chunks (raft_stem_pack_kernel); bf16x3: the same image read as a pair of 64
+            const int cp = dt == VTGB_BF16 ? 128 : 64;            // bf16: hi | lo chunks (raft_stem_pack_kernel)
             GemmDesc d = enc_stem_conv(dt, (int)M2, 64, H2, W2, cp, act1, w[0], F(w[1]), cf, 64, pad_page, sf);
-            if (x3) d.algo_flops = 2.0 * (double)M2 * 64 * 147;
-            if (!inorm && !x3) { d.epi = VTGB_EPI_STORE; d.act = 1; d.out = act0; }        // relu(bn1(conv1(x))) straight to bf16
+            if (!inorm) { d.epi = VTGB_EPI_STORE; d.act = 1; d.out = act0; }        // relu(bn1(conv1(x))) straight to bf16
             VTGB_TRY(conv_stats(d, stats));
-            if (inorm || x3) VTGB_TRY(norm(cf, M2, H2 * W2, 64, 64, 64, nullptr, act0, 1, 0, stats, sf != nullptr, h8l1));      // (f16c8: layer1 reads f16c8 pairs)
+            if (inorm) VTGB_TRY(norm(cf, M2, H2 * W2, 64, 64, 64, nullptr, act0, 1, 0, stats, sf != nullptr));
         }
     }
     // ---- six residual blocks
@@ -503,6 +595,53 @@ static int enc_impl(const vtgb_raft_encoder_args* a, Workspace& ws, hipStream_t 
         VTGB_TRY(launch_conv_gemm(d, s));
     }
     return VTGB_OK;
+}
+
+// ---- unit-level entry point of the bf16x3 stem (include/vtgb.h: vtgb_raft_stem): enc_stem_x3 on the caller's buffers
+static int stem_unit_impl(const vtgb_raft_stem_args* a, Workspace& ws, hipStream_t s) {
+    VTGB_REQUIRE(a, VTGB_EINVAL, "raft_stem: NULL args");
+    VTGB_REQUIRE(a->n_images > 0 && a->H >= 2 && a->W >= 2 && (a->H % 2) == 0 && (a->W % 2) == 0 && a->variant >= 0 && a->variant <= 2, VTGB_EINVAL,
+                 "raft_stem: bad dims n=%d H=%d W=%d variant=%d", a->n_images, a->H, a->W, a->variant);
+    const int ok = a->out_kind;
+    VTGB_REQUIRE(ok == VTGB_CONV_OUT_F32 || ok == VTGB_CONV_OUT_PAIR_BF16 || ok == VTGB_CONV_OUT_PAIR_F16C8, VTGB_EINVAL,
+                 "raft_stem: bad out_kind %d (VTGB_CONV_OUT_F32, _PAIR_BF16 or _PAIR_F16C8)", ok);
+    VTGB_REQUIRE(a->variant == 0 || stem7x7_supported(a->H, a->W), VTGB_EUNSUPPORTED, "raft_stem: the fused stem does not take %d x %d frames (variant 0 does)", a->H, a->W);
+    const bool pair = ok != VTGB_CONV_OUT_F32;
+    VTGB_REQUIRE(a->variant != 2 || (!pair && (a->H / 2) * (a->W / 2) >= 256), VTGB_EINVAL,
+                 "raft_stem: variant 2 (tile-order moments) belongs to fp32 rows of images of >= 256 half-resolution pixels");
+    const int n = a->n_images;
+    const int64_t M2 = (int64_t)n * (a->H / 2) * (a->W / 2);
+    VTGB_REQUIRE(M2 < (1ll << 31), VTGB_EUNSUPPORTED, "raft_stem: too many pixels per call (chunk the images)");
+    void* packed = a->variant == 0 ? ws.take(M2 * 128 * 2) : nullptr;
+    float* cf = a->variant == 0 && pair ? (float*)ws.take(M2 * 64 * 4) : nullptr;
+    size_t part_floats = (size_t)(M2 / 256 + 2) * 128 * 4;      // (the encoders' sizing)
+    if (conv64_stats_part_floats(n) > part_floats) part_floats = conv64_stats_part_floats(n);
+    if ((size_t)n * 16 * 128 * 2 > part_floats) part_floats = (size_t)n * 16 * 128 * 2;
+    float* spart = pair ? nullptr : (float*)ws.take(part_floats * 4);
+    void* pad_page = ws.take(256);
+    if (ws.dry) return VTGB_OK;
+    VTGB_REQUIRE(ws.ok(), VTGB_EWORKSPACE, "raft_stem: workspace %zu < %zu bytes", ws.size, ws.used);
+    VTGB_REQUIRE(a->images && a->weights && a->bias && a->out && (pair || a->moments), VTGB_EINVAL, "raft_stem: NULL operand (moments belong to the fp32 rows)");
+    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    VTGB_REQUIRE(al16(a->images) && al16(a->weights) && al16(a->bias) && al16(a->out) && (pair || al16(a->moments)) && al16(a->workspace), VTGB_EINVAL,
+                 "raft_stem: misaligned operand (16 bytes)");
+    const StemX3 t{a->images, a->weights, a->bias, n, a->H, a->W, pair ? cf : (float*)a->out, a->moments, spart, pair ? a->out : nullptr,
+                   ok == VTGB_CONV_OUT_PAIR_F16C8, packed, pad_page};
+    return enc_stem_x3(t, a->variant, s);
+}
+extern "C" size_t vtgb_raft_stem_workspace_bytes(const vtgb_raft_stem_args* a) {
+    Workspace ws(nullptr, 0);
+    if (stem_unit_impl(a, ws, nullptr) != VTGB_OK) return 0;
+    return align_up(ws.used, 256);
+}
+extern "C" int vtgb_raft_stem(const vtgb_raft_stem_args* a, vtgb_stream_t stream) {
+    VTGB_REQUIRE(a, VTGB_EINVAL, "raft_stem: NULL args");
+    // (a NULL workspace would read as a size query: the checks that do not need it run first, then it is refused)
+    Workspace probe(nullptr, 0);
+    VTGB_TRY(stem_unit_impl(a, probe, nullptr));
+    VTGB_REQUIRE(a->workspace, VTGB_EWORKSPACE, "raft_stem: workspace is NULL (%zu bytes needed)", align_up(probe.used, 256));
+    Workspace ws(a->workspace, a->workspace_bytes);
+    return stem_unit_impl(a, ws, (hipStream_t)stream);
 }
 
 extern "C" size_t vtgb_raft_encoder_workspace_bytes(const vtgb_raft_encoder_args* a) {

@@ -31,14 +31,7 @@ int raft_launch_lookup_convc1_h8(const CorrPyr& pyr, const float* flow, const vo
 int raft_launch_flow_head2(const float* P2, const float* bias, float* flow, int n_pairs, int H8, int W8, hipStream_t s);
 int raft_launch_upsample(const float* flow, const float* mask, float* flow_up, int n_pairs, int H8, int W8, hipStream_t s);
 
-__device__ __forceinline__ void pair_split4(const f32x4 v, bf16x4& hi, bf16x4& lo) {
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-        const float hf = bf16_round(v[e]);
-        hi[e] = (bf16_t)hf;
-        lo[e] = (bf16_t)(v[e] - hf);
-    }
-}
+// (pair_split4, fp32 x 4 -> the bf16 pair: pair_h8.h, next to its f16c8 sibling)
 __device__ __forceinline__ f32x4 pair_join4(const bf16x4 hi, const bf16x4 lo) {
     return f32x4{(float)hi[0] + (float)lo[0], (float)hi[1] + (float)lo[1], (float)hi[2] + (float)lo[2], (float)hi[3] + (float)lo[3]};
 }

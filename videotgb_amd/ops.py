@@ -1526,6 +1526,64 @@ def raft_corr(fmap: Tensor, n_pairs: int, H8: int, W8: int, pairs_per_clip: int,
     return lv
 
 
+def raft_stem_pack(w: Tensor, code: int) -> Tensor:
+    """The stem's weight [64, 3, 7, 7] fp32 (BatchNorm already folded for cnet) -> entry [0] of vtgb_raft_encoder's table as fp32 values [64, K]: the stem
+    as a 4x1 convolution over the space-to-depth image (raft_enc.hip): [co][tY][dX, py, px, c | pad to 64], ky = 2 tY + py - 1, kx = 2 dX + px - 1.  fp32
+    mode: the kernel packs 2*(x/255)-1 itself, weights as they are.  bf16 mode: the kernel packs x - 127.5 as a bf16 pair (hi | lo channel chunks), so
+    w' = w * 2/255 in BOTH chunks.  bf16x3 / f16c8: w' as the blocks [Wh | Wh | Wl]."""
+    w = w.float()
+    if code != F32:
+        w = w * (2.0 / 255.0)
+    wp = torch.zeros(64, 4, 4, 2, 2, 3, dtype=torch.float32, device=w.device)
+    for tY in range(4):
+        for py in range(2):
+            ky = 2 * tY + py - 1
+            if ky < 0:
+                continue
+            for dX in range(4):
+                for px in range(2):
+                    kx = 2 * dX + px - 1
+                    if kx >= 0:
+                        wp[:, tY, dX, py, px, :] = w[:, :, ky, kx]
+    wp = torch.nn.functional.pad(wp.reshape(64, 4, 48), (0, 16))                    # [co, tY, 64]
+    if code == BF16:
+        wp = torch.stack([wp, wp], 1)                                               # K order: 64-channel chunk major, tap minor
+    if code in (BF16X3, F16C8):                                                     # [co, tY, 1, 64] -> blocks [Wh | Wh | Wl], K order
+        wp = conv_k_order(split3(wp.reshape(64, 4, 1, 64)))
+    return wp.reshape(64, -1).contiguous()
+
+
+def raft_stem(images: Tensor, w: Tensor, bias: Tensor, variant: int = 1, out_kind: int = L.CONV_OUT_F32, out: Optional[Tensor] = None,
+              workspace: Optional[Tensor] = None):
+    """The encoders' stem at bf16x3 / f16c8 alone (include/vtgb.h vtgb_raft_stem): images [n, 3, H, W] fp32, w [64, 3, 7, 7] fp32 (packed here by
+    raft_stem_pack, as the encoder table packs it), bias [64].  variant 1: the fused kernel, 0: pack + implicit GEMM, 2 (fp32 rows only): the fused kernel + the moments added in variant 0's order, what
+    the encoder launches for fnet.  out_kind CONV_OUT_F32 -> (fp32 rows
+    [n * H/2 * W/2, 64], moments [n, 64, 2]); CONV_OUT_PAIR_BF16 / CONV_OUT_PAIR_F16C8 -> relu(.) as int16 pair rows [., 128].  ``out``: write the rows into
+    the head of this contiguous tensor instead of a fresh one; ``workspace``: a uint8 tensor to use as the scratch (at least the size the library asks for)."""
+    _need_cuda(images)
+    dev = images.device
+    images = images.contiguous().float()
+    n, _, H, W = images.shape
+    M2 = n * (H // 2) * (W // 2)
+    pair = out_kind != L.CONV_OUT_F32
+    packed = _bf16_exact(raft_stem_pack(w.to(dev), BF16X3))
+    bias_t = bias.to(dev).contiguous().float()
+    if out is None:
+        out = torch.empty(M2, 128, dtype=torch.int16, device=dev) if pair else torch.empty(M2, 64, dtype=torch.float32, device=dev)
+    assert out.is_contiguous() and out.numel() >= M2 * (128 if pair else 64) and out.dtype == (torch.int16 if pair else torch.float32)
+    moments = None if pair else torch.empty(n, 64, 2, dtype=torch.float32, device=dev)
+    a = L.RaftStemArgs(n, H, W, variant, out_kind, images.data_ptr(), packed.data_ptr(), bias_t.data_ptr(), out.data_ptr(), _ptr(moments), None, 0)
+    need = L.lib().vtgb_raft_stem_workspace_bytes(C.byref(a))
+    if need == 0:
+        L.check(L.lib().vtgb_raft_stem(C.byref(a), _stream()))   # raises with the library's message
+    ws = workspace if workspace is not None else _ws.get(need, dev)
+    assert ws.numel() >= need
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    L.check(L.lib().vtgb_raft_stem(C.byref(a), _stream()))
+    torch.cuda.current_stream().synchronize()      # (packed / bias_t are temporaries of this call)
+    return out if pair else (out, moments)
+
+
 class RaftEncoderWeights(_WeightTable):
     """of_extractor.{fnet,cnet}.* -> the packed table of vtgb_raft_encoder.  batch_norm=True folds the eval-mode
     BatchNorm2d that follows each convolution (extractor.py:20-24,124) into the convolution's weight and bias."""
@@ -1569,25 +1627,7 @@ class RaftEncoderWeights(_WeightTable):
         # ky = 2 tY + py - 1, kx = 2 dX + px - 1.  fp32 mode: the kernel packs 2*(x/255)-1 itself, weights as they are.
         # bf16 mode: the kernel packs x - 127.5 as a bf16 pair (hi | lo channel chunks), so w' = w * 2/255 in BOTH chunks, b' = b
         w, b = folded("conv1", "norm1")
-        if code != F32:
-            w = w * (2.0 / 255.0)
-        wp = torch.zeros(64, 4, 4, 2, 2, 3, dtype=torch.float32, device=w.device)
-        for tY in range(4):
-            for py in range(2):
-                ky = 2 * tY + py - 1
-                if ky < 0:
-                    continue
-                for dX in range(4):
-                    for px in range(2):
-                        kx = 2 * dX + px - 1
-                        if kx >= 0:
-                            wp[:, tY, dX, py, px, :] = w[:, :, ky, kx]
-        wp = torch.nn.functional.pad(wp.reshape(64, 4, 48), (0, 16))                    # [co, tY, 64]
-        if code == BF16:
-            wp = torch.stack([wp, wp], 1)                                               # K order: 64-channel chunk major, tap minor
-        if x3:                                                                          # [co, tY, 1, 64] -> blocks [Wh | Wh | Wl], K order
-            wp = conv_k_order(split3(wp.reshape(64, 4, 1, 64)))
-        self.add(wp.reshape(64, -1).contiguous(), True); self.add(b)
+        self.add(raft_stem_pack(w, code), True); self.add(b)
         cin_pad = 64
         for l, (li, c, cpad) in enumerate((("layer1", 64, 64), ("layer2", 96, 128), ("layer3", 128, 128))):
             for bi in range(2):
