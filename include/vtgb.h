@@ -1017,6 +1017,19 @@ typedef struct {
 } vtgb_llm_lora_args;
 int vtgb_llm_lora(const vtgb_llm_lora_args* a, vtgb_stream_t stream);
 
+/* The same update on a projection whose K-split reduce was deferred (vtgb_gemm_skinny with defer_reduce and S = n_splits > 1; added at
+ *   version 601 without a bump): ONE launch adds the fragments and applies the adapters.  `a->x` is bf16 [rows <= 128, K]; `a->y` is
+ *   bf16 [rows, n_cols] and is WRITTEN, NOT READ; `part` holds the fragments workspace[(tile * n_splits + split) * rows + m][128] of the
+ *   [rows, n_cols] projection (the layout stated at vtgb_gemm_skinny_args.defer_reduce).  For every column j:
+ *       base = rnd_bf16(0 + part[.. split 0 ..] + part[.. split 1 ..] + ...)     in split order: what the reduce launch stores
+ *       y    = base                                        outside every segment
+ *       y    = rnd(base + rnd(u * scaling))                inside a segment, t and u formed by the sums of vtgb_llm_lora
+ *   so the result equals vtgb_gemm_skinny (reduced) followed by vtgb_llm_lora, bit for bit, for every row count, split count, rank and
+ *   segment placement; a row's bits do not depend on the other rows.  No atomics, no workspace of its own.  Checked on the host before any
+ *   launch: vtgb_llm_lora's checks; VTGB_EINVAL for a dtype other than VTGB_BF16, rows > 128, n_splits outside 2 .. 64, NULL part;
+ *   VTGB_EUNSUPPORTED for a part that is not 4-byte aligned (the fragments are read one float per lane). */
+int vtgb_llm_lora_parts(const vtgb_llm_lora_args* a, const float* part, int32_t n_splits, vtgb_stream_t stream);
+
 size_t vtgb_pack_skinny_weight_bytes(int32_t N, int32_t K);
 int vtgb_pack_skinny_weight(const void* w, int64_t ldw, int32_t N, int32_t K, void* dst, vtgb_stream_t stream);
 size_t vtgb_gemm_skinny_workspace_bytes(const vtgb_gemm_skinny_args* a);

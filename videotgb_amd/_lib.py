@@ -48,7 +48,7 @@ EXPORTS = [
     "vtgb_raft_lookup_convc1", "vtgb_raft_gru_half", "vtgb_llm_lora", "vtgb_conv_launch", "vtgb_attention_cached",
     "vtgb_llm_decode_attention_beam", "vtgb_llm_beam_candidates", "vtgb_llm_attention_rows_beam", "vtgb_llm_decode_attention_beam_fp8",
     "vtgb_pack_skinny_weight_mxfp4_bytes", "vtgb_pack_skinny_weight_mxfp4", "vtgb_gemm_skinny_mxfp4",
-    "vtgb_raft_stem_workspace_bytes", "vtgb_raft_stem",
+    "vtgb_raft_stem_workspace_bytes", "vtgb_raft_stem", "vtgb_llm_lora_parts",
 ]
 COMM_ID_BYTES = 128
 
@@ -377,6 +377,8 @@ def lib() -> C.CDLL:
     L.vtgb_llm_attention_rows_beam.restype = C.c_int
     L.vtgb_llm_lora.argtypes = [C.POINTER(LlmLoraArgs), vp]
     L.vtgb_llm_lora.restype = C.c_int
+    L.vtgb_llm_lora_parts.argtypes = [C.POINTER(LlmLoraArgs), vp, i32, vp]
+    L.vtgb_llm_lora_parts.restype = C.c_int
     L.vtgb_llm_rope_cache_prefill_fp8.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     L.vtgb_llm_rope_cache_prefill_fp8.restype = C.c_int
     L.vtgb_gemm_skinny_splits.argtypes = [C.POINTER(GemmSkinnyArgs)]

@@ -101,6 +101,19 @@ def weights_key(lm):
 
 
 _LORA_PROJECTIONS = ("q_proj", "k_proj", "v_proj")
+_T5_LORA_PROJECTIONS = ("q", "k", "v")
+
+
+def _t5_attentions(lm):
+    """The attention modules of a T5 whose q / k / v the T5 graph decoder applies adapters on: every encoder block's SelfAttention, every
+    decoder block's SelfAttention and EncDecAttention."""
+    out = []
+    for stack, idx in ((getattr(lm, "encoder", None), (0,)), (getattr(lm, "decoder", None), (0, 1))):
+        for blk in getattr(stack, "block", None) or ():
+            for i in idx:
+                att = blk.layer[i]
+                out.append(getattr(att, "SelfAttention", None) or getattr(att, "EncDecAttention", None))
+    return [a for a in out if a is not None]
 
 
 def _lora_modules(lm):
@@ -113,22 +126,29 @@ def _lora_modules(lm):
 
 def lora_state(lm) -> Optional[str]:
     """None: ``lm`` has no LoRA adapters; "ok": the graph decoders serve its adapters (train.LoraLinear on q_proj / k_proj / v_proj of a
-    Llama's attention layers: fp32 "default" adapters, no bias, no active dropout), unmerged, as LoraLinear.forward computes them; any other
-    string: why they do not -- the decoders raise NotImplementedError with it and ``plan_decode`` hands the request to HF generate, which runs
-    the modules' own forward.  Never "decoded as the base model"."""
+    Llama's attention layers, or on q / k / v of a T5's ``_t5_attentions``: fp32 "default" adapters, no bias, no active dropout), unmerged, as
+    LoraLinear.forward computes them; any other string: why they do not (on a T5 it names the T5) -- the decoders raise NotImplementedError
+    with it and ``plan_decode`` hands the request to HF generate, which runs the modules' own forward.  Never "decoded as the base model"."""
     mods = _lora_modules(lm)
     if not mods:
         return None
-    from .train import LoraLinear
     if getattr(lm.config, "model_type", "") == "t5":
-        return f"LoRA adapters on a T5 language model ({mods[0][0]}): the T5 graph decoder does not apply adapters"
+        served = {id(getattr(att, p, None)) for att in _t5_attentions(lm) for p in _T5_LORA_PROJECTIONS}
+        why = _lora_refusal(lm, mods, served, "adapters outside q / k / v of the encoder's and the decoder's SelfAttention and the decoder's EncDecAttention")
+        return "ok" if why is None else f"LoRA adapters on a T5 language model -- {why}"
     layers = getattr(getattr(lm, "model", None), "layers", None) or ()
     served = {id(getattr(l.self_attn, p, None)) for l in layers if hasattr(l, "self_attn") for p in _LORA_PROJECTIONS}
+    return _lora_refusal(lm, mods, served, "adapters outside q_proj / k_proj / v_proj of the attention layers") or "ok"
+
+
+def _lora_refusal(lm, mods, served, outside: str) -> Optional[str]:
+    """Why the adapter-carrying modules ``mods`` are not all servable LoraLinears among ``served`` (ids), or None."""
+    from .train import LoraLinear
     for name, m in mods:
         if not isinstance(m, LoraLinear):
             return f"{name}: adapters on a {type(m).__name__}, not a videotgb_amd.train.LoraLinear"
         if id(m) not in served:
-            return f"{name}: adapters outside q_proj / k_proj / v_proj of the attention layers"
+            return f"{name}: {outside}"
         if "default" not in m.lora_A or "default" not in m.lora_B:
             return f"{name}: no \"default\" adapter"
         A, B = m.lora_A["default"].weight, m.lora_B["default"].weight
@@ -141,7 +161,7 @@ def lora_state(lm) -> Optional[str]:
             return f"{name}: training mode with lora_dropout={p} (HF generate applies the dropout; call .eval())"
         if not 1 <= A.shape[0] <= L.LORA_MAX_RANK:
             return f"{name}: rank {A.shape[0]} outside 1..{L.LORA_MAX_RANK}"
-    return "ok"
+    return None
 
 
 def _lora_servable(lm) -> bool:
@@ -1248,7 +1268,8 @@ class T5GreedyDecoder(_GraphDecoder):
     bias shared from the first block), so greedy ids equal HF generate's at fp32 (tests/test_decode.py).  Same EOS / pad /
     min_new_tokens semantics and the same return convention as HF for encoder-decoder models: ids start with
     ``decoder_start_token_id``.  Scope: greedy; padded encoder inputs (``attention_mask``) mask the pad keys of the encoder's
-    self-attention and of every decoder layer's cross-attention, as HF's extended mask does."""
+    self-attention and of every decoder layer's cross-attention, as HF's extended mask does.  LoRA adapters (train.LoraLinear on q / k / v of
+    the encoder's and decoder's SelfAttention and the decoder's EncDecAttention; ``lora_state``) are applied unmerged on every path."""
     _ACT_KIND = {"silu": 0, "swish": 0, "gelu_new": 1, "relu": 2, "gelu": 3}
 
     def __init__(self, lm, fused: bool = True, weights: str = "bf16", kv_cache: str = "bf16"):
@@ -1259,7 +1280,7 @@ class T5GreedyDecoder(_GraphDecoder):
             raise NotImplementedError(f"decode_weights={weights!r} is implemented for the Llama decoder only")
         if check_kv_cache(kv_cache) != "bf16":
             raise NotImplementedError("kv_cache='fp8' is implemented for the Llama decoder only")
-        _lora_servable(lm)      # (a T5 with adapters is never servable: NotImplementedError)
+        has_lora = _lora_servable(lm)      # (adapters outside q / k / v of the attention blocks: NotImplementedError)
         super().__init__(lm, fused, weights, kv_cache)
         self.H, self.dk, self.D = cfg.num_heads, cfg.d_kv, cfg.d_model
         self.eps = cfg.layer_norm_epsilon
@@ -1290,10 +1311,35 @@ class T5GreedyDecoder(_GraphDecoder):
         self.enc_bias_module = lm.encoder.block[0].layer[0].SelfAttention
         self.scale_out = bool(getattr(cfg, "scale_decoder_outputs", getattr(cfg, "tie_word_embeddings", False)))
         self._sk: Dict[int, object] = {}          # id(weight) -> its tiled copy for vtgb_gemm_skinny (built on first use)
+        # LoRA adapters (train.LoraLinear on q / k / v of the three attention blocks), UNMERGED: per layer the (col0, A, B, scaling) segments of
+        # a projection's output, as GreedyDecoder.lora holds them -- references to the model's own fp32 parameters, so a training step is seen
+        # without re-packing.  "enc" / "sa": the fused q|k|v of the encoder's / decoder's self-attention; "cq": the cross-attention's q;
+        # "ckv": its k | v over the encoder states.  None without adapters: today's launches and allocations.
+        self.lora = None
+        if has_lora:
+            HD = self.H * self.dk
+
+            def segs(att, names):
+                return [(i * HD, m.lora_A["default"].weight.detach(), m.lora_B["default"].weight.detach(), float(m.scaling))
+                        for i, n in enumerate(names) for m in (getattr(att, n),) if hasattr(m, "lora_A")]
+            dec_blocks = lm.decoder.block
+            self.lora = dict(enc=[segs(b.layer[0].SelfAttention, _T5_LORA_PROJECTIONS) for b in lm.encoder.block],
+                             sa=[segs(b.layer[0].SelfAttention, _T5_LORA_PROJECTIONS) for b in dec_blocks],
+                             cq=[segs(b.layer[1].EncDecAttention, ("q",)) for b in dec_blocks],
+                             ckv=[segs(b.layer[1].EncDecAttention, ("k", "v")) for b in dec_blocks])
 
     # ---- libvtgb.so building blocks (round 4: no torch.matmul / F.linear / F.softmax left in the T5 path on the device; the arithmetic is
     # transformers' modeling_t5 with its rounding points: T5LayerNorm = vtgb_llm_rmsnorm, unscaled scores + relative bias, fp32 softmax)
     MAX_KEYS = 2048
+    # the decode step's adapted projections (q|k|v, cross q) at bf16: True = the split-K projection with its reduce deferred and ONE
+    # vtgb_llm_lora_parts launch that adds the fragments and applies the adapters; False = the materialised projection (projection + reduce
+    # launches) and vtgb_llm_lora on top.  The same bits either way (tests/test_gpu_t5_lora.py).  Shipped off: at Flan-T5-XL geometry the one
+    # launch is 1.0 % faster per token at B = 1 and 1.8 % slower at B = 8 (profiles/t5_lora_decode_bench.json) -- the update's first phase
+    # (A . x), not the launch count, is what the adapters cost.
+    LORA_PARTS = False
+
+    def _lora_of(self, which: str, li: int):
+        return self.lora[which][li] if self.lora is not None else ()
 
     def _hip(self, x: Tensor) -> bool:
         return (self.fused and x.is_cuda and x.dtype in (torch.bfloat16, torch.float32) and self.act_kind is not None
@@ -1308,6 +1354,32 @@ class T5GreedyDecoder(_GraphDecoder):
                 sk = self._sk[id(w)] = ops.SkinnyWeight(w)
             return ops.gemm_skinny(x, sk, workspace=ws)
         return ops.gemm(x, w)
+
+    def _lin_lora(self, x: Tensor, w: Tensor, segs, ws: Optional[Tensor] = None) -> Tensor:
+        """``_lin`` with the adapter segments ``segs`` applied to its output (none: ``_lin`` itself)."""
+        if not segs:
+            return self._lin(x, w, ws)
+        M, K = x.shape
+        if self.LORA_PARTS and x.dtype == torch.bfloat16 and M <= 128 and K % 64 == 0:
+            sk = self._sk.get(id(w))
+            if sk is None:
+                sk = self._sk[id(w)] = ops.SkinnyWeight(w)
+            out, S, part = ops.gemm_skinny(x, sk, workspace=ws, defer_reduce=True)
+            if S > 1:      # `out` is not written yet: the fragments are reduced and updated in one launch
+                return ops.lora_update_parts(x, out, segs, part, S)
+            return ops.lora_update(x, out, segs)
+        return ops.lora_update(x, self._lin(x, w, ws), segs)
+
+    @staticmethod
+    def _lora_torch(x: Tensor, y: Tensor, segs, shift: int = 0) -> Tensor:
+        """The torch statement: y [..., n_cols] with train.LoraLinear.forward's update on the columns of every segment (``shift``: y's first
+        column in the segments' numbering; segments before it are another tensor's)."""
+        for c0, la, lb, scaling in segs:
+            c0, n = c0 - shift, lb.shape[0]
+            if 0 <= c0 < y.shape[-1]:
+                y = torch.cat((y[..., :c0], y[..., c0: c0 + n] + (F.linear(F.linear(x.to(la.dtype), la), lb) * scaling).to(y.dtype),
+                               y[..., c0 + n:]), dim=-1)
+        return y
 
     def _rms(self, x: Tensor, delta: Optional[Tensor], w: Tensor, h: Tensor) -> None:
         L.check(L.lib().vtgb_llm_rmsnorm(dtype_code(x.dtype), _ptr(x), _ptr(delta), _ptr(w), _ptr(h), x.shape[0], x.shape[1], self.eps, _stream()))
@@ -1340,9 +1412,11 @@ class T5GreedyDecoder(_GraphDecoder):
         with torch.no_grad():
             bias = self.enc_bias_module.compute_bias(P, P, device=x.device)[0].to(x.dtype).contiguous()      # [H, P (query), P (key)]
         delta = None
-        for w in self.enc_layers:
+        for li, w in enumerate(self.enc_layers):
             self._rms(x, delta, w["ln0"], h)
             qkv = self._lin(h, w["wqkv"])                                                                    # [B P, 3 H dk], token-major
+            if self._lora_of("enc", li):
+                ops.lora_update(h, qkv, self.lora["enc"][li])
             a = self._attn_rows(qkv, 3 * HD, qkv[:, HD:], qkv[:, 2 * HD:], (P * 3 * HD, self.dk, 3 * HD), B * P, P, P, P, bias, (P, P * P), None,
                                 key_valid)
             o = self._lin(a, w["wo"])
@@ -1368,7 +1442,7 @@ class T5GreedyDecoder(_GraphDecoder):
         delta = None
         for li, w in enumerate(self.layers):
             self._rms(x, delta, w["ln0"], h)
-            qkv = self._lin(h, w["wqkv"], ws)                                                                # [B, 3 H dk] = [B, (q | k | v heads), dk]
+            qkv = self._lin_lora(h, w["wqkv"], self._lora_of("sa", li), ws)                                  # [B, 3 H dk] = [B, (q | k | v heads), dk]; adapters before the append
             L.check(L.lib().vtgb_llm_rope_cache(dtype_code(x.dtype), _ptr(qkv), _ptr(q), _ptr(st["kc"][li]), _ptr(st["vc"][li]), None, None, _ptr(pos),
                                                 B, H, H, dk, N, _stream()))                                  # (no rotary: cache append)
             if beam:
@@ -1377,7 +1451,7 @@ class T5GreedyDecoder(_GraphDecoder):
                 a = self._attn_rows(q, HD, st["kc"][li], st["vc"][li], (H * N * dk, N * dk, dk), B, 1, 0, N, st["rel"], (N, N * N), pos)
             o = self._lin(a, w["wo"], ws)
             self._rms(x, o, w["ln1"], h)
-            cq = self._lin(h, w["cq"], ws)
+            cq = self._lin_lora(h, w["cq"], self._lora_of("cq", li), ws)
             ckv = st["ckv"][li].view(-1, 2 * HD)                                                             # k | v of the encoder states, rows [0, *plen] of every batch entry valid
             a = self._attn_rows(cq, HD, ckv, ckv[:, HD:], (Pb * 2 * HD, dk, 2 * HD), B, K, 0, Pb, None, (0, 0), st["plen"], st.get("ckv_valid"))
             o = self._lin(a, w["co"], ws)
@@ -1466,14 +1540,14 @@ class T5GreedyDecoder(_GraphDecoder):
         bias = st["bias"].index_select(0, pos)[0][None, :, None, :]                              # [1, H, 1, N]: relative bias + causal mask of this row
         for li, w in enumerate(self.layers):
             h = self._norm(x, w["ln0"])
-            qkv = F.linear(h, w["wqkv"]).view(B, 3, H, 1, dk)
+            qkv = self._lora_torch(h, F.linear(h, w["wqkv"]), self._lora_of("sa", li)).view(B, 3, H, 1, dk)
             st["kc"][li].index_copy_(2, pos, qkv[:, 1])
             st["vc"][li].index_copy_(2, pos, qkv[:, 2])
             sc = torch.matmul(qkv[:, 0], st["kc"][li].transpose(2, 3)) * self.scaling + bias     # [B, H, 1, N]
             a = torch.matmul(F.softmax(sc, dim=-1), st["vc"][li])                                # [B, H, 1, dk]
             x = x + F.linear(a.transpose(1, 2).reshape(B, H * dk), w["wo"])
             h = self._norm(x, w["ln1"])
-            q = F.linear(h, w["cq"]).view(B, H, 1, dk)
+            q = self._lora_torch(h, F.linear(h, w["cq"]), self._lora_of("cq", li)).view(B, H, 1, dk)
             sc = torch.matmul(q, st["ck"][li].transpose(2, 3)) * self.scaling                    # (no relative bias on cross-attention)
             if "cmask" in st:
                 sc = sc + st["cmask"]                                                            # padded encoder input: HF's extended mask
@@ -1573,15 +1647,20 @@ class T5GreedyDecoder(_GraphDecoder):
             enc = self._encode_hip(inputs_embeds, None if valid is None else valid.to(torch.uint8).contiguous())      # [B P, D]
             st["plen"].fill_(P - 1)
             for li, w in enumerate(self.layers):                                    # cross-attention K | V of every decoder layer, once, into the graph's buffers
-                st["ckv"][li][:, :P].copy_(self._lin(enc, w["ckv"]).view(B, P, 2 * self.H * self.dk))
+                ckv = self._lin(enc, w["ckv"])
+                if self._lora_of("ckv", li):      # the adapters of k and v, once per call, before the graph's buffers take the projection
+                    ops.lora_update(enc, ckv, self.lora["ckv"][li])
+                st["ckv"][li][:, :P].copy_(ckv.view(B, P, 2 * self.H * self.dk))
         else:
             am = torch.ones(B, P, dtype=torch.long, device=dev) if valid is None else valid.long()
             enc = self.lm.encoder(inputs_embeds=inputs_embeds, attention_mask=am).last_hidden_state
             if valid is not None:
                 st["cmask"].copy_(rep(torch.where(valid, 0.0, torch.finfo(dt).min).to(dt)[:, None, None, :]))
             for li, w in enumerate(self.layers):
-                st["ck"][li].copy_(rep(F.linear(enc, w["ck"]).view(B, P, self.H, self.dk).transpose(1, 2)))
-                st["cv"][li].copy_(rep(F.linear(enc, w["cv"]).view(B, P, self.H, self.dk).transpose(1, 2)))
+                segs = self._lora_of("ckv", li)
+                ck, cv = self._lora_torch(enc, F.linear(enc, w["ck"]), segs), self._lora_torch(enc, F.linear(enc, w["cv"]), segs, self.H * self.dk)
+                st["ck"][li].copy_(rep(ck.view(B, P, self.H, self.dk).transpose(1, 2)))
+                st["cv"][li].copy_(rep(cv.view(B, P, self.H, self.dk).transpose(1, 2)))
         if beam is not None:
             self._beam_reset(st)
             st["step"].zero_()

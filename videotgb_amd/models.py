@@ -433,6 +433,15 @@ class PathModel(nn.Module):
         return self.language_model.get_input_embeddings()
 
 
+def flatten_peft_keys(state_dict):
+    """A reference (Lightning) checkpoint's ``state_dict`` without peft's ``language_model.base_model.model.`` wrapper level, which
+    train.apply_lora does not add (the adapters keep peft's names below it: ``...q.lora_A.default.weight``)."""
+    lp = "model.language_model.base_model.model."
+    if any(k.startswith(lp) for k in state_dict):
+        state_dict = {("model.language_model." + k[len(lp):] if k.startswith(lp) else k): v for k, v in state_dict.items()}
+    return state_dict
+
+
 class _LSTPBase(nn.Module):
     ARCH = "instructblip"
     TGB_MODE = "multi_modal"
@@ -494,7 +503,8 @@ class _LSTPBase(nn.Module):
         if lora:
             # the reference wraps the LLM with peft (r=8, alpha=32, dropout 0.1, inference mode; eval/utils/model.py:40-44);
             # same adapter arithmetic and parameter names here (videotgb_amd.train.LoraLinear), without peft's
-            # ``base_model.model.`` wrapper level -- load_state_dict strips it from a reference checkpoint's keys
+            # ``base_model.model.`` wrapper level -- load_state_dict strips it from a reference checkpoint's keys.  The targets are peft's
+            # defaults for the language model's type: q_proj / v_proj of a Llama, q / v of a Flan-T5 (LSTP_blip2, eval/utils/model.py:259-263)
             from .train import apply_lora
             apply_lora(self.model.language_model, r=8, lora_alpha=32, lora_dropout=0.1)
             self.model.language_model.eval()
@@ -511,10 +521,7 @@ class _LSTPBase(nn.Module):
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         """Accepts a reference (Lightning) checkpoint's ``state_dict`` as is: peft's ``language_model.base_model.model.``
         level is flattened, the dead ``position_ids`` buffers older transformers versions persisted are tolerated."""
-        lp = "model.language_model.base_model.model."
-        if any(k.startswith(lp) for k in state_dict):
-            state_dict = {("model.language_model." + k[len(lp):] if k.startswith(lp) else k): v for k, v in state_dict.items()}
-        return super().load_state_dict(state_dict, strict=strict, **kw)
+        return super().load_state_dict(flatten_peft_keys(state_dict), strict=strict, **kw)
 
     def set_compute_dtype(self, compute_dtype):
         for m in (self.model.vision_model, self.model.qformer, self.temporal_encoder):

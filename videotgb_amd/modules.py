@@ -412,6 +412,10 @@ class _LSTPLightningBase(_Base):
         self.val_bleu_score.reset()
         self.val_score_best = 0.0
 
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        """Accepts a reference checkpoint of the IVT flavours as is (models.flatten_peft_keys: peft's wrapper level is flattened)."""
+        return super().load_state_dict(models.flatten_peft_keys(state_dict), strict=strict, **kw)
+
     def configure_optimizers(self) -> Dict[str, Any]:
         """LSTP_module.py:634-679: ``optimizer(params=self.parameters())`` (a functools.partial from Hydra); "cosine" =
         transformers' warmup-cosine with warmup = int(trainer.max_steps * scheduler_params["warmup_steps"]), per-epoch."""

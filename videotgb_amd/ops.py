@@ -708,20 +708,39 @@ def attention_rows_beam(q: Tensor, kc: Tensor, vc: Tensor, src_row: Tensor, pos:
     return out
 
 
+def _lora_args(x: Tensor, y: Tensor, segments, name: str):
+    """vtgb_llm_lora_args of both LoRA entries (the wrappers' own shape / dtype checks; the library checks the rest)."""
+    _need_cuda(x, y, *(t for _, A, B, _ in segments for t in (A, B)))
+    assert x.dim() == 2 and y.dim() == 2 and x.shape[0] == y.shape[0] and x.dtype == y.dtype, f"{name}: x [rows, K] and y [rows, n_cols] of one dtype"
+    assert x.stride(1) == 1 and y.stride(1) == 1, f"{name}: unit column stride"
+    a = L.LlmLoraArgs(dtype_code(y.dtype), x.shape[1], y.shape[1], len(segments), x.shape[0], x.stride(0), y.stride(0), _ptr(x), _ptr(y))
+    for s, (col0, A, B, scaling) in enumerate(segments[:L.LORA_MAX_SEGMENTS]):
+        assert A.dtype == B.dtype == torch.float32 and A.is_contiguous() and B.is_contiguous(), f"{name}: fp32 contiguous adapters"
+        assert A.dim() == 2 and B.dim() == 2 and A.shape[1] == x.shape[1] and B.shape[1] == A.shape[0], f"{name}: A [r, K], B [n, r]"
+        a.seg[s] = L.LlmLoraSeg(_ptr(A), _ptr(B), A.shape[0], B.shape[0], int(col0), float(scaling))
+    return a
+
+
 def lora_update(x: Tensor, y: Tensor, segments) -> Tensor:
     """Unmerged LoRA adapters on a projection's output, in place (vtgb_llm_lora): for every ``(col0, A, B, scaling)`` of ``segments`` (1 .. 4,
     disjoint column ranges), ``y[:, col0 : col0 + n] += ((x.float() @ A.T) @ B.T * scaling).to(y.dtype)`` -- train.LoraLinear.forward in eval
     mode, rounding for rounding.  x [rows, K] and y [rows, n_cols] bf16 or fp32 (the same), unit column stride, any row stride; A [r, K] and
     B [n, r] fp32 contiguous.  Returns ``y``.  The library checks the rest (include/vtgb.h) and raises through ``_lib.check``."""
-    _need_cuda(x, y, *(t for _, A, B, _ in segments for t in (A, B)))
-    assert x.dim() == 2 and y.dim() == 2 and x.shape[0] == y.shape[0] and x.dtype == y.dtype, "lora_update: x [rows, K] and y [rows, n_cols] of one dtype"
-    assert x.stride(1) == 1 and y.stride(1) == 1, "lora_update: unit column stride"
-    a = L.LlmLoraArgs(dtype_code(y.dtype), x.shape[1], y.shape[1], len(segments), x.shape[0], x.stride(0), y.stride(0), _ptr(x), _ptr(y))
-    for s, (col0, A, B, scaling) in enumerate(segments[:L.LORA_MAX_SEGMENTS]):
-        assert A.dtype == B.dtype == torch.float32 and A.is_contiguous() and B.is_contiguous(), "lora_update: fp32 contiguous adapters"
-        assert A.dim() == 2 and B.dim() == 2 and A.shape[1] == x.shape[1] and B.shape[1] == A.shape[0], "lora_update: A [r, K], B [n, r]"
-        a.seg[s] = L.LlmLoraSeg(_ptr(A), _ptr(B), A.shape[0], B.shape[0], int(col0), float(scaling))
+    a = _lora_args(x, y, segments, "lora_update")
     L.check(L.lib().vtgb_llm_lora(C.byref(a), _stream()))
+    return y
+
+
+def lora_update_parts(x: Tensor, y: Tensor, segments, part: Tensor, n_splits: int) -> Tensor:
+    """The K-split reduce of a deferred projection and ``lora_update`` in ONE launch (vtgb_llm_lora_parts): ``part`` and ``n_splits`` > 1 are
+    the workspace and split count ``gemm_skinny(x, w, defer_reduce=True)`` returned for the [rows <= 128, n_cols] projection; ``y`` (bf16, as
+    x) is written, not read.  Bit for bit ``lora_update(x, gemm_skinny(x, w, n_splits=n_splits), segments)``.  Returns ``y``."""
+    a = _lora_args(x, y, segments, "lora_update_parts")
+    _need_cuda(part)
+    rows, n_cols = y.shape
+    need = -(-n_cols // 128) * int(n_splits) * rows * 128 * 4
+    assert part.is_contiguous() and part.numel() * part.element_size() >= need, f"lora_update_parts: fragments of {need} bytes"
+    L.check(L.lib().vtgb_llm_lora_parts(C.byref(a), _ptr(part), int(n_splits), _stream()))
     return y
 
 

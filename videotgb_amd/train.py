@@ -532,11 +532,15 @@ class LoraLinear(nn.Linear):
 
 
 def apply_lora(language_model: nn.Module, r: int = 8, lora_alpha: int = 32, lora_dropout: float = 0.1,
-               target_modules: Sequence[str] = ("q_proj", "v_proj")) -> List[nn.Parameter]:
+               target_modules: Optional[Sequence[str]] = None) -> List[nn.Parameter]:
     """``get_peft_model(language_model, LoraConfig(task_type=CAUSAL_LM, r=8, lora_alpha=32, lora_dropout=0.1))``
-    (LSTP_Vicuna_IVT_module.py:183-186): peft's default targets for Llama are q_proj and v_proj; every other
-    parameter of the language model is frozen.  Returns the trainable (adapter) parameters
-    (Vicuna-7B: 32 layers x 2 x (4096*8 + 8*4096) = 4,194,304)."""
+    (LSTP_Vicuna_IVT_module.py:183-186) and its SEQ_2_SEQ_LM twin (LSTP_Blip2_IVT_module.py:185-188, eval/utils/model.py:259-263).
+    ``target_modules`` None picks peft's defaults by ``config.model_type``: q and v for a T5 (every SelfAttention of both stacks and every
+    EncDecAttention), q_proj and v_proj otherwise (Llama); every other parameter of the language model is frozen.  Returns the trainable
+    (adapter) parameters (Vicuna-7B: 32 layers x 2 x (4096*8 + 8*4096) = 4,194,304; a T5 of L_e + L_d layers: 2 (2 L_e + 4 L_d) tensors)."""
+    if target_modules is None:
+        t5 = getattr(getattr(language_model, "config", None), "model_type", "") == "t5"
+        target_modules = ("q", "v") if t5 else ("q_proj", "v_proj")
     for p in language_model.parameters():
         p.requires_grad = False
     for parent in list(language_model.modules()):
