@@ -968,6 +968,55 @@ typedef struct {
 } vtgb_llm_beam_candidates_args;
 int vtgb_llm_beam_candidates(const vtgb_llm_beam_candidates_args* a, vtgb_stream_t stream);
 
+/* ---- Eos-id SETS on the graph decoders (opt-in: eos_sets = "graph"; emit.hip, beam.hip; added at version 601 without a bump).  A request may
+ *   name up to VTGB_LLM_EOS_MAX eos ids (Llama-3.1-Instruct's generation config lists three); the list is device int32 [n_eos], duplicates
+ *   allowed.  The list lives on the device, so the entries cannot read it: whoever builds it checks 0 <= id < V on the host (ops.eos_list, the
+ *   decoders), and the kernels treat an id outside [0, V) as equal to no token -- it blocks nothing, ends nothing and indexes nothing.
+ * vtgb_llm_pick_greedy: the greedy emission of one decode step in one launch, one workgroup per row.  logits [B, V] (`dtype`, row stride V;
+ *   a row that does not start on 16 bytes -- odd V in bf16 -- is read element by element up to the first boundary, never wide from a misaligned
+ *   address).  Per row b, t = the LOWEST index of the maximum (torch.argmax's rule), the listed ids counting as -inf while *step < min_new;
+ *   a row with fin[b] set gives t = pad and keeps fin[b]; otherwise fin[b] |= (t in eos_ids).  t goes to tok[b] and out[b, *step] (out
+ *   [B, N] int64; *step device int64, clamped to [0, N) before it is used as a column: a wrong step gives a wrong column, never a write
+ *   outside out).  The result depends on the row alone, not on B or the row's place.  Logits containing NaN are NOT specified (some index in
+ *   [0, V) is written).  VTGB_EINVAL: NULL args / operand (eos_ids may be NULL when n_eos == 0), a dtype other than VTGB_BF16 / VTGB_F32,
+ *   non-positive B / V / N, n_eos outside [0, VTGB_LLM_EOS_MAX]; VTGB_EUNSUPPORTED: a misaligned operand (logits 16 bytes; step, tok, out 8;
+ *   eos_ids 4) -- on the host, before any launch.
+ * vtgb_llm_beam_candidates_eos: vtgb_llm_beam_candidates with the list in place of `eos`: lp[id] = -inf for every listed id while
+ *   *step < min_new; everything else, the workspace and the refusals are that entry's (plus n_eos out of range / NULL eos_ids: VTGB_EINVAL, a
+ *   misaligned eos_ids: VTGB_EUNSUPPORTED).  With a one-element list the scores and indices equal vtgb_llm_beam_candidates' BIT FOR BIT. */
+#define VTGB_LLM_EOS_MAX 8
+typedef struct {
+    int32_t dtype;                       /* of logits */
+    int32_t B, V, N;
+    int32_t min_new;
+    int32_t n_eos;                       /* 0 .. VTGB_LLM_EOS_MAX */
+    int64_t pad;
+    const void* logits;                  /* [B, V] */
+    const int64_t* step;                 /* device */
+    const int32_t* eos_ids;              /* device [n_eos] */
+    uint8_t* fin;                        /* [B] bool, read and written */
+    int64_t* tok;                        /* [B] */
+    int64_t* out;                        /* [B, N], column *step written */
+} vtgb_llm_pick_greedy_args;
+int vtgb_llm_pick_greedy(const vtgb_llm_pick_greedy_args* a, vtgb_stream_t stream);
+typedef struct {
+    int32_t dtype;                       /* of logits */
+    int32_t R, K, V, N;
+    int32_t n_eos;                       /* 0 .. VTGB_LLM_EOS_MAX */
+    int32_t min_new;
+    float penalty;                       /* repetition penalty, > 0 (1: none) */
+    const void* logits;                  /* [R, V] */
+    const int64_t* seq;                  /* [R, N] generated ids */
+    const int64_t* step;                 /* device */
+    const float* running;                /* [R / K, K] */
+    const int32_t* eos_ids;              /* device [n_eos] */
+    float* cand_score;                   /* [R / K, 2 K] */
+    int32_t* cand_idx;                   /* [R / K, 2 K] */
+    void* workspace;
+    size_t workspace_bytes;
+} vtgb_llm_beam_candidates_eos_args;
+int vtgb_llm_beam_candidates_eos(const vtgb_llm_beam_candidates_eos_args* a, vtgb_stream_t stream);
+
 /* ---- Beam search on the T5 decode step (opt-in: beam_search = "graph+t5"; llm.hip; added at version 601 without a bump).
  * vtgb_llm_attention_rows_beam: vtgb_llm_attention_rows in its decode form -- `pos` given, keys [0, *pos], bias row *pos -- over the caches
  *   k / v of `cache_rows` rows (row stride kv_batch), where K and V of key t of query row r come from cache row

@@ -48,7 +48,7 @@ EXPORTS = [
     "vtgb_raft_lookup_convc1", "vtgb_raft_gru_half", "vtgb_llm_lora", "vtgb_conv_launch", "vtgb_attention_cached",
     "vtgb_llm_decode_attention_beam", "vtgb_llm_beam_candidates", "vtgb_llm_attention_rows_beam", "vtgb_llm_decode_attention_beam_fp8",
     "vtgb_pack_skinny_weight_mxfp4_bytes", "vtgb_pack_skinny_weight_mxfp4", "vtgb_gemm_skinny_mxfp4",
-    "vtgb_raft_stem_workspace_bytes", "vtgb_raft_stem", "vtgb_llm_lora_parts",
+    "vtgb_raft_stem_workspace_bytes", "vtgb_raft_stem", "vtgb_llm_lora_parts", "vtgb_llm_pick_greedy", "vtgb_llm_beam_candidates_eos",
 ]
 COMM_ID_BYTES = 128
 
@@ -239,6 +239,19 @@ class LlmBeamCandidatesArgs(C.Structure):
                 ("seq", vp), ("step", vp), ("running", vp), ("cand_score", vp), ("cand_idx", vp), ("workspace", vp), ("workspace_bytes", sz)]
 
 
+class LlmPickGreedyArgs(C.Structure):
+    """vtgb_llm_pick_greedy_args: one step's logits -> the greedy token of every row under a set of eos ids, written to tok / out / fin."""
+    _fields_ = [("dtype", i32), ("B", i32), ("V", i32), ("N", i32), ("min_new", i32), ("n_eos", i32), ("pad", i64), ("logits", vp), ("step", vp),
+                ("eos_ids", vp), ("fin", vp), ("tok", vp), ("out", vp)]
+
+
+class LlmBeamCandidatesEosArgs(C.Structure):
+    """vtgb_llm_beam_candidates_eos_args: LlmBeamCandidatesArgs with a device list of eos ids in place of the one id."""
+    _fields_ = [("dtype", i32), ("R", i32), ("K", i32), ("V", i32), ("N", i32), ("n_eos", i32), ("min_new", i32), ("penalty", f32), ("logits", vp),
+                ("seq", vp), ("step", vp), ("running", vp), ("eos_ids", vp), ("cand_score", vp), ("cand_idx", vp), ("workspace", vp),
+                ("workspace_bytes", sz)]
+
+
 class GemmArgs(C.Structure):
     _fields_ = [("dtype", i32), ("M", i32), ("N", i32), ("K", i32), ("epilogue", i32), ("A", vp), ("lda", i64),
                 ("W", vp), ("ldw", i64), ("bias", vp), ("resid", vp), ("out", vp), ("ldo", i64)]
@@ -373,6 +386,10 @@ def lib() -> C.CDLL:
     L.vtgb_llm_decode_attention_beam_fp8.restype = C.c_int
     L.vtgb_llm_beam_candidates.argtypes = [C.POINTER(LlmBeamCandidatesArgs), vp]
     L.vtgb_llm_beam_candidates.restype = C.c_int
+    L.vtgb_llm_pick_greedy.argtypes = [C.POINTER(LlmPickGreedyArgs), vp]
+    L.vtgb_llm_pick_greedy.restype = C.c_int
+    L.vtgb_llm_beam_candidates_eos.argtypes = [C.POINTER(LlmBeamCandidatesEosArgs), vp]
+    L.vtgb_llm_beam_candidates_eos.restype = C.c_int
     L.vtgb_llm_attention_rows_beam.argtypes = [C.POINTER(LlmAttnRowsArgs), vp, i64, i32, vp]
     L.vtgb_llm_attention_rows_beam.restype = C.c_int
     L.vtgb_llm_lora.argtypes = [C.POINTER(LlmLoraArgs), vp]

@@ -3,7 +3,8 @@
 // eos block of the min-length processors on the log-probabilities, + the running beam scores, torch.topk over K * V).  Two launches:
 //
 // beam_row_kernel, one workgroup per beam row.  In fp32: m = max x, S = sum exp(x - m), lp = (x - m) - log S into the workspace row; then
-// every DISTINCT id of seq[r, 0 .. *step) is penalised once (lp < 0 ? lp * p : lp / p), lp[eos] = -inf while *step < min_new, and the row's
+// every DISTINCT id of seq[r, 0 .. *step) is penalised once (lp < 0 ? lp * p : lp / p), lp[eos] = -inf while *step < min_new (one id, or
+// every id of a device list: vtgb_llm_beam_candidates_eos), and the row's
 // 2 K best scores lp + running[r] are taken in descending order, equal scores in ascending token: every thread keeps the best of its own
 // tokens (token % 256 == thread) that has not been taken, a round picks the workgroup's best and only its owner looks again.
 // Which values share a partial sum and the order inside the sum depend on V alone (thread = token % 256, a thread's tokens ascending, then
@@ -14,6 +15,8 @@
 #include "common.h"
 
 #include <math.h>
+
+#include <type_traits>
 
 constexpr int BEAM_MAX_K = 16;
 constexpr int BEAM_MAX_V = 1 << 20;
@@ -37,10 +40,17 @@ __device__ __forceinline__ void beam_block_best(float& v, int& i, float (*sv)[4]
         if (beam_better(sv[slot][w], si[slot][w], v, i)) v = sv[slot][w], i = si[slot][w];
 }
 
-template <typename T>
+// the eos operand of beam_row_kernel: one id by value (vtgb_llm_beam_candidates; < 0: none), or a device list (vtgb_llm_beam_candidates_eos).
+// A second instantiation, not a branch: the one-id kernel's arguments and instructions are what they were before the list existed.
+struct BeamEosList {
+    const int* ids;
+    int n;
+};
+
+template <typename T, typename E>
 __global__ __launch_bounds__(256) void beam_row_kernel(const T* __restrict__ logits, const int64_t* __restrict__ seq, const int64_t* __restrict__ step_p,
                                                        const float* __restrict__ running, float* __restrict__ lp_ws, float* __restrict__ row_score,
-                                                       int* __restrict__ row_idx, int K, int V, int N, int eos, int min_new, float penalty) {
+                                                       int* __restrict__ row_idx, int K, int V, int N, E eos, int min_new, float penalty) {
     __shared__ float red[4];
     __shared__ float sv[2][4];
     __shared__ int si[2][4];
@@ -80,9 +90,19 @@ __global__ __launch_bounds__(256) void beam_row_kernel(const T* __restrict__ log
         }
         __syncthreads();
     }
-    if (eos >= 0 && eos < V && step64 < (int64_t)min_new) {
-        if (tid == 0) lp[eos] = -INFINITY;
-        __syncthreads();
+    if constexpr (std::is_same<E, int>::value) {
+        if (eos >= 0 && eos < V && step64 < (int64_t)min_new) {
+            if (tid == 0) lp[eos] = -INFINITY;
+            __syncthreads();
+        }
+    } else {
+        if (eos.n > 0 && step64 < (int64_t)min_new) {      // every listed id (a duplicate writes the same value twice)
+            if (tid < eos.n) {
+                const int id = eos.ids[tid];
+                if (id >= 0 && id < V) lp[id] = -INFINITY;
+            }
+            __syncthreads();
+        }
     }
 
     // ---- the row's 2 K best under (score descending, token ascending)
@@ -133,8 +153,8 @@ __global__ __launch_bounds__(512) void beam_merge_kernel(const float* __restrict
     }
 }
 
-extern "C" int vtgb_llm_beam_candidates(const vtgb_llm_beam_candidates_args* a, vtgb_stream_t stream) {
-    VTGB_REQUIRE(a, VTGB_EINVAL, "llm_beam_candidates: NULL args");
+template <typename E>
+static int beam_candidates_launch(const vtgb_llm_beam_candidates_args* a, E eos, vtgb_stream_t stream) {
     VTGB_REQUIRE(a->logits && a->step && a->running && a->cand_score && a->cand_idx && a->workspace && (a->seq || a->N == 0), VTGB_EINVAL,
                  "llm_beam_candidates: NULL operand");
     VTGB_REQUIRE((a->dtype == VTGB_BF16 || a->dtype == VTGB_F32) && a->R > 0 && a->K > 0 && a->V > 0 && a->N >= 0 && a->penalty > 0.f, VTGB_EINVAL,
@@ -151,13 +171,30 @@ extern "C" int vtgb_llm_beam_candidates(const vtgb_llm_beam_candidates_args* a, 
     float* row_score = (float*)((char*)a->workspace + lp_bytes);
     int* row_idx = (int*)(row_score + (size_t)a->R * 2 * a->K);
     if (a->dtype == VTGB_BF16)
-        hipLaunchKernelGGL(beam_row_kernel<bf16_t>, dim3(a->R), dim3(256), 0, s, (const bf16_t*)a->logits, a->seq, a->step, a->running, lp, row_score, row_idx,
-                           a->K, a->V, a->N, a->eos, a->min_new, a->penalty);
+        hipLaunchKernelGGL((beam_row_kernel<bf16_t, E>), dim3(a->R), dim3(256), 0, s, (const bf16_t*)a->logits, a->seq, a->step, a->running, lp, row_score,
+                           row_idx, a->K, a->V, a->N, eos, a->min_new, a->penalty);
     else
-        hipLaunchKernelGGL(beam_row_kernel<float>, dim3(a->R), dim3(256), 0, s, (const float*)a->logits, a->seq, a->step, a->running, lp, row_score, row_idx,
-                           a->K, a->V, a->N, a->eos, a->min_new, a->penalty);
+        hipLaunchKernelGGL((beam_row_kernel<float, E>), dim3(a->R), dim3(256), 0, s, (const float*)a->logits, a->seq, a->step, a->running, lp, row_score,
+                           row_idx, a->K, a->V, a->N, eos, a->min_new, a->penalty);
     VTGB_HIP(hipGetLastError());
     hipLaunchKernelGGL(beam_merge_kernel, dim3(a->R / a->K), dim3(512), 0, s, (const float*)row_score, (const int*)row_idx, a->cand_score, a->cand_idx, a->K);
     VTGB_HIP(hipGetLastError());
     return VTGB_OK;
+}
+
+extern "C" int vtgb_llm_beam_candidates(const vtgb_llm_beam_candidates_args* a, vtgb_stream_t stream) {
+    VTGB_REQUIRE(a, VTGB_EINVAL, "llm_beam_candidates: NULL args");
+    return beam_candidates_launch<int>(a, a->eos, stream);
+}
+
+// the same two launches with the list instantiation of beam_row_kernel; everything but the eos operand is checked by the shared launcher
+extern "C" int vtgb_llm_beam_candidates_eos(const vtgb_llm_beam_candidates_eos_args* a, vtgb_stream_t stream) {
+    VTGB_REQUIRE(a, VTGB_EINVAL, "llm_beam_candidates_eos: NULL args");
+    VTGB_REQUIRE(a->n_eos >= 0 && a->n_eos <= VTGB_LLM_EOS_MAX, VTGB_EINVAL, "llm_beam_candidates_eos: n_eos=%d eos ids, 0 .. %d are taken", a->n_eos,
+                 VTGB_LLM_EOS_MAX);
+    VTGB_REQUIRE(a->eos_ids || a->n_eos == 0, VTGB_EINVAL, "llm_beam_candidates_eos: NULL operand");
+    VTGB_REQUIRE((reinterpret_cast<uintptr_t>(a->eos_ids) & 3) == 0, VTGB_EUNSUPPORTED, "llm_beam_candidates_eos: eos_ids alignment (4 bytes)");
+    vtgb_llm_beam_candidates_args c = {a->dtype, a->R, a->K, a->V, a->N, -1, a->min_new, a->penalty, a->logits, a->seq, a->step, a->running,
+                                       a->cand_score, a->cand_idx, a->workspace, a->workspace_bytes};
+    return beam_candidates_launch<BeamEosList>(&c, BeamEosList{a->eos_ids, a->n_eos}, stream);
 }

@@ -93,6 +93,22 @@ def check_beam_search(beam_search) -> str:
     return beam_search
 
 
+EOS_SETS = ("hf", "graph")
+
+
+def check_eos_sets(eos_sets) -> str:
+    """Who runs a request with several distinct eos ids: "hf" (HF generate, the default) or "graph" (opt-in: the graph decoders, up to
+    ``ops.EOS_MAX`` ids -- ``GreedyDecoder(eos_sets=True)`` / ``T5GreedyDecoder(eos_sets=True)``); ValueError otherwise."""
+    if not isinstance(eos_sets, str) or eos_sets not in EOS_SETS:
+        raise ValueError(f"eos_sets must be one of {EOS_SETS}, got {eos_sets!r}")
+    return eos_sets
+
+
+def _first_eos(eos):
+    """The id HF's defaults take from a request's eos: the id itself, or the first of a set."""
+    return eos[0] if isinstance(eos, tuple) else eos
+
+
 def weights_key(lm):
     """(in-place version, storage address) of every parameter: the decoders hold re-packed COPIES of the language model's weights
     (concatenated q|k|v, tiled decode weights, captured graphs), so an optimizer step, a load_state_dict or a `.data` swap on
@@ -255,18 +271,26 @@ class _GraphDecoder:
     MAX_STATES = 4
     FEEDBACK = ("tok", "pos", "step", "out", "fin", "len")      # what one step writes besides the model's caches
 
-    def __init__(self, lm, fused: bool, weights: str = "bf16", kv_cache: str = "bf16"):
+    def __init__(self, lm, fused: bool, weights: str = "bf16", kv_cache: str = "bf16", eos_sets: bool = False):
         self.lm, self.cfg, self.fused, self.weights = lm, lm.config, fused, check_decode_weights(weights)
         self.kv_cache = check_kv_cache(kv_cache)
+        self.eos_sets = bool(eos_sets)      # opt-in (eos_sets="graph"): requests with 2 .. ops.EOS_MAX distinct eos ids instead of a refusal
         self.key = weights_key(lm)
         self.graphs: Dict[tuple, dict] = {}
 
     def _special(self, eos_token_id, pad_token_id, min_new_tokens):
-        """(eos, pad, min_new) as the state holds them: a one-element eos list unwrapped, HF's pad default (the eos id), ints."""
+        """(eos, pad, min_new) as the state holds them: a one-element eos list unwrapped, HF's pad default (the eos id), ints.  A decoder built
+        with ``eos_sets``: a list of 2 .. ops.EOS_MAX distinct ids in [0, V) stays a tuple in the caller's order, duplicates dropped (HF's pad
+        default is then its first id); a list that collapses to one id is that id."""
         if isinstance(eos_token_id, (list, tuple)):
-            if len(eos_token_id) != 1:
-                raise NotImplementedError(f"{type(self).__name__}: one eos_token_id")
-            eos_token_id = eos_token_id[0]
+            ids = tuple(dict.fromkeys(int(v) for v in eos_token_id)) if self.eos_sets and len(eos_token_id) > 0 else tuple(eos_token_id)
+            if len(ids) != 1:
+                V = self.lm.lm_head.weight.shape[0]
+                if not self.eos_sets or not 2 <= len(ids) <= ops.EOS_MAX or any(not 0 <= v < V for v in ids):
+                    raise NotImplementedError(f"{type(self).__name__}: one eos_token_id" + (
+                        f", or (eos_sets) 2 .. {ops.EOS_MAX} distinct ids in [0, {V})" if self.eos_sets else ""))
+                return ids, int(pad_token_id if pad_token_id is not None else ids[0]), int(min_new_tokens or 0)
+            eos_token_id = ids[0]
         return eos_token_id, int(pad_token_id if pad_token_id is not None else (eos_token_id or 0)), int(min_new_tokens or 0)
 
     def _cached_state(self, key: tuple, B: int, N: int, n_ar: int, device, eos, pad: int, min_new: int, sample, stop, buffers: Callable[[], dict]) -> dict:
@@ -283,6 +307,8 @@ class _GraphDecoder:
                       stop_t=[torch.tensor(t, dtype=torch.long, device=device) for t in (stop or ())],      # (device copies made outside any capture)
                       # sampling: one uniform number per (step, row); the generated length of every row (N = not finished)
                       u=torch.zeros(N, B, device=device), len=torch.full((B,), N, dtype=torch.long, device=device))
+            if isinstance(eos, tuple):      # an eos set: its device list (isin on the torch path, the kernels' operand on the fused one)
+                st["eos_t"] = torch.tensor(eos, dtype=torch.int32, device=device)
             st.update(buffers())
         self.graphs[key] = st
         return st
@@ -297,7 +323,8 @@ class _GraphDecoder:
         if eos is not None and st["min_new"] > 0:
             blocked = (step < st["min_new"]) if isinstance(step, Tensor) else torch.tensor([step < st["min_new"]], device=logits.device)
             logits = logits.clone()
-            logits[:, eos] = torch.where(blocked, torch.full_like(logits[:, eos], float("-inf")), logits[:, eos])
+            for e in (eos if isinstance(eos, tuple) else (eos,)):      # (an eos set: every id of it)
+                logits[:, e] = torch.where(blocked, torch.full_like(logits[:, e], float("-inf")), logits[:, e])
         if st["sample"] is None:
             nxt = logits.argmax(-1)
         else:
@@ -314,7 +341,9 @@ class _GraphDecoder:
             nxt = idx.gather(-1, j[:, None])[:, 0]
         if eos is not None or st["stop"] is not None:
             nxt = torch.where(st["fin"], torch.full_like(nxt, st["pad"]), nxt)
-        if eos is not None:
+        if isinstance(eos, tuple):
+            st["fin"].logical_or_(torch.isin(nxt, st["eos_t"]))
+        elif eos is not None:
             st["fin"].logical_or_(nxt == eos)
         return nxt
 
@@ -337,9 +366,13 @@ class _GraphDecoder:
             st["len"].copy_(torch.where(st["fin"] & (st["len"] == N), (step + 1).expand_as(st["len"]), st["len"]))
 
     def _emit(self, st, logits: Tensor):
-        nxt = self._pick(st, logits, st["step"])
-        st["tok"].copy_(nxt)
-        st["out"].index_copy_(1, st["step"], nxt[:, None])
+        if "eos_t" in st and st["sample"] is None and self.fused and logits.is_cuda:
+            # an eos set, greedy, on the device: ``_pick`` and the two writes below in one launch (vtgb_llm_pick_greedy)
+            ops.pick_greedy(logits, st["step"], st["eos_t"], st["fin"], st["tok"], st["out"], st["min_new"], st["pad"])
+        else:
+            nxt = self._pick(st, logits, st["step"])
+            st["tok"].copy_(nxt)
+            st["out"].index_copy_(1, st["step"], nxt[:, None])
         self._after_token(st, st["step"])
         st["pos"].add_(1)
         st["step"].add_(1)
@@ -442,6 +475,10 @@ class _GraphDecoder:
         bm, step = st["beam"], st["step"]
         B, K, N = st["run_seq"].shape
         V = logits.shape[-1]
+        if bm["kernel"] and "eos_t" in st:      # an eos set: the list instantiation of the same kernel
+            sc, ix = ops.beam_candidates_eos(logits, st["run_seq"].view(B * K, N), step, st["run_scores"], st["eos_t"], bm["repetition_penalty"],
+                                             st["min_new"], out=(st["cand_score"], st["cand_idx"]), workspace=st["cand_ws"])
+            return sc, ix.long()
         if bm["kernel"]:
             sc, ix = ops.beam_candidates(logits, st["run_seq"].view(B * K, N), step, st["run_scores"], bm["repetition_penalty"], st["eos"],
                                          st["min_new"], out=(st["cand_score"], st["cand_idx"]), workspace=st["cand_ws"])
@@ -454,7 +491,8 @@ class _GraphDecoder:
             lp = lp.scatter(1, ids, torch.where(g < 0, g * bm["repetition_penalty"], g / bm["repetition_penalty"]))[:, :V]
         if st["eos"] is not None and st["min_new"] > 0:
             lp = lp.clone()
-            lp[:, st["eos"]] = torch.where(step < st["min_new"], torch.full_like(lp[:, st["eos"]], float("-inf")), lp[:, st["eos"]])
+            for e in (st["eos"] if isinstance(st["eos"], tuple) else (st["eos"],)):      # (an eos set: every id of it)
+                lp[:, e] = torch.where(step < st["min_new"], torch.full_like(lp[:, e], float("-inf")), lp[:, e])
         acc = (lp.view(B, K, V) + st["run_scores"][:, :, None]).reshape(B, K * V)
         return torch.topk(acc, k=2 * K)
 
@@ -481,7 +519,9 @@ class _GraphDecoder:
         top_bi = take(st["run_bi"], beam).scatter(2, at, (beam + st["item_off"]).to(torch.int32)[:, :, None])
         # d. stopping criteria: EosTokenCriteria | MaxLengthCriteria
         hits = (step + 1 >= N).expand(B, 2 * K)
-        if st["eos"] is not None:
+        if "eos_t" in st:
+            hits = hits | torch.isin(token, st["eos_t"])
+        elif st["eos"] is not None:
             hits = hits | (token == st["eos"])
         # e. _get_running_beams_for_next_iteration
         run_lp = score + hits.to(torch.float32) * -1.0e9
@@ -567,13 +607,13 @@ class GreedyDecoder(_GraphDecoder):
     epilogue -- ops.gemm_skinny(bias=), vtgb_gemm_skinny_bias --, prefill and large batches through vtgb_gemm's bias, ``_layer`` through
     F.linear).  Anything else raises NotImplementedError with the reason."""
 
-    def __init__(self, lm, fused: bool = True, weights: str = "bf16", kv_cache: str = "bf16", fp8_beams: bool = False):
+    def __init__(self, lm, fused: bool = True, weights: str = "bf16", kv_cache: str = "bf16", fp8_beams: bool = False, eos_sets: bool = False):
         cfg = lm.config
         if "llama" not in cfg.model_type:
             raise NotImplementedError("GreedyDecoder handles Llama-architecture models; use HF generate otherwise")
         _llama_servable(lm)
         has_lora = _lora_servable(lm)
-        super().__init__(lm, fused, weights, kv_cache)
+        super().__init__(lm, fused, weights, kv_cache, eos_sets)
         self.fp8_beams = bool(fp8_beams)      # opt-in (beam_search="...+kv8"): num_beams > 1 over the fp8 K/V cache; inert with a bf16 cache
         wdt = lm.lm_head.weight.dtype
         if self.kv_cache == "fp8" and wdt != torch.bfloat16 and (fused or wdt != torch.float32):
@@ -1126,7 +1166,7 @@ class GreedyDecoder(_GraphDecoder):
         pmask = _padding(attention_mask, B, P)
         dev, dt = inputs_embeds.device, inputs_embeds.dtype
         eos, _, min_new = self._special(eos_token_id, pad_token_id, min_new_tokens)
-        fill = -1 if eos is None else int(pad_token_id if pad_token_id else eos)      # HF: ``pad_token_id or eos_token_id`` -- pad 0 fills with eos
+        fill = -1 if eos is None else int(pad_token_id if pad_token_id else _first_eos(eos))      # HF: ``pad_token_id or eos_token_id`` -- pad 0 fills with eos (a set: its first id)
         # the rotary row of every item's first generated token (HF: position_ids[b, P-1] + 1), from the host copy of the mask
         if pmask is None:
             first = torch.full((B,), P, dtype=torch.long)
@@ -1214,7 +1254,10 @@ class GreedyDecoder(_GraphDecoder):
         ``num_beams`` > 1: HF's deterministic beam search (``_beam_search``, early_stopping False) with ``length_penalty`` and
         ``repetition_penalty`` -- per batch item the best finished beam, cropped to the longest, finished rows filled with ``pad_token_id or
         eos_token_id``; greedy only, no stopping criteria, the bf16 K/V cache -- or the fp8 one of a decoder built with ``fp8_beams=True`` --
-        (NotImplementedError otherwise)."""
+        (NotImplementedError otherwise).
+        ``eos_token_id``: None, an id, or a list; a list of several distinct ids is served by a decoder built with ``eos_sets=True`` (up to
+        ops.EOS_MAX ids, each in [0, V): any of them ends a row, all are blocked by ``min_new_tokens``, HF's pad default is the first) and
+        refused otherwise."""
         num_beams = int(num_beams)
         if num_beams < 1 or not float(repetition_penalty) > 0.0:
             raise ValueError(f"num_beams={num_beams} / repetition_penalty={repetition_penalty}: at least one beam, a positive penalty")
@@ -1272,7 +1315,7 @@ class T5GreedyDecoder(_GraphDecoder):
     the encoder's and decoder's SelfAttention and the decoder's EncDecAttention; ``lora_state``) are applied unmerged on every path."""
     _ACT_KIND = {"silu": 0, "swish": 0, "gelu_new": 1, "relu": 2, "gelu": 3}
 
-    def __init__(self, lm, fused: bool = True, weights: str = "bf16", kv_cache: str = "bf16"):
+    def __init__(self, lm, fused: bool = True, weights: str = "bf16", kv_cache: str = "bf16", eos_sets: bool = False):
         cfg = lm.config
         if getattr(cfg, "model_type", "") != "t5":
             raise NotImplementedError("T5GreedyDecoder handles T5ForConditionalGeneration")
@@ -1281,7 +1324,7 @@ class T5GreedyDecoder(_GraphDecoder):
         if check_kv_cache(kv_cache) != "bf16":
             raise NotImplementedError("kv_cache='fp8' is implemented for the Llama decoder only")
         has_lora = _lora_servable(lm)      # (adapters outside q / k / v of the attention blocks: NotImplementedError)
-        super().__init__(lm, fused, weights, kv_cache)
+        super().__init__(lm, fused, weights, kv_cache, eos_sets)
         self.H, self.dk, self.D = cfg.num_heads, cfg.d_kv, cfg.d_model
         self.eps = cfg.layer_norm_epsilon
         self.start = cfg.decoder_start_token_id if cfg.decoder_start_token_id is not None else cfg.pad_token_id
@@ -1579,6 +1622,11 @@ class T5GreedyDecoder(_GraphDecoder):
         V = logits.shape[-1]
         st["pen_seq"][:, 1:].copy_(st["run_seq"].view(B * K, N))
         st["pen_step"].copy_(step + 1)
+        if bm["kernel"] and "eos_t" in st:      # an eos set: the list instantiation of the same kernel
+            sc, ix = ops.beam_candidates_eos(logits, st["pen_seq"], st["pen_step"], st["run_scores"], st["eos_t"], bm["repetition_penalty"],
+                                             st["min_new"] + 1 if st["min_new"] > 0 else 0, out=(st["cand_score"], st["cand_idx"]),
+                                             workspace=st["cand_ws"])
+            return sc, ix.long()
         if bm["kernel"]:
             sc, ix = ops.beam_candidates(logits, st["pen_seq"], st["pen_step"], st["run_scores"], bm["repetition_penalty"], st["eos"],
                                          st["min_new"] + 1 if st["min_new"] > 0 else 0, out=(st["cand_score"], st["cand_idx"]), workspace=st["cand_ws"])
@@ -1591,7 +1639,8 @@ class T5GreedyDecoder(_GraphDecoder):
             lp = lp.scatter(1, ids, torch.where(g < 0, g * bm["repetition_penalty"], g / bm["repetition_penalty"]))[:, :V]
         if st["eos"] is not None and st["min_new"] > 0:
             lp = lp.clone()
-            lp[:, st["eos"]] = torch.where(step < st["min_new"], torch.full_like(lp[:, st["eos"]], float("-inf")), lp[:, st["eos"]])
+            for e in (st["eos"] if isinstance(st["eos"], tuple) else (st["eos"],)):      # (an eos set: every id of it)
+                lp[:, e] = torch.where(step < st["min_new"], torch.full_like(lp[:, e], float("-inf")), lp[:, e])
         acc = (lp.view(B, K, V) + st["run_scores"][:, :, None]).reshape(B, K * V)
         return torch.topk(acc, k=2 * K)
 
@@ -1618,7 +1667,7 @@ class T5GreedyDecoder(_GraphDecoder):
         ``num_beams`` > 1: HF's deterministic beam search (``_beam_search``, early_stopping False) with ``length_penalty`` and
         ``repetition_penalty`` -- the start token, then per batch item the best finished beam, cropped to the longest, finished rows filled
         with ``pad_token_id or eos_token_id``.  Sampling and stopping criteria are not served (NotImplementedError), nor is a repetition
-        penalty on one beam."""
+        penalty on one beam.  A list of several distinct eos ids: a decoder built with ``eos_sets=True`` (``GreedyDecoder.generate``)."""
         num_beams = int(num_beams)
         if num_beams < 1 or not float(repetition_penalty) > 0.0:
             raise ValueError(f"num_beams={num_beams} / repetition_penalty={repetition_penalty}: at least one beam, a positive penalty")
@@ -1637,7 +1686,7 @@ class T5GreedyDecoder(_GraphDecoder):
             if K > ops.BEAM_MAX_BEAMS or 2 * K > self.lm.lm_head.weight.shape[0]:
                 raise NotImplementedError(f"num_beams={K}: up to {ops.BEAM_MAX_BEAMS} beams, 2 x num_beams <= vocab_size")
             # HF fills with ``pad_token_id or eos_token_id``: pad 0 fills with eos
-            beam = dict(K=K, fill=-1 if eos_token_id is None else int(pad_token_id if pad_token_id else eos_token_id),
+            beam = dict(K=K, fill=-1 if eos_token_id is None else int(pad_token_id if pad_token_id else _first_eos(eos_token_id)),
                         repetition_penalty=float(repetition_penalty), length_penalty=1.0 if length_penalty is None else float(length_penalty))
         st = self._state(B, P, N, dev, dt, eos_token_id, beam["fill"] if beam else pad_token_id, min_new_tokens, pmask is not None, beam)
         valid = None if pmask is None else (pmask.to(dev) != 0)
@@ -1695,13 +1744,14 @@ def keyword_stop_plan(criteria) -> dict:
     return dict(stop_ids=[[int(v) for v in t.tolist()] for c in crit for t in c.keyword_ids], text_stop=text_stop)
 
 
-def make_decoder(lm, weights: str = "bf16", kv_cache: str = "bf16", fp8_beams: bool = False):
+def make_decoder(lm, weights: str = "bf16", kv_cache: str = "bf16", fp8_beams: bool = False, eos_sets: bool = False):
     """The graph decoder for a language model: Llama-architecture causal LMs and T5 seq2seq LMs; NotImplementedError otherwise.
     ``weights``: "bf16", or "fp8" / "mxfp4" (Llama only: GreedyDecoder); ``kv_cache``: "bf16", or "fp8" (likewise); ``fp8_beams``: GreedyDecoder's
-    (a T5 decoder has no fp8 cache and does not take it)."""
+    (a T5 decoder has no fp8 cache and does not take it); ``eos_sets``: both decoders' (requests with several distinct eos ids)."""
+    sets = dict(eos_sets=True) if eos_sets else {}
     if getattr(lm.config, "model_type", "") == "t5":
-        return T5GreedyDecoder(lm, weights=weights, kv_cache=kv_cache)
-    return GreedyDecoder(lm, weights=weights, kv_cache=kv_cache, **(dict(fp8_beams=True) if fp8_beams else {}))
+        return T5GreedyDecoder(lm, weights=weights, kv_cache=kv_cache, **sets)
+    return GreedyDecoder(lm, weights=weights, kv_cache=kv_cache, **(dict(fp8_beams=True) if fp8_beams else {}), **sets)
 
 
 def prompt_padding(attention_mask: Tensor) -> Tuple[Optional[bool], Tensor]:
@@ -1717,16 +1767,20 @@ def prompt_padding(attention_mask: Tensor) -> Tuple[Optional[bool], Tensor]:
 def decoder_for(owner, lm):
     """The graph decoder for ``lm``, cached on ``owner`` (attribute ``_decoder``): the cached one when it was built for this ``lm`` and the
     weights it re-packed are still the model's (``weights_key``) and in the owner's modes (attributes ``decode_weights`` and ``kv_cache``,
-    "bf16" when it has none; ``fp8_beams`` = "kv8" in its ``beam_search``), else a new one (``make_decoder``)."""
+    "bf16" when it has none; ``fp8_beams`` = "kv8" in its ``beam_search``; ``eos_sets`` = its ``eos_sets`` is "graph"), else a new one
+    (``make_decoder``)."""
     mode = check_decode_weights(getattr(owner, "decode_weights", "bf16"))
     kv = check_kv_cache(getattr(owner, "kv_cache", "bf16"))
     kv8 = "kv8" in check_beam_search(getattr(owner, "beam_search", "hf"))
+    sets = check_eos_sets(getattr(owner, "eos_sets", "hf")) == "graph"
     dec = getattr(owner, "_decoder", None)
     if (dec is None or dec.lm is not lm or dec.key != weights_key(lm) or getattr(dec, "weights", "bf16") != mode
-            or getattr(dec, "kv_cache", "bf16") != kv or getattr(dec, "fp8_beams", kv8) != kv8):      # (a T5 decoder has no such flag)
+            or getattr(dec, "kv_cache", "bf16") != kv or getattr(dec, "fp8_beams", kv8) != kv8      # (a T5 decoder has no such flag)
+            or getattr(dec, "eos_sets", False) != sets):
         kw = ({} if mode == "bf16" else dict(weights=mode))
         kw.update({} if kv == "bf16" else dict(kv_cache=kv))
         kw.update(dict(fp8_beams=True) if kv8 else {})
+        kw.update(dict(eos_sets=True) if sets else {})
         dec = owner._decoder = make_decoder(lm, **kw)      # (the default modes: the positional lm alone)
     return dec
 
@@ -1738,6 +1792,9 @@ class Envelope(NamedTuple):
     neutral: dict
     sampling: bool
     need_max_new: bool
+    # opt-in (eos_sets="graph"): several distinct eos ids (up to ops.EOS_MAX, each in [0, vocab_size)) stay on the decoders.  Always given by
+    # name (``_replace(eos_sets=True)``); it stands before the beam switches because tests/test_t5_beam_decode.py pins those as the last two fields
+    eos_sets: bool = False
     beams: bool = False      # opt-in (beam_search="graph"): Llama, num_beams > 1 with any positive repetition_penalty and any length_penalty
     t5_beams: bool = False   # opt-in (beam_search="graph+t5"): the same requests on a T5 as well
 
@@ -1763,13 +1820,18 @@ MODULE_ENVELOPE_T5_BEAMS = MODULE_ENVELOPE_BEAMS._replace(t5_beams=True)
 
 def envelope_for(owner, module: bool) -> Envelope:
     """The envelope a caller plans with: today's, or its beam twin when the owner opted in (attribute ``beam_search``, "hf" when it has none;
-    "graph+t5": the twin with ``t5_beams``; "+kv8" changes the decoder, not the envelope)."""
+    "graph+t5": the twin with ``t5_beams``; "+kv8" changes the decoder, not the envelope); an owner whose ``eos_sets`` is "graph" gets that
+    envelope's ``_replace(eos_sets=True)`` twin."""
     mode = check_beam_search(getattr(owner, "beam_search", "hf")).replace("+kv8", "")
     if mode == "graph+t5":
-        return MODULE_ENVELOPE_T5_BEAMS if module else GENERATE_ENVELOPE_T5_BEAMS
-    if module:
-        return MODULE_ENVELOPE_BEAMS if mode == "graph" else MODULE_ENVELOPE
-    return GENERATE_ENVELOPE_BEAMS if mode == "graph" else GENERATE_ENVELOPE
+        env = MODULE_ENVELOPE_T5_BEAMS if module else GENERATE_ENVELOPE_T5_BEAMS
+    elif module:
+        env = MODULE_ENVELOPE_BEAMS if mode == "graph" else MODULE_ENVELOPE
+    else:
+        env = GENERATE_ENVELOPE_BEAMS if mode == "graph" else GENERATE_ENVELOPE
+    if check_eos_sets(getattr(owner, "eos_sets", "hf")) == "graph":      # (else: the very objects above)
+        env = env._replace(eos_sets=True)
+    return env
 
 
 def generated_length(lm, request: dict, P: int) -> Optional[Tuple[int, Optional[int]]]:
@@ -1790,7 +1852,7 @@ def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: E
     """The keyword arguments of ``decoder_for(owner, lm).generate(inputs_embeds, max_new_tokens, **plan)`` for a request HF ``generate`` would get
     as ``generate(inputs_embeds=..., attention_mask=..., **request)``, or None when it is outside what the graph decoders reproduce (then HF
     ``generate`` runs it).  Inside: a Llama the decoder states (``llama_state``) or a T5 language model on the device, at most one distinct eos
-    id, only keys ``env`` knows, one beam, neutral penalties (or, where
+    id (under ``env.eos_sets``: up to ops.EOS_MAX, each in [0, vocab_size)), only keys ``env`` knows, one beam, neutral penalties (or, where
     ``env.beams`` -- for a T5 ``env.t5_beams`` -- says so, deterministic beam search with a positive repetition penalty), a 0 / 1
     attention mask with a token in every row (a padded mask goes into the plan as its host copy); greedy, or -- Llama, where ``env`` serves it --
     sampling with temperature / top_k / top_p; ``stopping_criteria`` None or (Llama) KeywordsStoppingCriteria objects (eval/utils/builder_utils.py:
@@ -1824,9 +1886,13 @@ def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: E
         return None
     gc = getattr(lm, "generation_config", None)     # HF generate's defaults come from the generation config
     eos = request.get("eos_token_id", getattr(gc, "eos_token_id", None))
-    if isinstance(eos, (list, tuple)) and len(set(eos)) > 1:      # several distinct eos ids (Llama-3.1-Instruct ships three): HF generate
-        return None
-    if isinstance(eos, (list, tuple)) and len(eos) > 1:      # (one id, repeated)
+    if isinstance(eos, (list, tuple)) and len(set(eos)) > 1:      # several distinct eos ids (Llama-3.1-Instruct ships three): HF generate,
+        # or -- under ``env.eos_sets`` -- the decoders' eos sets: up to ops.EOS_MAX ids, each a token of the vocabulary
+        V = getattr(lm.config, "vocab_size", 0)
+        if not env.eos_sets or len(set(eos)) > ops.EOS_MAX or any(not isinstance(e, int) or isinstance(e, bool) or not 0 <= e < V for e in eos):
+            return None
+        eos = list(eos)
+    elif isinstance(eos, (list, tuple)) and len(eos) > 1:      # (one id, repeated)
         eos = [eos[0]]
     plan = dict(eos_token_id=eos,
                 pad_token_id=request.get("pad_token_id", getattr(gc, "pad_token_id", None)), min_new_tokens=int(request.get("min_new_tokens", 0) or 0))

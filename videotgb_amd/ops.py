@@ -684,6 +684,66 @@ def beam_candidates(logits: Tensor, seq: Tensor, step: Tensor, running: Tensor, 
     return out
 
 
+# ---- eos-id sets on the graph decoders (opt-in: eos_sets="graph").  A request's eos ids as a device int32 list of up to EOS_MAX entries
+# (VTGB_LLM_EOS_MAX of include/vtgb.h), read by vtgb_llm_pick_greedy and vtgb_llm_beam_candidates_eos inside the captured step.
+EOS_MAX = 8
+
+
+def eos_list(ids, V: int, device) -> Tensor:
+    """The device list the eos-set entries read: int32 [n], 0 <= n <= EOS_MAX, every id in [0, V) -- checked HERE, on the host, because the
+    entries cannot read a device list (ValueError).  Duplicates are allowed.  Builds a tensor: call it outside any capture."""
+    ids = [int(v) for v in ids]
+    if len(ids) > EOS_MAX:
+        raise ValueError(f"{len(ids)} eos ids: up to {EOS_MAX} are taken")
+    if any(not 0 <= v < V for v in ids):
+        raise ValueError(f"eos ids {ids}: every id has to be in [0, {V})")
+    return torch.tensor(ids, dtype=torch.int32, device=device)
+
+
+def pick_greedy(logits: Tensor, step: Tensor, eos_ids: Tensor, fin: Tensor, tok: Tensor, out: Tensor, min_new: int = 0, pad: int = 0) -> Tensor:
+    """The greedy emission of one decode step in one launch (vtgb_llm_pick_greedy): logits [B, V] bf16 / fp32, ``step`` device int64,
+    ``eos_ids`` device int32 [n <= EOS_MAX] (``eos_list``) -> per row the lowest index of the maximum (torch.argmax), the listed ids at -inf
+    while step < min_new; a row with ``fin`` [B] bool set emits ``pad`` and keeps it, another row's ``fin`` is set when its token is listed.
+    The token is written to ``tok`` [B] int64 and ``out[:, step]`` ([B, N] int64).  Every operand is the caller's: nothing is allocated, so
+    the call can be captured.  Returns ``tok``."""
+    _need_cuda(logits, step, eos_ids, fin, tok, out)
+    B, V = logits.shape
+    N = out.shape[1]
+    assert fin.shape == (B,) and tok.shape == (B,) and out.shape == (B, N) and eos_ids.dim() == 1 and step.numel() == 1
+    assert fin.dtype == torch.bool and tok.dtype == torch.int64 and out.dtype == torch.int64 and step.dtype == torch.int64 and eos_ids.dtype == torch.int32
+    assert logits.is_contiguous() and out.is_contiguous() and tok.is_contiguous() and fin.is_contiguous() and eos_ids.is_contiguous()
+    n = eos_ids.numel()
+    a = L.LlmPickGreedyArgs(dtype_code(logits.dtype), B, V, N, int(min_new), n, int(pad), _ptr(logits), _ptr(step), _ptr(eos_ids) if n else None,
+                            _ptr(fin), _ptr(tok), _ptr(out))
+    L.check(L.lib().vtgb_llm_pick_greedy(C.byref(a), _stream()))
+    return tok
+
+
+def beam_candidates_eos(logits: Tensor, seq: Tensor, step: Tensor, running: Tensor, eos_ids: Tensor, repetition_penalty: float = 1.0,
+                        min_new: int = 0, out: Optional[Tuple[Tensor, Tensor]] = None, workspace: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """``beam_candidates`` with a device list of eos ids (vtgb_llm_beam_candidates_eos; ``eos_ids`` int32 [n <= EOS_MAX], ``eos_list``): every
+    listed id is at -inf while step < min_new.  The workspace is ``beam_candidates_workspace_bytes``; with a one-element list the result equals
+    ``beam_candidates``' bit for bit."""
+    _need_cuda(logits, seq, step, running, eos_ids)
+    R, V = logits.shape
+    B, K = running.shape
+    N = seq.shape[1]
+    assert R == B * K and seq.shape == (R, N) and seq.dtype == torch.int64 and step.dtype == torch.int64 and running.dtype == torch.float32
+    assert logits.is_contiguous() and seq.is_contiguous() and running.is_contiguous()
+    assert eos_ids.dim() == 1 and eos_ids.dtype == torch.int32 and eos_ids.is_contiguous()
+    if out is None:
+        out = (torch.empty(B, 2 * K, dtype=torch.float32, device=logits.device), torch.empty(B, 2 * K, dtype=torch.int32, device=logits.device))
+    need = beam_candidates_workspace_bytes(R, K, V)
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=logits.device)
+    n = eos_ids.numel()
+    a = L.LlmBeamCandidatesEosArgs(dtype_code(logits.dtype), R, K, V, N, n, int(min_new), float(repetition_penalty), _ptr(logits),
+                                   _ptr(seq) if N else None, _ptr(step), _ptr(running), _ptr(eos_ids) if n else None, _ptr(out[0]), _ptr(out[1]),
+                                   _ptr(workspace), workspace.numel() * workspace.element_size())
+    L.check(L.lib().vtgb_llm_beam_candidates_eos(C.byref(a), _stream()))
+    return out
+
+
 # ---- beam search on the T5 decode step (opt-in: beam_search="graph+t5").  vtgb_llm_attention_rows_beam keeps its scores and the table rows of a
 # (row, head) in LDS: the largest t_pad (= decoder positions of a state) it is launched with, VTGB_LLM_ATTN_ROWS_BEAM_MAX_T of include/vtgb.h.
 ATTENTION_ROWS_BEAM_MAX_KEYS = 1920
