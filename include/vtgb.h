@@ -669,6 +669,40 @@ typedef struct {
 size_t vtgb_raft_stem_workspace_bytes(const vtgb_raft_stem_args* a);
 int vtgb_raft_stem(const vtgb_raft_stem_args* a, vtgb_stream_t stream);
 
+/* Unit-level surface of ONE layer1 convolution of vtgb_raft_encoder at VTGB_F16C8 (extractor.py:136-143: 3x3, stride 1, 64 -> 64 channels at half resolution;
+ * added at version 601 without a bump), launched by the function the encoder itself calls (csrc/raft_enc.hip enc_conv_h8), through the caller's workspace.
+ *   variant 0: the implicit GEMM of csrc/gemm_h8.hip on its 64-wide tile -- every pixel's 256 bytes staged once per tap;
+ *   variant 1: the row-resident kernel (csrc/conv64.hip layer1_h8_kernel; 16 <= W <= 112, H >= 4, else VTGB_EUNSUPPORTED): every input row staged once into
+ *              an LDS ring, the weights in registers, the taps as shifted fragment reads.  It writes no moments;
+ *   variant 2: (VTGB_CONV_OUT_F32, H * W >= 256) variant 1's rows, and the moments added per 256-row tile in the order of variant 0's epilogue by a pass of
+ *              their own -- variant 0's moments bit for bit.
+ * Every output element is accumulated in one order -- the bias, the nine fp16 k-tiles in tap order, the nine correction k-tiles -- so the variants' rows are
+ * bit-identical.  x: f16c8 pair rows [n_images * H * W, 128 16-bit units] (vtgb_pair_pack); weights / bias / scale: the encoder table's entries of the
+ * convolution ([64, 1152] 16-bit units, [64] fp32, one int32 of weights[40]).
+ * out_kind VTGB_CONV_OUT_F32 (fnet): out = fp32 rows [M, 64]; moments (variants 0, 2; H * W >= 256; NULL = none) [n_images, 64, 2] = per image and channel
+ *   the (sum, sum of squares) of the stored values;
+ * VTGB_CONV_OUT_PAIR_F16C8 (cnet, BatchNorm folded): out = relu(.) as pair rows [M, 128 units], or with resid (f16c8 pair rows [M, 128]) the ResidualBlock's
+ *   tail relu(resid + relu(.)); VTGB_CONV_OUT_PAIR_BF16: that tail as a bf16 pair (resid required).
+ * VTGB_EINVAL on the host, before any launch, for NULL args, bad dims / variant / out_kind, resid or moments outside their out_kind, moments with variant 1 or
+ * H * W < 256, variant 2 without them, a NULL operand or a misaligned one (16 bytes; scale: 4); VTGB_EWORKSPACE for a NULL or short workspace.  What
+ * tests/test_gpu_layer1_h8.py checks. */
+typedef struct {
+    int32_t n_images, H, W;     /* the convolution's own grid */
+    int32_t variant;            /* 0: implicit GEMM, 1: row-resident kernel, 2: row-resident kernel + tile-order moments */
+    int32_t out_kind;           /* VTGB_CONV_OUT_F32, VTGB_CONV_OUT_PAIR_BF16 or VTGB_CONV_OUT_PAIR_F16C8 */
+    const void* x;              /* [n_images * H * W, 128] 16-bit units */
+    const void* weights;        /* [64, 1152] 16-bit units */
+    const float* bias;          /* [64] */
+    const int32_t* scale;       /* the E8M0 byte of the weights' scale */
+    const void* resid;          /* pair rows only: f16c8 pair rows [M, 128] or NULL */
+    void* out;
+    float* moments;             /* VTGB_CONV_OUT_F32, variants 0 / 2: [n_images, 64, 2] or NULL */
+    void* workspace;
+    size_t workspace_bytes;
+} vtgb_raft_layer1_h8_args;
+size_t vtgb_raft_layer1_h8_workspace_bytes(const vtgb_raft_layer1_h8_args* a);
+int vtgb_raft_layer1_h8(const vtgb_raft_layer1_h8_args* a, vtgb_stream_t stream);
+
 /* CorrBlock.__init__ (raft_utils/corr.py:12-27; the all-pairs product :52-60): for every pair the correlation of each
  * pixel of image 1 with every pixel of image 2 over the `dim` = 256 features, divided by sqrt(dim), and its three
  * avg_pool2d(2, stride 2) -- one kernel, the four levels are its only output.  Pair n uses the feature maps of images

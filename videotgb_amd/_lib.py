@@ -49,6 +49,7 @@ EXPORTS = [
     "vtgb_llm_decode_attention_beam", "vtgb_llm_beam_candidates", "vtgb_llm_attention_rows_beam", "vtgb_llm_decode_attention_beam_fp8",
     "vtgb_pack_skinny_weight_mxfp4_bytes", "vtgb_pack_skinny_weight_mxfp4", "vtgb_gemm_skinny_mxfp4",
     "vtgb_raft_stem_workspace_bytes", "vtgb_raft_stem", "vtgb_llm_lora_parts", "vtgb_llm_pick_greedy", "vtgb_llm_beam_candidates_eos",
+    "vtgb_raft_layer1_h8_workspace_bytes", "vtgb_raft_layer1_h8",
 ]
 COMM_ID_BYTES = 128
 
@@ -181,6 +182,12 @@ class RaftStemArgs(C.Structure):
     """vtgb_raft_stem_args: the encoders' bf16x3 stem alone (variant 0: pack + implicit GEMM, 1: fused) through the caller's workspace."""
     _fields_ = [("n_images", i32), ("H", i32), ("W", i32), ("variant", i32), ("out_kind", i32), ("images", vp), ("weights", vp), ("bias", vp), ("out", vp),
                 ("moments", vp), ("workspace", vp), ("workspace_bytes", sz)]
+
+
+class RaftLayer1H8Args(C.Structure):
+    """vtgb_raft_layer1_h8_args: one f16c8 layer1 convolution of the encoders (variant 0: implicit GEMM, 1: row-resident kernel, 2: + tile-order moments)."""
+    _fields_ = [("n_images", i32), ("H", i32), ("W", i32), ("variant", i32), ("out_kind", i32), ("x", vp), ("weights", vp), ("bias", vp), ("scale", vp),
+                ("resid", vp), ("out", vp), ("moments", vp), ("workspace", vp), ("workspace_bytes", sz)]
 
 
 class RaftCorrArgs(C.Structure):
@@ -339,6 +346,10 @@ def lib() -> C.CDLL:
     L.vtgb_raft_stem.restype = C.c_int
     L.vtgb_raft_stem_workspace_bytes.argtypes = [C.POINTER(RaftStemArgs)]
     L.vtgb_raft_stem_workspace_bytes.restype = sz
+    L.vtgb_raft_layer1_h8.argtypes = [C.POINTER(RaftLayer1H8Args), vp]
+    L.vtgb_raft_layer1_h8.restype = C.c_int
+    L.vtgb_raft_layer1_h8_workspace_bytes.argtypes = [C.POINTER(RaftLayer1H8Args)]
+    L.vtgb_raft_layer1_h8_workspace_bytes.restype = sz
     L.vtgb_raft_update.argtypes = [C.POINTER(RaftUpdateArgs), vp]
     L.vtgb_raft_update.restype = C.c_int
     L.vtgb_raft_update_workspace_bytes.argtypes = [C.POINTER(RaftUpdateArgs)]

@@ -266,6 +266,11 @@ int cu_count();   // compute units of the current device (gemm_pp.hip)
 bool conv3x3_c64_supported(int H, int W);
 int launch_conv3x3_c64(const void* in, const void* w, const float* bias, float* out_f32, float* stats, float* stats_part, void* out_bf16, const void* resid,
                        int n_img, int H, int W, int relu, int post_relu, hipStream_t s);
+// the same convolution over f16c8 pair rows [M, 128 16-bit units] against the f16c8 table entry w [64, 1152] + its scale byte, with launch_conv_h8's bits:
+// fp32 rows [M, 64] (out_f32) or relu(.) / relu(resid + relu(.)) (resid: f16c8 pair rows) as f16c8 or (out_bf16) bf16 pair rows (out_pair) -- one of the two
+bool layer1_h8_supported(int H, int W);
+int launch_layer1_h8(const void* in, const void* w, const float* bias, const int* scale, float* out_f32, void* out_pair, const void* resid, int out_bf16, int n_img, int H,
+                     int W, hipStream_t s);
 
 struct LnDesc {
     int dtype, M, D;

@@ -19,6 +19,8 @@
 // Epilogues: fp32 output + per-(image, channel) sum / sum of squares for InstanceNorm (fnet: reduced in registers / LDS per run, one
 // atomic per channel and run -- stored without atomics when a workgroup owns the image), or bf16 output with ReLU / skip + ReLU
 // (cnet, BatchNorm folded into the weights).
+#include <type_traits>
+#include <utility>
 #include "common.h"
 #include "pair_h8.h"
 
@@ -496,6 +498,218 @@ __global__ __launch_bounds__(512) void stem7x7_kernel(const StemParams p) {
 #endif
 }
 
+// ---------------------------------------------------------------------------------------
+// layer1 at VTGB_F16C8: the same 3x3 / stride 1 / 64 -> 64 convolution over f16c8 pair rows [M, 128 16-bit units] (pair_h8.h: 128 bytes of fp16 values +
+// 128 correction bytes per pixel), with the rows resident.  On gemm_h8.hip's 256 x 64 tile every pixel's 256 bytes were staged nine times (once per tap, 40
+// LDS-DMA pieces per 512 matrix-pipe cycles) and the 8 KiB weight tile once per k-tile of every m-tile: 27-30 % matrix-pipe busy.  Here
+//   * a persistent workgroup (8 waves) walks runs of image rows ONE output row per step; LDS holds a ring of 4 input rows x (W + 2, rounded up to 4) pixel slots
+//     x 256 bytes, sized from W (112 pixels: 29 696 B per row), filled one row ahead by LDS-DMA -- slot 0 and W + 1 are the zero columns, rows -1 and H the
+//     DMA's out-of-range reads; the 16-byte chunks of a slot are XOR-swizzled by (slot & 15);
+//   * waves form a 4 (16-channel blocks) x 2 (halves of the row: 4 pixel fragments each) grid; a wave keeps the nine taps' fp16 AND correction weight fragments
+//     of its 16 channels in registers (9 x 16 = 144 VGPRs) for the whole launch: nothing but the pixels passes through LDS;
+//   * taps are shifted fragment reads (slot px + kx of ring row y + ky - 1), 36 groups per row step, each requested one group ahead of the MFMAs that consume it
+//     into three register sets (the order pinned by sched_group_barrier: hipcc otherwise puts every read in front of its MFMA).  ds_read_b128 moves 256 B/clk
+//     per CU, so the four channel-block waves' reads of a row equal its matrix work per SIMD; the bias is read back from LDS at every row start.
+// Arithmetic: per output element conv_h8_kernel's chain -- the accumulator starts at the bias, takes the nine fp16 k-tiles in tap order (each as its two
+// 32-deep halves, channels 0..31 then 32..63), then the nine correction k-tiles (one scaled fp8 MFMA each, the weight operand's E8M0 byte from the table), with
+// the operand bytes in the lane and k positions of gemm_h8.hip's fragment reads (chunk fg / fg + 4 of the 128-byte k-tile row).  Same instructions, same
+// operands, same order: the fp32 sums have that kernel's bits, and the epilogues apply pair_h8.h's functions to them as its epilogues do.
+// MODE 0: fp32 rows [M, 64] (fnet; the moments are the caller's: raft_enc.hip); MODE 1: relu(.) as a pair row; MODE 2: relu(resid + relu(.)), resid an f16c8
+// pair, as a pair row.  Pair rows are f16c8 or (out_bf16) bf16 pairs.  A lane's accumulator holds four consecutive channels of one pixel -- the group
+// h8_split4 / pair_split4 take -- so the rows are stored from the accumulators.
+// ---------------------------------------------------------------------------------------
+constexpr int L1_R = 4;                    // ring rows: y - 1, y, y + 1 and the row in flight
+constexpr int L1_MAX_W = 112;
+constexpr int L1_READ_SPAN = 130 * 256;    // a fragment read reaches slot 127 + 2 of its ring row, whatever W is (results of pixels >= W are not stored)
+typedef int l1_i32x4 __attribute__((ext_vector_type(4)));
+typedef int l1_i32x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 l1_f16x8 __attribute__((ext_vector_type(8)));
+
+template <class F, int... G>
+__device__ __forceinline__ void l1_static_for(std::integer_sequence<int, G...>, F&& f) { (f(std::integral_constant<int, G>{}), ...); }
+
+struct Layer1H8Params {
+    const char* in;        // [n_img * H * W, 256 bytes]
+    const char* w;         // [64, 2304 bytes]: nine fp16 k-tiles of 128 bytes (tap order), then the nine correction k-tiles (ops.py h8_conv_pack)
+    const float* bias;     // [64]
+    const int* scale;      // the E8M0 byte of 2^-11 / sw
+    float* out_f32;        // MODE 0
+    char* out_pair;        // MODE 1, 2: [M, 256 bytes]
+    const char* resid;     // MODE 2: f16c8 pair rows [M, 256 bytes]
+    int n_img, H, W, out_bf16;
+    int parts, rows_per_part, row_bytes;
+};
+
+template <int MODE, int OBF>
+__global__ __launch_bounds__(512) void layer1_h8_kernel(const Layer1H8Params p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    extern __shared__ __attribute__((aligned(16))) char ring[];
+    const int tid = threadIdx.x, lane = tid & 63, fr = lane & 15, fg = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wn = wave & 3, wm = wave >> 2;      // (the two row halves of a channel block share a SIMD: 4 + 3 fragments at W = 112)
+    const int H = p.H, W = p.W, row_bytes = p.row_bytes;
+    const int sc_w = *p.scale;
+
+    // ---- this wave's weights: per tap the two 32-deep halves of the fp16 k-tile and the 64-byte halves of the correction k-tile, output channel 16 wn + fr
+    l1_i32x4 wh[9][2];
+    l1_i32x8 wc[9];
+    {
+        const char* const wrow = p.w + (wn * 16 + fr) * 2304 + fg * 16;
+#pragma unroll
+        for (int t = 0; t < 9; t++) {
+            wh[t][0] = *reinterpret_cast<const l1_i32x4*>(wrow + t * 128);
+            wh[t][1] = *reinterpret_cast<const l1_i32x4*>(wrow + t * 128 + 64);
+            wc[t].lo = *reinterpret_cast<const l1_i32x4*>(wrow + (9 + t) * 128);
+            wc[t].hi = *reinterpret_cast<const l1_i32x4*>(wrow + (9 + t) * 128 + 64);
+        }
+    }
+    // the bias lives behind the ring (read back at every row start: four registers the read-ahead needs)
+    float* const bias_s = reinterpret_cast<float*>(ring + (L1_R - 1) * row_bytes + L1_READ_SPAN);
+    if (tid < 64) bias_s[tid] = p.bias[tid];
+    __syncthreads();
+
+    // ---- staging: a piece = 4 pixel slots x 256 bytes; wave w issues pieces w, w + 8, ..  Lane l of a piece: slot 4 piece + (l >> 4), LDS chunk position
+    // l & 15 <- global chunk (l & 15) ^ (slot & 15) of pixel slot - 1; slots outside [1, W] read out of range (zeros)
+    constexpr unsigned OOB = 0x80000000u;
+    const int n_pieces = row_bytes >> 10;
+    // (piece q * 8 + wave sits 32 slots = 8192 bytes behind piece wave, in LDS and in the image row, with the same swizzle term)
+    const int dma_x = wave * 4 + (lane >> 4) - 1;
+    const unsigned dma_off0 = (unsigned)(dma_x * 256 + (((lane & 15) ^ ((dma_x + 1) & 15)) << 4));
+    // ---- fragment reads: pixel px = 64 wm + 16 jj + fr reads slot px + kx of ring row y + ky - 1: chunk fg of the fp16 half; its second 32-deep half and the
+    // correction halves are chunks + 4, + 8, + 12 = byte ^ 64, ^ 128, ^ 192; fragment jj sits 16 slots = 4096 bytes further with the same swizzle term
+    unsigned x_off[3];
+#pragma unroll
+    for (int kx = 0; kx < 3; kx++) {
+        const int slot = wm * 64 + fr + kx;
+        x_off[kx] = (unsigned)(slot * 256 + ((fg ^ (slot & 15)) << 4));
+    }
+    const int nj = W - wm * 64 >= 64 ? 4 : W - wm * 64 <= 0 ? 0 : (W - wm * 64 + 15) >> 4;      // this wave's fragments that hold pixels
+    typedef __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned u32x4_t;
+    typedef __attribute__((__vector_size__(2 * sizeof(unsigned)))) unsigned u32x2_t;
+    // byte offset of (pixel fragment jj, this lane's four channels) inside an output image row; pixels beyond the row store out of range
+    constexpr int OPX = 256;                              // bytes per output pixel: 64 fp32 or a 128-unit pair row
+    constexpr int OCH = MODE == 0 ? 4 : 2;
+    const int px0 = wm * 64 + fr;                         // fragment jj: pixel px0 + 16 jj, 16 * OPX bytes further
+    const unsigned o_off0 = (unsigned)(px0 * OPX + (wn * 16 + fg * 4) * OCH);
+
+    const int n_units = p.n_img * p.parts;
+    for (int unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
+        const int img = unit / p.parts, y0 = (unit - img * p.parts) * p.rows_per_part;
+        if (y0 >= H) continue;
+        const int y1 = y0 + p.rows_per_part < H ? y0 + p.rows_per_part : H;
+        const int64_t ioff = (int64_t)img * H * W * 256;
+        const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.in + ioff), 0, H * W * 256, 0x00020000);
+        const auto orsrc = __builtin_amdgcn_make_buffer_rsrc(MODE == 0 ? (void*)(reinterpret_cast<char*>(p.out_f32) + ioff) : (void*)(p.out_pair + ioff), 0, H * W * OPX, 0x00020000);
+        const auto rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>((MODE == 2 ? p.resid : p.in) + ioff), 0, H * W * 256, 0x00020000);
+#define L1_ISSUE(yy)                                                                                                          \
+        {                                                                                                                      \
+            const int so_ = ((yy) >= 0 && (yy) < H) ? (yy) * W * 256 : 0x7FFFFF00;      /* rows -1 and H: out of range, zeros */  \
+            char* const dst_ = ring + ((yy) & (L1_R - 1)) * row_bytes + wave * 1024;                                           \
+            _Pragma("unroll") for (int q = 0; q < 4; q++)                                                                      \
+                if (q * 8 + wave < n_pieces)                                                                                   \
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (c64_lptr_t)(dst_ + q * 8192), 16,                          \
+                                                             (dma_x + q * 32 >= 0 && dma_x + q * 32 < W) ? dma_off0 + q * 8192u : OOB, so_, 0, 0); \
+        }
+        __builtin_amdgcn_s_waitcnt(0x0F70);               // (my rows of the previous unit have landed / been stored)
+        __builtin_amdgcn_s_barrier();                     // the previous unit's last rows have been consumed by every wave: the ring is free
+        L1_ISSUE(y0 - 1)
+        L1_ISSUE(y0)
+        L1_ISSUE(y0 + 1)
+        // One output row per step.  NJ: the wave's pixel fragments (3 for the second half of a 112-pixel row; waves with fewer run 4: what they read beyond
+        // the row is inside the allocation and never stored).  NST stores per step, always issued, so the counted wait is exact: behind row y + 1 (requested one
+        // step ago) only the previous step's stores are outstanding.
+        auto step = [&](auto nj_c, const int y) {
+            constexpr int NJ = decltype(nj_c)::value;
+            constexpr int NST = (MODE == 0 ? 1 : 2) * NJ;
+            if (y == y0) __builtin_amdgcn_s_waitcnt(0x0F70);
+            else __builtin_amdgcn_s_waitcnt(0x0F70 | NST);
+            __builtin_amdgcn_s_barrier();                 // everybody's pieces of row y + 1 are in LDS; everybody is done with row y - 2
+            u32x2_t rh[NJ], rl[NJ];
+            if constexpr (MODE == 2) {                    // the skip operand (requested BEFORE this step's DMA: vmcnt completes in order)
+#pragma unroll
+                for (int jj = 0; jj < NJ; jj++) {
+                    const unsigned off = px0 + jj * 16 < W ? o_off0 + (unsigned)(jj * 16 * OPX + y * W * 256) : OOB;
+                    rh[jj] = __builtin_bit_cast(u32x2_t, __builtin_amdgcn_raw_buffer_load_b64(rrsrc, off, 0, 0));
+                    rl[jj] = __builtin_bit_cast(u32x2_t, __builtin_amdgcn_raw_buffer_load_b64(rrsrc, off != OOB ? off + 128u : OOB, 0, 0));
+                }
+            }
+            L1_ISSUE(y + 2)
+            f32x4 acc[NJ];
+#pragma unroll
+            for (int jj = 0; jj < NJ; jj++) acc[jj] = *reinterpret_cast<const f32x4*>(bias_s + wn * 16 + fg * 4);
+            // 36 read groups of NJ fragment reads -- per tap the two 32-deep fp16 halves (groups 0..17), then per tap the two 64-byte halves of the
+            // correction k-tile (18..35) -- each requested ONE group ahead of the MFMAs that consume it (left to itself hipcc put every read right in
+            // front of its MFMA: lgkmcnt(0) per instruction).  fp16: NJ MFMAs per group; correction: NJ MFMAs per pair of groups.
+            l1_i32x4 xg[3][NJ];                           // group g lives in set g % 3 (a correction batch reads two sets while the third is in flight)
+#define L1_READ(g)                                                                                                             \
+            {                                                                                                                  \
+                constexpr int t_ = (g) < 18 ? (g) / 2 : ((g) - 18) / 2;                                                        \
+                constexpr unsigned cx_ = (g) < 18 ? ((g) & 1) * 64u : 128u + ((g) & 1) * 64u;                                  \
+                const char* const rowp_ = ring + ((y + t_ / 3 - 1) & (L1_R - 1)) * row_bytes;                                  \
+                _Pragma("unroll") for (int jj = 0; jj < NJ; jj++)                                                              \
+                    xg[(g) % 3][jj] = *reinterpret_cast<const l1_i32x4*>(rowp_ + (x_off[t_ % 3] ^ cx_) + jj * 4096);           \
+            }
+            L1_READ(0)
+            __builtin_amdgcn_sched_barrier(0);
+            l1_static_for(std::make_integer_sequence<int, 36>{}, [&](auto gc) {
+                constexpr int g = decltype(gc)::value;
+                if constexpr (g + 1 < 36) { L1_READ(g + 1) }
+                if constexpr (g < 18) {             // the fp16 k-tile of tap g / 2: channels 0..31 (even g), then 32..63
+#pragma unroll
+                    for (int jj = 0; jj < NJ; jj++)
+                        acc[jj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(l1_f16x8, wh[g / 2][g & 1]), __builtin_bit_cast(l1_f16x8, xg[g % 3][jj]), acc[jj], 0, 0, 0);
+                } else if constexpr ((g & 1) != 0) {      // the correction k-tile of tap (g - 18) / 2: weights e4m3 (scaled by the table's byte), activations e5m2 (scale 1)
+#pragma unroll
+                    for (int jj = 0; jj < NJ; jj++) {
+                        l1_i32x8 xc;
+                        xc.lo = xg[(g - 1) % 3][jj]; xc.hi = xg[g % 3][jj];
+                        acc[jj] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wc[(g - 18) / 2], xc, acc[jj], 0, 1, 0, sc_w, 0, 127);
+                    }
+                }
+                // (pin the order inside the group: the next group's reads first -- hipcc otherwise sinks them below the MFMAs to reuse their registers)
+                if constexpr (g + 1 < 36) __builtin_amdgcn_sched_group_barrier(0x100, NJ, 0);
+                if constexpr (g < 18 || (g & 1) != 0) __builtin_amdgcn_sched_group_barrier(0x008, NJ, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            });
+#undef L1_READ
+            // ---- epilogue: NST stores, always issued
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int jj = 0; jj < NJ; jj++) {
+                const bool ok = px0 + jj * 16 < W;
+                const unsigned off = ok ? o_off0 + (unsigned)(jj * 16 * OPX + y * W * OPX) : OOB;
+                f32x4 v = acc[jj];
+                if constexpr (MODE == 0) {
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), orsrc, off, 0, 0);
+                } else {
+                    v = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+                    if constexpr (MODE == 2) {
+                        v += h8_join4(rh[jj], rl[jj]);
+                        v = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+                    }
+                    u32x2_t hu, lu;
+                    if constexpr (OBF) {
+                        bf16x4 hi, lo;
+                        pair_split4(v, hi, lo);
+                        hu = __builtin_bit_cast(u32x2_t, hi); lu = __builtin_bit_cast(u32x2_t, lo);
+                    } else {
+                        h8_split4(v, hu, lu);
+                    }
+                    __builtin_amdgcn_raw_buffer_store_b64(hu, orsrc, off, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b64(lu, orsrc, ok ? off + 128u : OOB, 0, 0);      // the second half: 64 units further
+                }
+            }
+        };
+        if (nj == 3) {
+            for (int y = y0; y < y1; y++) step(std::integral_constant<int, 3>{}, y);
+        } else {
+            for (int y = y0; y < y1; y++) step(std::integral_constant<int, 4>{}, y);
+        }
+#undef L1_ISSUE
+    }
+#endif
+}
+
 }   // namespace
 
 // x [n_img, H, W, 64] bf16 -> 3x3 / stride 1 / pad 1 convolution with w [64, 576] (+ bias): fp32 [.., 64] + moments (out_f32 != NULL) or bf16
@@ -589,4 +803,47 @@ int launch_stem7x7_x3(const float* img, const void* w, const float* bias, float*
                       int W, hipStream_t s) {
     VTGB_REQUIRE((out_f32 != nullptr) != (out_pair != nullptr), VTGB_EINVAL, "stem7x7 x3: exactly one of the fp32 rows and the pair rows");
     return stem7x7_launch(true, img, w, bias, out_f32, stats, stats_part, out_pair, h8, n_img, H, W, out_pair ? 1 : 0, s);
+}
+
+// layer1 at VTGB_F16C8 with the rows resident: x = f16c8 pair rows [n_img * H * W, 128 units], w [64, 1152 units] + scale byte (the encoder table's entries).
+// Exactly one output: out_f32 (fp32 rows [M, 64]) or out_pair (relu(.), or relu(resid + relu(.)) with an f16c8 pair `resid`, as f16c8 or bf16 pair rows).
+// Every element has launch_conv_h8's bits (layer1_h8_kernel).
+bool layer1_h8_supported(int H, int W) { return W >= 16 && W <= L1_MAX_W && H >= 4 && (int64_t)H * W * 256 < 0x7FFFFF00ll; }
+
+int launch_layer1_h8(const void* in, const void* w, const float* bias, const int* scale, float* out_f32, void* out_pair, const void* resid, int out_bf16, int n_img, int H,
+                     int W, hipStream_t s) {
+    VTGB_REQUIRE(n_img > 0 && layer1_h8_supported(H, W), VTGB_EUNSUPPORTED, "layer1_h8: %d images of %d x %d outside 16 <= W <= %d, H >= 4", n_img, H, W, L1_MAX_W);
+    VTGB_REQUIRE(in && w && bias && scale && ((out_f32 != nullptr) != (out_pair != nullptr)) && (!resid || out_pair) && (!out_bf16 || resid), VTGB_EINVAL,
+                 "layer1_h8: operands, the scale byte and exactly one of the fp32 rows and the pair rows (resid belongs to pair rows, bf16 pairs to the residual tail)");
+    Layer1H8Params p;
+    p.in = (const char*)in; p.w = (const char*)w; p.bias = bias; p.scale = scale; p.out_f32 = out_f32; p.out_pair = (char*)out_pair; p.resid = (const char*)resid;
+    p.n_img = n_img; p.H = H; p.W = W; p.out_bf16 = out_bf16;
+    p.row_bytes = ((W + 2 + 3) / 4) * 1024;
+    // runs of rows: enough of them that the persistent grid is balanced (>= 4 per workgroup); a run re-stages two halo rows
+    int parts = 1;
+    while ((int64_t)n_img * parts < 4 * cu_count() && H / (parts * 2) >= 7) parts *= 2;
+    p.rows_per_part = (H + parts - 1) / parts;
+    p.parts = (H + p.rows_per_part - 1) / p.rows_per_part;
+    const int64_t units = (int64_t)n_img * p.parts;
+    const int grid = units < cu_count() ? (int)units : cu_count();
+    const int lds = (L1_R - 1) * p.row_bytes + L1_READ_SPAN + 256;      // + the bias
+    constexpr int lds_max = (L1_R - 1) * ((L1_MAX_W + 2 + 3) / 4) * 1024 + L1_READ_SPAN + 256;
+    const double flops = 2.0 * n_img * H * W * 64.0 * 576.0;
+    ProfScope prof(VTGB_PROF_CONV, flops, s, 2.0 * flops);      // (in fp16-MFMA units: an fp8 k-tile takes the matrix-pipe cycles of an fp16 one)
+    static DeviceOnce a0, a1, a2, a3;
+    if (out_f32) {
+        VTGB_FUNC_LDS_ONCE(a0, (layer1_h8_kernel<0, 0>), lds_max);
+        hipLaunchKernelGGL((layer1_h8_kernel<0, 0>), dim3(grid), dim3(512), lds, s, p);
+    } else if (!resid) {
+        VTGB_FUNC_LDS_ONCE(a1, (layer1_h8_kernel<1, 0>), lds_max);
+        hipLaunchKernelGGL((layer1_h8_kernel<1, 0>), dim3(grid), dim3(512), lds, s, p);
+    } else if (!out_bf16) {
+        VTGB_FUNC_LDS_ONCE(a2, (layer1_h8_kernel<2, 0>), lds_max);
+        hipLaunchKernelGGL((layer1_h8_kernel<2, 0>), dim3(grid), dim3(512), lds, s, p);
+    } else {
+        VTGB_FUNC_LDS_ONCE(a3, (layer1_h8_kernel<2, 1>), lds_max);
+        hipLaunchKernelGGL((layer1_h8_kernel<2, 1>), dim3(grid), dim3(512), lds, s, p);
+    }
+    VTGB_HIP(hipGetLastError());
+    return VTGB_OK;
 }

@@ -309,6 +309,54 @@ static int enc_stem_x3(const StemX3& t, int variant, hipStream_t s) {
     return launch_stats_finish_parts(t.spart, t.stats, t.n, splits, 64, s);
 }
 
+// ---- one stride-1 3x3 convolution of the residual blocks at VTGB_F16C8, over an f16c8 pair [M, 2 Cpad units] -- the ONE place that builds these launches
+// (enc_impl and the unit entry vtgb_raft_layer1_h8).  pair == NULL (fnet): fp32 rows cf [M, ld Cpad] (+ the InstanceNorm moments, complete in `stats`, when
+// `spart` -- the per-tile slots -- is given: images of >= 256 pixels); else (cnet, BatchNorm folded): relu(.), or with `resid` (an f16c8 pair) the block's tail
+// relu(resid + relu(.)), as pair rows, f16c8 or (out_bf16) bf16 pairs.
+//   variant 0: gemm_h8.hip's implicit GEMM (64- / 128-wide tile), the moments from its epilogue's per-tile slots;
+//   variant 1: layer1 (64 -> 64 channels, layer1_h8_supported sizes): conv64.hip's row-resident kernel -- variant 0's bits in every row; no moments;
+//   variant 2: variant 1's fp32 rows + stats_tiles_c64_kernel: the moments per 256-row tile in variant 0's association, bit for bit.
+struct EncH8 {
+    const void* A; const void* W; const float* bias; const int* scale;
+    int n, H, Wd, C, Cpad;
+    float* cf; float* spart; float* stats;
+    void* pair; const void* resid; int out_bf16;
+    void* zero;
+};
+static int g_l1_h8 = 3;      // layer1 on the row-resident kernel: bit 0 cnet, bit 1 fnet (rows + the moments pass)
+extern "C" void vtgb_debug_set_l1_h8(int mask) { g_l1_h8 = mask & 3; }      // 0: gemm_h8.hip's tile for both (same-process A/B)
+static int enc_conv_h8(const EncH8& t, int variant, hipStream_t s) {
+    const int HW = t.H * t.Wd, C2 = 2 * t.Cpad;
+    const int64_t Mo = (int64_t)t.n * HW;
+    if (variant != 0) {
+        VTGB_REQUIRE(t.C == 64 && t.Cpad == 64 && layer1_h8_supported(t.H, t.Wd), VTGB_EUNSUPPORTED, "enc_conv_h8: the row-resident kernel takes 64 -> 64 channels, 16 <= W <= 112, H >= 4");
+        VTGB_REQUIRE(variant == 1 || (!t.pair && t.spart && HW >= 256), VTGB_EINVAL, "enc_conv_h8: tile-order moments belong to fp32 rows of images of >= 256 pixels");
+        VTGB_TRY(launch_layer1_h8(t.A, t.W, t.bias, t.scale, t.pair ? nullptr : t.cf, t.pair, t.resid, t.out_bf16, t.n, t.H, t.Wd, s));
+        if (variant == 1) return VTGB_OK;
+        hipLaunchKernelGGL(stats_tiles_c64_kernel, dim3((unsigned)((Mo + 255) / 256)), dim3(512), 0, s, t.cf, t.spart, (int)Mo, HW);
+        return launch_stats_finish_tiles(t.spart, t.stats, t.n, HW, 64, Mo, s);
+    }
+    GemmDesc d;
+    memset(&d, 0, sizeof(d));
+    d.dtype = VTGB_BF16; d.M = (int)Mo; d.K = 9 * C2;
+    d.A = t.A; d.lda = C2; d.W = t.W; d.ldw = d.K; d.bias = t.bias;
+    d.conv_H = t.H; d.conv_W = t.Wd; d.conv_KH = 3; d.conv_KW = 3; d.conv_Cin = C2; d.conv_split = C2; d.zero_page = t.zero;
+    d.h8_run = 9 * (t.Cpad / 64); d.h8_scale = t.scale;
+    d.algo_flops = 2.0 * Mo * (double)t.C * (9 * t.C);
+    if (!t.pair) {      // g.Cpad -> g.C channels -> cf fp32 [Mo, ld Cpad] (+ per-tile moments)
+        d.N = t.C; d.epi = VTGB_EPI_STORE_F32; d.out = t.cf; d.ldo = t.Cpad;
+        d.col_stats = t.spart; d.stats_rows = HW;
+        VTGB_TRY(launch_conv_h8(d, s));
+        if (t.spart) VTGB_TRY(launch_stats_finish_tiles(t.spart, t.stats, t.n, HW, t.C, Mo, s));
+        return VTGB_OK;
+    }
+    // g.Cpad output rows with ReLU (+ the block's tail relu(x + .), x an f16c8 pair) and the pair store in the epilogue (cnet)
+    d.N = t.Cpad; d.epi = VTGB_EPI_SPLIT; d.act = 1; d.out = t.pair; d.ldo = C2; d.split_lo = t.Cpad;
+    d.resid_bf16 = t.resid; d.ldrb = C2; d.post_relu = t.resid != nullptr;
+    d.h8_out_bf16 = t.out_bf16;
+    return launch_conv_h8(d, s);
+}
+
 static int enc_impl(const vtgb_raft_encoder_args* a, Workspace& ws, hipStream_t s) {
     VTGB_REQUIRE(a, VTGB_EINVAL, "raft_encoder: NULL args");
     VTGB_REQUIRE(a->n_images > 0 && a->H >= 64 && a->W >= 64 && (a->H % 8) == 0 && (a->W % 8) == 0 && (a->norm == 0 || a->norm == 1), VTGB_EINVAL,
@@ -479,31 +527,17 @@ static int enc_impl(const vtgb_raft_encoder_args* a, Workspace& ws, hipStream_t 
             VTGB_REQUIRE(w[40], VTGB_EINVAL, "raft_encoder: weights[40] (the f16c8 convolutions' scale bytes) is NULL at VTGB_F16C8");
             const int C2 = 2 * g.Cpad;      // 16-bit units per pair row
             const bool s2 = g.stride != 1;
-            // 3x3, stride 1, g.Cpad -> g.C channels over an f16c8 pair -> cf fp32 [Mo, ld Cpad] (+ per-tile moments)
+            // layer1 (64 -> 64 channels) on conv64.hip's row-resident kernel where it is dispatched (enc_conv_h8: same bits); other sizes and layers: gemm_h8.hip
+            const bool l1 = g.C == 64 && g.Cpad == 64 && !s2 && layer1_h8_supported(g.Ho, g.Wo);
+            // 3x3, stride 1, g.Cpad -> g.C channels over an f16c8 pair -> cf fp32 [Mo, ld Cpad] (+ the moments, complete in `stats`, when col_stats is given)
             auto conv_h8 = [&](const void* A, const void* Wt, const float* bias, float* col_stats, int si) -> int {
-                GemmDesc d;
-                memset(&d, 0, sizeof(d));
-                d.dtype = VTGB_BF16; d.M = (int)Mo; d.N = g.C; d.K = 9 * C2; d.epi = VTGB_EPI_STORE_F32;
-                d.A = A; d.lda = C2; d.W = Wt; d.ldw = d.K; d.bias = bias; d.out = cf; d.ldo = g.Cpad;
-                d.conv_H = g.Ho; d.conv_W = g.Wo; d.conv_KH = 3; d.conv_KW = 3; d.conv_Cin = C2; d.conv_split = C2; d.zero_page = zero;
-                d.col_stats = col_stats; d.stats_rows = HWo;
-                d.h8_run = 9 * (g.Cpad / 64); d.h8_scale = (const int*)w[40] + si;
-                d.algo_flops = 2.0 * Mo * (double)g.C * (9 * g.C);
-                VTGB_TRY(launch_conv_h8(d, s));
-                if (col_stats) VTGB_TRY(launch_stats_finish_tiles(col_stats, stats, n, HWo, g.C, Mo, s));
-                return VTGB_OK;
+                const EncH8 t{A, Wt, bias, (const int*)w[40] + si, n, g.Ho, g.Wo, g.C, g.Cpad, cf, col_stats, stats, nullptr, nullptr, 0, zero};
+                return enc_conv_h8(t, l1 && (g_l1_h8 & 2) ? (col_stats ? 2 : 1) : 0, s);
             };
             // the same convolution over g.Cpad output rows with ReLU (+ the block's tail relu(x + .), x an f16c8 pair) and the pair store in its epilogue (cnet)
             auto conv_pair = [&](const void* A, const void* Wt, const float* bias, int si, const void* resid, void* out, int out_bf16) -> int {
-                GemmDesc d;
-                memset(&d, 0, sizeof(d));
-                d.dtype = VTGB_BF16; d.M = (int)Mo; d.N = g.Cpad; d.K = 9 * C2; d.epi = VTGB_EPI_SPLIT; d.act = 1;
-                d.A = A; d.lda = C2; d.W = Wt; d.ldw = d.K; d.bias = bias; d.out = out; d.ldo = C2; d.split_lo = g.Cpad;
-                d.conv_H = g.Ho; d.conv_W = g.Wo; d.conv_KH = 3; d.conv_KW = 3; d.conv_Cin = C2; d.conv_split = C2; d.zero_page = zero;
-                d.resid_bf16 = resid; d.ldrb = C2; d.post_relu = resid != nullptr;
-                d.h8_run = 9 * (g.Cpad / 64); d.h8_scale = (const int*)w[40] + si; d.h8_out_bf16 = out_bf16;
-                d.algo_flops = 2.0 * Mo * (double)g.C * (9 * g.C);
-                return launch_conv_h8(d, s);
+                const EncH8 t{A, Wt, bias, (const int*)w[40] + si, n, g.Ho, g.Wo, g.C, g.Cpad, nullptr, nullptr, nullptr, out, resid, out_bf16, zero};
+                return enc_conv_h8(t, l1 && (g_l1_h8 & 1) && (resid || !out_bf16) ? 1 : 0, s);
             };
             const int out_h8 = (b & 1) == 0;      // the block's output pair: f16c8 for the stride-1 block behind it, bf16 for a bf16x3 consumer
             if (!inorm) {
@@ -642,6 +676,53 @@ extern "C" int vtgb_raft_stem(const vtgb_raft_stem_args* a, vtgb_stream_t stream
     VTGB_REQUIRE(a->workspace, VTGB_EWORKSPACE, "raft_stem: workspace is NULL (%zu bytes needed)", align_up(probe.used, 256));
     Workspace ws(a->workspace, a->workspace_bytes);
     return stem_unit_impl(a, ws, (hipStream_t)stream);
+}
+
+// ---- unit-level entry point of one f16c8 layer1 convolution (include/vtgb.h: vtgb_raft_layer1_h8): enc_conv_h8 on the caller's buffers
+static int layer1_unit_impl(const vtgb_raft_layer1_h8_args* a, Workspace& ws, hipStream_t s) {
+    VTGB_REQUIRE(a, VTGB_EINVAL, "raft_layer1_h8: NULL args");
+    VTGB_REQUIRE(a->n_images > 0 && a->H >= 1 && a->W >= 1 && a->variant >= 0 && a->variant <= 2, VTGB_EINVAL, "raft_layer1_h8: bad dims n=%d H=%d W=%d variant=%d",
+                 a->n_images, a->H, a->W, a->variant);
+    const int ok = a->out_kind;
+    VTGB_REQUIRE(ok == VTGB_CONV_OUT_F32 || ok == VTGB_CONV_OUT_PAIR_BF16 || ok == VTGB_CONV_OUT_PAIR_F16C8, VTGB_EINVAL,
+                 "raft_layer1_h8: bad out_kind %d (VTGB_CONV_OUT_F32, _PAIR_BF16 or _PAIR_F16C8)", ok);
+    const bool pair = ok != VTGB_CONV_OUT_F32;
+    const int HW = a->H * a->W;
+    const int64_t M = (int64_t)a->n_images * HW;
+    VTGB_REQUIRE(M < (1ll << 31) / 64, VTGB_EUNSUPPORTED, "raft_layer1_h8: too many pixels per call (chunk the images)");
+    VTGB_REQUIRE(pair || !a->resid, VTGB_EINVAL, "raft_layer1_h8: resid belongs to pair rows");
+    VTGB_REQUIRE(ok != VTGB_CONV_OUT_PAIR_BF16 || a->resid, VTGB_EINVAL, "raft_layer1_h8: bf16 pairs are the output of the residual tail (resid is NULL)");
+    VTGB_REQUIRE(a->variant != 2 || (!pair && HW >= 256 && a->moments), VTGB_EINVAL,
+                 "raft_layer1_h8: variant 2 (tile-order moments) belongs to fp32 rows of images of >= 256 pixels, with moments");
+    VTGB_REQUIRE(a->variant != 1 || !a->moments, VTGB_EINVAL, "raft_layer1_h8: variant 1 writes no moments (moments must be NULL)");
+    VTGB_REQUIRE(!a->moments || (!pair && HW >= 256), VTGB_EINVAL, "raft_layer1_h8: moments belong to fp32 rows of images of >= 256 pixels");
+    VTGB_REQUIRE(a->variant == 0 || layer1_h8_supported(a->H, a->W), VTGB_EUNSUPPORTED,
+                 "raft_layer1_h8: the row-resident kernel does not take %d x %d images (16 <= W <= 112, H >= 4; variant 0 does)", a->H, a->W);
+    float* spart = a->moments ? (float*)ws.take((size_t)(M / 256 + 2) * 128 * 4 * 4) : nullptr;      // (the encoders' sizing)
+    void* zero = ws.take(256);
+    if (ws.dry) return VTGB_OK;
+    VTGB_REQUIRE(ws.ok(), VTGB_EWORKSPACE, "raft_layer1_h8: workspace %zu < %zu bytes", ws.size, ws.used);
+    VTGB_REQUIRE(a->x && a->weights && a->bias && a->scale && a->out, VTGB_EINVAL, "raft_layer1_h8: NULL operand");
+    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    VTGB_REQUIRE(al16(a->x) && al16(a->weights) && al16(a->bias) && al16(a->out) && al16(a->resid) && al16(a->moments) && al16(a->workspace) && ((uintptr_t)a->scale & 3) == 0,
+                 VTGB_EINVAL, "raft_layer1_h8: misaligned operand (16 bytes; the scale: 4)");
+    VTGB_HIP(hipMemsetAsync(zero, 0, 256, s));
+    const EncH8 t{a->x, a->weights, a->bias, (const int*)a->scale, a->n_images, a->H, a->W, 64, 64, pair ? nullptr : (float*)a->out, spart, a->moments,
+                  pair ? a->out : nullptr, a->resid, ok == VTGB_CONV_OUT_PAIR_BF16, zero};
+    return enc_conv_h8(t, a->variant, s);
+}
+extern "C" size_t vtgb_raft_layer1_h8_workspace_bytes(const vtgb_raft_layer1_h8_args* a) {
+    Workspace ws(nullptr, 0);
+    if (layer1_unit_impl(a, ws, nullptr) != VTGB_OK) return 0;
+    return align_up(ws.used, 256);
+}
+extern "C" int vtgb_raft_layer1_h8(const vtgb_raft_layer1_h8_args* a, vtgb_stream_t stream) {
+    VTGB_REQUIRE(a, VTGB_EINVAL, "raft_layer1_h8: NULL args");
+    Workspace probe(nullptr, 0);
+    VTGB_TRY(layer1_unit_impl(a, probe, nullptr));
+    VTGB_REQUIRE(a->workspace, VTGB_EWORKSPACE, "raft_layer1_h8: workspace is NULL (%zu bytes needed)", align_up(probe.used, 256));
+    Workspace ws(a->workspace, a->workspace_bytes);
+    return layer1_unit_impl(a, ws, (hipStream_t)stream);
 }
 
 extern "C" size_t vtgb_raft_encoder_workspace_bytes(const vtgb_raft_encoder_args* a) {

@@ -1663,6 +1663,40 @@ def raft_stem(images: Tensor, w: Tensor, bias: Tensor, variant: int = 1, out_kin
     return out if pair else (out, moments)
 
 
+def raft_layer1_h8(x: Tensor, w: Tensor, bias: Tensor, n: int, H: int, W: int, variant: int = 1, out_kind: int = L.CONV_OUT_F32, resid: Optional[Tensor] = None,
+                   moments: bool = False, out: Optional[Tensor] = None, workspace: Optional[Tensor] = None):
+    """One layer1 convolution of the encoders at f16c8 alone (include/vtgb.h vtgb_raft_layer1_h8): x = f16c8 pair rows [n * H * W, 128] int16 (pair_pack),
+    w [64, 3, 3, 64] fp32 (co, kh, kw, ci; packed here by h8_conv_pack with h8_weight_scale's scale, as the encoder table packs it), bias [64].
+    variant 0: the implicit GEMM, 1: the row-resident kernel, 2 (fp32 rows + moments): the row-resident kernel + the moments in variant 0's order.
+    out_kind CONV_OUT_F32 -> fp32 rows [M, 64] (with ``moments``: (rows, moments [n, 64, 2])); CONV_OUT_PAIR_F16C8 -> relu(.) or, with ``resid`` (f16c8 pair
+    rows), relu(resid + relu(.)) as int16 pair rows [M, 128]; CONV_OUT_PAIR_BF16: that tail as a bf16 pair.  ``out``: write the rows into the head of this
+    contiguous tensor; ``workspace``: a uint8 tensor to use as the scratch."""
+    _need_cuda(x, w)
+    dev = x.device
+    M = n * H * W
+    assert x.is_contiguous() and x.dtype == torch.int16 and tuple(x.shape) == (M, 128) and tuple(w.shape) == (64, 3, 3, 64)
+    sw, byte = h8_weight_scale(w)
+    packed = h8_conv_pack(w.to(dev), sw)
+    scale = torch.tensor([byte], dtype=torch.int32, device=dev)
+    bias_t = bias.to(dev).contiguous().float()
+    pair = out_kind != L.CONV_OUT_F32
+    if out is None:
+        out = torch.empty(M, 128, dtype=torch.int16, device=dev) if pair else torch.empty(M, 64, dtype=torch.float32, device=dev)
+    assert out.is_contiguous() and out.numel() >= M * (128 if pair else 64) and out.dtype == (torch.int16 if pair else torch.float32)
+    mom = torch.empty(n, 64, 2, dtype=torch.float32, device=dev) if moments else None
+    a = L.RaftLayer1H8Args(n, H, W, variant, out_kind, x.data_ptr(), packed.data_ptr(), bias_t.data_ptr(), scale.data_ptr(), _ptr(resid), out.data_ptr(), _ptr(mom),
+                           None, 0)
+    need = L.lib().vtgb_raft_layer1_h8_workspace_bytes(C.byref(a))
+    if need == 0:
+        L.check(L.lib().vtgb_raft_layer1_h8(C.byref(a), _stream()))   # raises with the library's message
+    ws = workspace if workspace is not None else _ws.get(need, dev)
+    assert ws.numel() >= need
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    L.check(L.lib().vtgb_raft_layer1_h8(C.byref(a), _stream()))
+    torch.cuda.current_stream().synchronize()      # (packed / scale / bias_t are temporaries of this call)
+    return (out, mom) if moments else out
+
+
 class RaftEncoderWeights(_WeightTable):
     """of_extractor.{fnet,cnet}.* -> the packed table of vtgb_raft_encoder.  batch_norm=True folds the eval-mode
     BatchNorm2d that follows each convolution (extractor.py:20-24,124) into the convolution's weight and bias."""
