@@ -104,6 +104,19 @@ def check_eos_sets(eos_sets) -> str:
     return eos_sets
 
 
+SAMPLED_DECODE = ("hf", "graph")
+
+
+def check_sampled_decode(sampled_decode) -> str:
+    """Who runs a LightningModule twin's sampled ``generate_configs``: "hf" (HF generate, the default) or "graph" (opt-in: the module envelope
+    serves ``do_sample`` with temperature / top_p and takes the length as HF's ``max_length`` / ``min_length`` -- the literal dictionaries of
+    the reference's LSTP_blip2.yaml / LSTP_instructblip.yaml family -- so that on a Llama they stay on the graph decoder's sampling path;
+    a T5's sampled requests stay on HF generate); ValueError otherwise."""
+    if not isinstance(sampled_decode, str) or sampled_decode not in SAMPLED_DECODE:
+        raise ValueError(f"sampled_decode must be one of {SAMPLED_DECODE}, got {sampled_decode!r}")
+    return sampled_decode
+
+
 def _first_eos(eos):
     """The id HF's defaults take from a request's eos: the id itself, or the first of a set."""
     return eos[0] if isinstance(eos, tuple) else eos
@@ -1791,6 +1804,8 @@ class Envelope(NamedTuple):
     keys: frozenset
     neutral: dict
     sampling: bool
+    # the request must give its length: as ``max_new_tokens``, or -- in an envelope whose ``keys`` hold "max_length" (the beam and sampled
+    # twins of the module envelope) -- as HF's ``max_length``, which ``graph_generate`` resolves with ``generated_length``
     need_max_new: bool
     # opt-in (eos_sets="graph"): several distinct eos ids (up to ops.EOS_MAX, each in [0, vocab_size)) stay on the decoders.  Always given by
     # name (``_replace(eos_sets=True)``); it stands before the beam switches because tests/test_t5_beam_decode.py pins those as the last two fields
@@ -1821,7 +1836,8 @@ MODULE_ENVELOPE_T5_BEAMS = MODULE_ENVELOPE_BEAMS._replace(t5_beams=True)
 def envelope_for(owner, module: bool) -> Envelope:
     """The envelope a caller plans with: today's, or its beam twin when the owner opted in (attribute ``beam_search``, "hf" when it has none;
     "graph+t5": the twin with ``t5_beams``; "+kv8" changes the decoder, not the envelope); an owner whose ``eos_sets`` is "graph" gets that
-    envelope's ``_replace(eos_sets=True)`` twin."""
+    envelope's ``_replace(eos_sets=True)`` twin, one whose ``sampled_decode`` is "graph" the module envelope's twin with ``sampling`` and the
+    keys ``max_length`` / ``min_length``."""
     mode = check_beam_search(getattr(owner, "beam_search", "hf")).replace("+kv8", "")
     if mode == "graph+t5":
         env = MODULE_ENVELOPE_T5_BEAMS if module else GENERATE_ENVELOPE_T5_BEAMS
@@ -1831,6 +1847,9 @@ def envelope_for(owner, module: bool) -> Envelope:
         env = GENERATE_ENVELOPE_BEAMS if mode == "graph" else GENERATE_ENVELOPE
     if check_eos_sets(getattr(owner, "eos_sets", "hf")) == "graph":      # (else: the very objects above)
         env = env._replace(eos_sets=True)
+    if module and check_sampled_decode(getattr(owner, "sampled_decode", "hf")) == "graph":
+        # the modules' configurations may sample and give the length as ``max_length`` / ``min_length`` (LSTP.generate's envelope samples already)
+        env = env._replace(sampling=True, keys=env.keys | {"max_length", "min_length"})
     return env
 
 
@@ -1860,7 +1879,7 @@ def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: E
     mt = getattr(lm.config, "model_type", "")
     if not inputs_embeds.is_cuda or not ("llama" in mt or mt == "t5"):
         return None
-    if set(request) - env.keys or (env.need_max_new and "max_new_tokens" not in request and not (env.beams and request.get("max_length") is not None)):
+    if set(request) - env.keys or (env.need_max_new and "max_new_tokens" not in request and not ("max_length" in env.keys and request.get("max_length") is not None)):
         return None
     if lora_state(lm) not in (None, "ok"):      # adapters the decoders do not apply: HF generate runs the modules' own forward
         return None
@@ -1919,7 +1938,7 @@ def graph_generate(owner, lm, inputs_embeds: Tensor, attention_mask: Tensor, gen
     plan = plan_decode(lm, inputs_embeds, attention_mask, gc, env)
     if plan is None:
         return None
-    if not env.beams:
+    if "max_length" not in env.keys:      # (the length is ``max_new_tokens``: ``need_max_new``)
         return decoder_for(owner, lm).generate(inputs_embeds, int(gc["max_new_tokens"]), **plan)
     n, min_new = generated_length(lm, gc, inputs_embeds.shape[1])
     if n <= 0:      # HF generate reports it in its own words

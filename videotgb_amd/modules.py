@@ -176,14 +176,17 @@ class _LSTPLightningBase(_Base):
     def __init__(self, model_name_or_path: str, sampler_name_or_path: str, of_extractor_name_or_path: str, temperature: float = 1.0,
                  optimizer=None, scheduler: Optional[str] = None, scheduler_params: Optional[dict] = None,
                  generate_configs: Optional[dict] = None, compute_dtype="bf16", processor=None, tgb_cfg: Optional[synth.TgbCfg] = None,
-                 decode_weights: str = "bf16", kv_cache: str = "bf16", beam_search: str = "hf", eos_sets: str = "hf"):
+                 decode_weights: str = "bf16", kv_cache: str = "bf16", beam_search: str = "hf", eos_sets: str = "hf", sampled_decode: str = "hf"):
         super().__init__()
         self.save_hyperparameters(logger=False)
-        from .decode import check_beam_search, check_decode_weights, check_eos_sets, check_kv_cache
+        from .decode import check_beam_search, check_decode_weights, check_eos_sets, check_kv_cache, check_sampled_decode
         self.decode_weights = check_decode_weights(decode_weights)      # "fp8": models.LSTP's opt-in decode mode (decode.decoder_for reads it)
         self.kv_cache = check_kv_cache(kv_cache)                        # "fp8": models.LSTP's opt-in K/V cache mode (likewise)
         self.beam_search = check_beam_search(beam_search)               # "graph" / "graph+t5" (/ "+kv8"): models.LSTP's opt-in beam search (decode.graph_generate reads it)
         self.eos_sets = check_eos_sets(eos_sets)                        # "graph": models.LSTP's opt-in eos-id sets (decode.graph_generate reads it)
+        # "graph": the shipped sampled generate_configs -- do_sample, top_p, temperature, max_length / min_length -- stay on the Llama graph
+        # decoder (decode.envelope_for reads it; a T5's sampled requests stay on HF generate)
+        self.sampled_decode = check_sampled_decode(sampled_decode)
         if not hasattr(self.hparams, "optimizer"):      # the stand-in base: keep what configure_optimizers reads
             self.hparams.optimizer, self.hparams.scheduler, self.hparams.scheduler_params = optimizer, scheduler, scheduler_params or {}
         self.temperature = temperature
@@ -333,7 +336,8 @@ class _LSTPLightningBase(_Base):
             inputs_embeddings = torch.cat([lm_inputs, emb], dim=1)
         outputs = None
         if getattr(self, "fast_decode", True):       # (round 6: on by default) hipGraph-replayed decode of the same HF weights whenever generate_configs is a
-            # configuration decode.graph_generate reproduces exactly (greedy, one beam, padded questions included, Llama / T5); None -> HF generate below
+            # configuration decode.graph_generate serves: one it reproduces exactly (greedy, one beam, padded questions included, Llama / T5) or --
+            # under sampled_decode="graph", Llama -- a sampled one (HF's warped distribution, the decoder's own random stream); None -> HF generate below
             from .decode import graph_generate
             outputs = graph_generate(self, lm, inputs_embeddings, attention_mask, self.generate_configs)
         if outputs is None:
