@@ -1051,6 +1051,28 @@ typedef struct {
 } vtgb_llm_beam_candidates_eos_args;
 int vtgb_llm_beam_candidates_eos(const vtgb_llm_beam_candidates_eos_args* a, vtgb_stream_t stream);
 
+/* ---- Repetition penalty on ONE beam (opt-in: penalty_decode = "graph"; emit.hip; added at version 601 without a bump).
+ * vtgb_llm_repetition_penalty: HF's RepetitionPenaltyLogitsProcessor on the logits of one decode step.  logits [R, V] (`dtype`, row stride V;
+ *   16-byte loads only from 16-byte-aligned addresses, so rows of an odd V are fine), seq [R, N] int64, *step device int64, out [R, V] fp32.
+ *   With x = (float)logits[r, i]:  out[r, i] = (x < 0 ? x * penalty : x / penalty)  when i is SEEN in row r, else x -- one correctly rounded fp32
+ *   multiply or divide, applied once however often an id repeats.  Index i is seen when it is among seq[r, 0 .. clamp(*step, 0, N)) or equals
+ *   start_id (an id that is always seen: T5's decoder start token; -1 for none).  An id outside [0, V) matches no index; entries of seq at or
+ *   behind *step are never read.  The result is elementwise: it depends on the row alone, not on R, the grid or the row's place.  logits and
+ *   out must not overlap.  VTGB_EINVAL: NULL args / operand, a dtype other than VTGB_BF16 / VTGB_F32, non-positive R / V / N, a penalty that
+ *   is not finite and positive; VTGB_EUNSUPPORTED: more than 65535 rows, a misaligned operand (logits, out 16 bytes; seq, step 8) -- on the
+ *   host, before any launch. */
+typedef struct {
+    int32_t dtype;                       /* of logits */
+    int32_t R, V, N;
+    int32_t start_id;                    /* always seen; -1: none */
+    float penalty;                       /* > 0, finite (1: out = (float)logits) */
+    const void* logits;                  /* [R, V] */
+    const int64_t* seq;                  /* [R, N] ids */
+    const int64_t* step;                 /* device */
+    float* out;                          /* [R, V] */
+} vtgb_llm_repetition_penalty_args;
+int vtgb_llm_repetition_penalty(const vtgb_llm_repetition_penalty_args* a, vtgb_stream_t stream);
+
 /* ---- Beam search on the T5 decode step (opt-in: beam_search = "graph+t5"; llm.hip; added at version 601 without a bump).
  * vtgb_llm_attention_rows_beam: vtgb_llm_attention_rows in its decode form -- `pos` given, keys [0, *pos], bias row *pos -- over the caches
  *   k / v of `cache_rows` rows (row stride kv_batch), where K and V of key t of query row r come from cache row

@@ -49,6 +49,7 @@ EXPORTS = [
     "vtgb_llm_decode_attention_beam", "vtgb_llm_beam_candidates", "vtgb_llm_attention_rows_beam", "vtgb_llm_decode_attention_beam_fp8",
     "vtgb_pack_skinny_weight_mxfp4_bytes", "vtgb_pack_skinny_weight_mxfp4", "vtgb_gemm_skinny_mxfp4",
     "vtgb_raft_stem_workspace_bytes", "vtgb_raft_stem", "vtgb_llm_lora_parts", "vtgb_llm_pick_greedy", "vtgb_llm_beam_candidates_eos",
+    "vtgb_llm_repetition_penalty",
     "vtgb_raft_layer1_h8_workspace_bytes", "vtgb_raft_layer1_h8",
 ]
 COMM_ID_BYTES = 128
@@ -259,6 +260,12 @@ class LlmBeamCandidatesEosArgs(C.Structure):
                 ("workspace_bytes", sz)]
 
 
+class LlmRepetitionPenaltyArgs(C.Structure):
+    """vtgb_llm_repetition_penalty_args: one step's logits -> HF's repetition-penalised fp32 scores over the row's ids (one beam)."""
+    _fields_ = [("dtype", i32), ("R", i32), ("V", i32), ("N", i32), ("start_id", i32), ("penalty", f32), ("logits", vp), ("seq", vp), ("step", vp),
+                ("out", vp)]
+
+
 class GemmArgs(C.Structure):
     _fields_ = [("dtype", i32), ("M", i32), ("N", i32), ("K", i32), ("epilogue", i32), ("A", vp), ("lda", i64),
                 ("W", vp), ("ldw", i64), ("bias", vp), ("resid", vp), ("out", vp), ("ldo", i64)]
@@ -401,6 +408,8 @@ def lib() -> C.CDLL:
     L.vtgb_llm_pick_greedy.restype = C.c_int
     L.vtgb_llm_beam_candidates_eos.argtypes = [C.POINTER(LlmBeamCandidatesEosArgs), vp]
     L.vtgb_llm_beam_candidates_eos.restype = C.c_int
+    L.vtgb_llm_repetition_penalty.argtypes = [C.POINTER(LlmRepetitionPenaltyArgs), vp]
+    L.vtgb_llm_repetition_penalty.restype = C.c_int
     L.vtgb_llm_attention_rows_beam.argtypes = [C.POINTER(LlmAttnRowsArgs), vp, i64, i32, vp]
     L.vtgb_llm_attention_rows_beam.restype = C.c_int
     L.vtgb_llm_lora.argtypes = [C.POINTER(LlmLoraArgs), vp]

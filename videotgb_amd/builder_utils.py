@@ -16,14 +16,16 @@ from . import models, video
 
 
 def load_pretrained_model(ckpt_path, base_model_path, base_sampler_path, device, lora=False, compute_dtype="bf16", load_processors=True,
-                          decode_weights="bf16", kv_cache="bf16", beam_search="hf", eos_sets="hf", **model_kwargs):
+                          decode_weights="bf16", kv_cache="bf16", beam_search="hf", eos_sets="hf", penalty_decode="hf",
+                          **model_kwargs):
     """eval/utils/builder_utils.py:169-187.  ``compute_dtype`` / ``load_processors`` / ``decode_weights`` / ``kv_cache`` / ``model_kwargs`` are keyword extensions
     (the processors need tokenizer files next to the config; tests that only have a config.json pass ``load_processors=False``;
     ``decode_weights="fp8"``: the opt-in fp8 weight stream of the Llama graph decoder, ``"mxfp4"``: its opt-in MXFP4 weight stream (the ids are the
     quantised model's, not the reference's; answer quality on a trained checkpoint is not measured by this project), ``kv_cache="fp8"``: its opt-in fp8 K/V cache, ``beam_search="graph"``: its opt-in
     beam search, ``"graph+t5"``: that and the T5 graph decoder's, ``eos_sets="graph"``: requests with several distinct eos ids stay on the graph
-    decoders, models.LSTP)."""
-    from .decode import check_beam_search, check_decode_weights, check_eos_sets, check_kv_cache
+    decoders, ``penalty_decode="graph"``: one-beam requests with a repetition penalty stay on the graph decoders, models.LSTP)."""
+    from .decode import check_beam_search, check_decode_weights, check_eos_sets, check_kv_cache, check_penalty_decode
+    check_penalty_decode(penalty_decode)
     check_eos_sets(eos_sets)
     check_decode_weights(decode_weights)
     check_kv_cache(kv_cache)
@@ -36,10 +38,10 @@ def load_pretrained_model(ckpt_path, base_model_path, base_sampler_path, device,
         sampler_processor = AutoTokenizer.from_pretrained(base_sampler_path)
     if "instructblip" in base_model_path:
         model = models.LSTP(base_model_path, device, lora, compute_dtype=compute_dtype, decode_weights=decode_weights, kv_cache=kv_cache, beam_search=beam_search,
-                            eos_sets=eos_sets, **model_kwargs)
+                            eos_sets=eos_sets, penalty_decode=penalty_decode, **model_kwargs)
     elif "blip2" in base_model_path:
         model = models.LSTP_blip2(base_model_path, device, lora, compute_dtype=compute_dtype, decode_weights=decode_weights, kv_cache=kv_cache,
-                                  beam_search=beam_search, eos_sets=eos_sets, **model_kwargs)
+                                  beam_search=beam_search, eos_sets=eos_sets, penalty_decode=penalty_decode, **model_kwargs)
     else:   # the reference leaves `model` unbound here and dies with UnboundLocalError
         raise ValueError(f"base_model_path {base_model_path!r} names neither an instructblip nor a blip2 model")
     state_dict = torch.load(ckpt_path, map_location="cpu")

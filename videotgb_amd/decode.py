@@ -24,6 +24,8 @@ Opt-in (an owner's ``beam_search="graph"``): HF's deterministic beam search on t
 repetition_penalty=..., length_penalty=...)``; by default such requests go to HF generate as before (tests/test_beam_decode.py,
 test_gpu_beam_decode.py).  ``beam_search="graph+kv8"`` / ``"graph+t5+kv8"``: the same, and the beams of a ``kv_cache="fp8"`` Llama run over
 the fp8 cache (``GreedyDecoder(fp8_beams=True)``; tests/test_beam_kv8.py, test_gpu_beam_kv8.py).
+Opt-in (an owner's ``penalty_decode="graph"``): ``repetition_penalty`` != 1 on ONE beam, on both decoders (``_penalise``,
+vtgb_llm_repetition_penalty; tests/test_penalty_decode.py, test_gpu_penalty_decode.py); by default such requests go to HF generate as before.
 
 Structure: ``_GraphDecoder`` owns everything that is not the model -- the state cache (LRU, MAX_STATES), the emission state (token / position
 feedback, finished flags, lengths, sampling and stopping data), token selection, capture, the replay loop and the truncation of the returned ids;
@@ -115,6 +117,18 @@ def check_sampled_decode(sampled_decode) -> str:
     if not isinstance(sampled_decode, str) or sampled_decode not in SAMPLED_DECODE:
         raise ValueError(f"sampled_decode must be one of {SAMPLED_DECODE}, got {sampled_decode!r}")
     return sampled_decode
+
+
+PENALTY_DECODE = ("hf", "graph")
+
+
+def check_penalty_decode(penalty_decode) -> str:
+    """Who runs a ONE-beam request with ``repetition_penalty != 1``: "hf" (HF generate, the default) or "graph" (opt-in: the graph decoders --
+    ``GreedyDecoder(penalty=True)`` / ``T5GreedyDecoder(penalty=True)`` -- apply HF's RepetitionPenaltyLogitsProcessor inside the captured step:
+    greedy on both, sampling on a Llama); ValueError otherwise.  Beams keep their own penalty (``beam_search``)."""
+    if not isinstance(penalty_decode, str) or penalty_decode not in PENALTY_DECODE:
+        raise ValueError(f"penalty_decode must be one of {PENALTY_DECODE}, got {penalty_decode!r}")
+    return penalty_decode
 
 
 def _first_eos(eos):
@@ -284,10 +298,15 @@ class _GraphDecoder:
     MAX_STATES = 4
     FEEDBACK = ("tok", "pos", "step", "out", "fin", "len")      # what one step writes besides the model's caches
 
-    def __init__(self, lm, fused: bool, weights: str = "bf16", kv_cache: str = "bf16", eos_sets: bool = False):
+    # a one-beam repetition penalty on the fused device path: True = ops.repetition_penalty (vtgb_llm_repetition_penalty) into the state's fp32
+    # buffer; False = the torch statement of ``_penalise`` (what every other path runs) -- the switch of the A/B (tools/penalty_decode_bench.py)
+    PENALTY_KERNEL = True
+
+    def __init__(self, lm, fused: bool, weights: str = "bf16", kv_cache: str = "bf16", eos_sets: bool = False, penalty: bool = False):
         self.lm, self.cfg, self.fused, self.weights = lm, lm.config, fused, check_decode_weights(weights)
         self.kv_cache = check_kv_cache(kv_cache)
         self.eos_sets = bool(eos_sets)      # opt-in (eos_sets="graph"): requests with 2 .. ops.EOS_MAX distinct eos ids instead of a refusal
+        self.penalty = bool(penalty)        # opt-in (penalty_decode="graph"): one beam with repetition_penalty != 1 instead of a refusal
         self.key = weights_key(lm)
         self.graphs: Dict[tuple, dict] = {}
 
@@ -306,9 +325,20 @@ class _GraphDecoder:
             eos_token_id = ids[0]
         return eos_token_id, int(pad_token_id if pad_token_id is not None else (eos_token_id or 0)), int(min_new_tokens or 0)
 
-    def _cached_state(self, key: tuple, B: int, N: int, n_ar: int, device, eos, pad: int, min_new: int, sample, stop, buffers: Callable[[], dict]) -> dict:
+    def _one_beam_penalty(self, repetition_penalty) -> float:
+        """The penalty a one-beam state holds: 1.0 (none), or -- a decoder built with ``penalty`` -- the request's; today's refusal otherwise."""
+        p = float(repetition_penalty)
+        if p != 1.0 and not self.penalty:
+            raise NotImplementedError("repetition_penalty with one beam: use HF generate")
+        return p
+
+    def _cached_state(self, key: tuple, B: int, N: int, n_ar: int, device, eos, pad: int, min_new: int, sample, stop, buffers: Callable[[], dict],
+                      penalty: float = 1.0) -> dict:
         """The state under ``key``, most recently used last; a new one takes the least recently used state's place once MAX_STATES are kept
-        (its graph and buffers are freed first) and is the emission state below plus the model's ``buffers()``."""
+        (its graph and buffers are freed first) and is the emission state below plus the model's ``buffers()``.  ``penalty`` != 1 (one beam):
+        the key gets it -- the captured step bakes the scalar in -- and the state its operands (``_penalise``)."""
+        if penalty != 1.0:
+            key = key + (("penalty", penalty),)
         st = self.graphs.pop(key, None)
         if st is None:
             while len(self.graphs) >= self.MAX_STATES:
@@ -322,6 +352,10 @@ class _GraphDecoder:
                       u=torch.zeros(N, B, device=device), len=torch.full((B,), N, dtype=torch.long, device=device))
             if isinstance(eos, tuple):      # an eos set: its device list (isin on the torch path, the kernels' operand on the fused one)
                 st["eos_t"] = torch.tensor(eos, dtype=torch.int32, device=device)
+            if penalty != 1.0:      # the scalar, its fp32 tensor (a tensor divisor is a true division on every backend) and, where the kernel runs, its output
+                st.update(pen=penalty, pen_t=torch.tensor([penalty], dtype=torch.float32, device=device))
+                if self.fused and torch.device(device).type == "cuda":
+                    st["pen_out"] = torch.zeros(B, self.lm.lm_head.weight.shape[0], dtype=torch.float32, device=device)
             st.update(buffers())
         self.graphs[key] = st
         return st
@@ -378,7 +412,28 @@ class _GraphDecoder:
             N = st["out"].shape[1]
             st["len"].copy_(torch.where(st["fin"] & (st["len"] == N), (step + 1).expand_as(st["len"]), st["len"]))
 
+    def _penalty_start(self) -> Optional[int]:
+        """An id HF's processors always see besides the generated ones (T5: the decoder start token); None: none."""
+        return None
+
+    def _penalise(self, st, logits: Tensor) -> Tensor:
+        """HF's RepetitionPenaltyLogitsProcessor on fp32 scores over the ids a row has generated so far (``out[:, :step]``, + ``_penalty_start``):
+        x < 0 ? x * p : x / p at every seen index, once.  On the fused device path ops.repetition_penalty into the state's buffer; elsewhere
+        (and under ``PENALTY_KERNEL = False``) the fixed-shape statement: ids behind the step go to a spare column, gather / scatter."""
+        start, N, V = self._penalty_start(), st["out"].shape[1], logits.shape[-1]
+        if "pen_out" in st and self.PENALTY_KERNEL and logits.is_cuda and logits.dtype in (torch.bfloat16, torch.float32):
+            return ops.repetition_penalty(logits, st["out"], st["step"], st["pen"], start, out=st["pen_out"])
+        x = logits.float()
+        ids = torch.where(st["ar"][None, :N] < st["step"], st["out"], torch.full_like(st["out"], V))
+        if start is not None:
+            ids = torch.cat((torch.full_like(ids[:, :1], start), ids), dim=1)
+        x = torch.cat((x, torch.zeros_like(x[:, :1])), dim=-1)
+        g = x.gather(1, ids)
+        return x.scatter(1, ids, torch.where(g < 0, g * st["pen_t"], g / st["pen_t"]))[:, :V].contiguous()
+
     def _emit(self, st, logits: Tensor):
+        if "pen" in st:      # (one beam, repetition_penalty != 1) before the eos block of min_new_tokens and the warpers, as in HF
+            logits = self._penalise(st, logits)
         if "eos_t" in st and st["sample"] is None and self.fused and logits.is_cuda:
             # an eos set, greedy, on the device: ``_pick`` and the two writes below in one launch (vtgb_llm_pick_greedy)
             ops.pick_greedy(logits, st["step"], st["eos_t"], st["fin"], st["tok"], st["out"], st["min_new"], st["pad"])
@@ -620,13 +675,14 @@ class GreedyDecoder(_GraphDecoder):
     epilogue -- ops.gemm_skinny(bias=), vtgb_gemm_skinny_bias --, prefill and large batches through vtgb_gemm's bias, ``_layer`` through
     F.linear).  Anything else raises NotImplementedError with the reason."""
 
-    def __init__(self, lm, fused: bool = True, weights: str = "bf16", kv_cache: str = "bf16", fp8_beams: bool = False, eos_sets: bool = False):
+    def __init__(self, lm, fused: bool = True, weights: str = "bf16", kv_cache: str = "bf16", fp8_beams: bool = False, eos_sets: bool = False,
+                 penalty: bool = False):
         cfg = lm.config
         if "llama" not in cfg.model_type:
             raise NotImplementedError("GreedyDecoder handles Llama-architecture models; use HF generate otherwise")
         _llama_servable(lm)
         has_lora = _lora_servable(lm)
-        super().__init__(lm, fused, weights, kv_cache, eos_sets)
+        super().__init__(lm, fused, weights, kv_cache, eos_sets, penalty)
         self.fp8_beams = bool(fp8_beams)      # opt-in (beam_search="...+kv8"): num_beams > 1 over the fp8 K/V cache; inert with a bf16 cache
         wdt = lm.lm_head.weight.dtype
         if self.kv_cache == "fp8" and wdt != torch.bfloat16 and (fused or wdt != torch.float32):
@@ -932,7 +988,7 @@ class GreedyDecoder(_GraphDecoder):
     def _attn_route(self, tmax: int) -> Optional[str]:
         return ops.decode_attention_route(tmax, self.hd, self.DECODE_SPLIT_MIN_KEYS)
 
-    def _state(self, B: int, P: int, N: int, device, dtype, eos=None, pad=0, min_new=0, sample=None, stop=None, padded=False):
+    def _state(self, B: int, P: int, N: int, device, dtype, eos=None, pad=0, min_new=0, sample=None, stop=None, padded=False, penalty: float = 1.0):
         # The cache length is bucketed (multiples of 64) and the true prompt length is device data (`pos`): an eval loop over real
         # questions with varying P reuses a handful of graphs instead of capturing one -- and allocating 2 x n_layers KV caches --
         # per distinct P.  At most MAX_STATES states are kept (least recently used goes: graph and caches are freed).  A padded batch has
@@ -971,7 +1027,7 @@ class GreedyDecoder(_GraphDecoder):
                 self._skinny_weights()
             return st
         key = (B, tmax, N, eos, pad, min_new, sample, stop, padded) + ((self.kv_cache,) if self.kv_cache != "bf16" else ())
-        return self._cached_state(key, B, N, tmax, device, eos, pad, min_new, sample, stop, buffers)
+        return self._cached_state(key, B, N, tmax, device, eos, pad, min_new, sample, stop, buffers, penalty)
 
     def _decode_step_fused(self, st):
         """One token for every sequence with the per-layer small ops fused in libvtgb.so
@@ -1270,7 +1326,10 @@ class GreedyDecoder(_GraphDecoder):
         (NotImplementedError otherwise).
         ``eos_token_id``: None, an id, or a list; a list of several distinct ids is served by a decoder built with ``eos_sets=True`` (up to
         ops.EOS_MAX ids, each in [0, V): any of them ends a row, all are blocked by ``min_new_tokens``, HF's pad default is the first) and
-        refused otherwise."""
+        refused otherwise.
+        ``repetition_penalty`` != 1 with one beam: served by a decoder built with ``penalty=True`` -- HF's RepetitionPenaltyLogitsProcessor on
+        the fp32 scores of every step over the ids the row has generated (the first token, from the prefill, has none), before the eos block
+        of ``min_new_tokens`` and the sampling warpers; greedy or sampled, with every other option -- and refused otherwise."""
         num_beams = int(num_beams)
         if num_beams < 1 or not float(repetition_penalty) > 0.0:
             raise ValueError(f"num_beams={num_beams} / repetition_penalty={repetition_penalty}: at least one beam, a positive penalty")
@@ -1281,8 +1340,7 @@ class GreedyDecoder(_GraphDecoder):
                 raise NotImplementedError("num_beams > 1 with kv_cache='fp8': use HF generate")
             return self._generate_beams(inputs_embeds, max_new_tokens, use_graph, eos_token_id, pad_token_id, min_new_tokens, attention_mask, num_beams,
                                         1.0 if length_penalty is None else float(length_penalty), float(repetition_penalty))
-        if float(repetition_penalty) != 1.0:
-            raise NotImplementedError("repetition_penalty with one beam: use HF generate")
+        penalty = self._one_beam_penalty(repetition_penalty)
         B, P, _ = inputs_embeds.shape
         pmask = _padding(attention_mask, B, P)
         N = max_new_tokens
@@ -1296,7 +1354,7 @@ class GreedyDecoder(_GraphDecoder):
         stop = tuple(tuple(int(v) for v in t) for t in stop_ids if len(t)) if stop_ids else None
         if text_stop is not None and B != 1:
             raise AssertionError("Only support batch size 1 (yet)")                                          # (the reference's criteria: builder_utils.py:334)
-        st = self._state(B, P, N, dev, dt, eos_token_id, pad_token_id, min_new_tokens, sample, stop or None, pmask is not None)
+        st = self._state(B, P, N, dev, dt, eos_token_id, pad_token_id, min_new_tokens, sample, stop or None, pmask is not None, penalty)
         if sample is not None:
             if sample_noise is not None:
                 st["u"].copy_(sample_noise.to(dev).reshape(N, B))
@@ -1328,7 +1386,7 @@ class T5GreedyDecoder(_GraphDecoder):
     the encoder's and decoder's SelfAttention and the decoder's EncDecAttention; ``lora_state``) are applied unmerged on every path."""
     _ACT_KIND = {"silu": 0, "swish": 0, "gelu_new": 1, "relu": 2, "gelu": 3}
 
-    def __init__(self, lm, fused: bool = True, weights: str = "bf16", kv_cache: str = "bf16", eos_sets: bool = False):
+    def __init__(self, lm, fused: bool = True, weights: str = "bf16", kv_cache: str = "bf16", eos_sets: bool = False, penalty: bool = False):
         cfg = lm.config
         if getattr(cfg, "model_type", "") != "t5":
             raise NotImplementedError("T5GreedyDecoder handles T5ForConditionalGeneration")
@@ -1337,7 +1395,7 @@ class T5GreedyDecoder(_GraphDecoder):
         if check_kv_cache(kv_cache) != "bf16":
             raise NotImplementedError("kv_cache='fp8' is implemented for the Llama decoder only")
         has_lora = _lora_servable(lm)      # (adapters outside q / k / v of the attention blocks: NotImplementedError)
-        super().__init__(lm, fused, weights, kv_cache, eos_sets)
+        super().__init__(lm, fused, weights, kv_cache, eos_sets, penalty)
         self.H, self.dk, self.D = cfg.num_heads, cfg.d_kv, cfg.d_model
         self.eps = cfg.layer_norm_epsilon
         self.start = cfg.decoder_start_token_id if cfg.decoder_start_token_id is not None else cfg.pad_token_id
@@ -1396,6 +1454,10 @@ class T5GreedyDecoder(_GraphDecoder):
 
     def _lora_of(self, which: str, li: int):
         return self.lora[which][li] if self.lora is not None else ()
+
+    def _penalty_start(self) -> Optional[int]:
+        # HF's decoder input is the start token: RepetitionPenaltyLogitsProcessor sees it from the first step on
+        return int(self.start)
 
     def _hip(self, x: Tensor) -> bool:
         return (self.fused and x.is_cuda and x.dtype in (torch.bfloat16, torch.float32) and self.act_kind is not None
@@ -1525,7 +1587,7 @@ class T5GreedyDecoder(_GraphDecoder):
             y = y.to(w.dtype)
         return w * y
 
-    def _state(self, B, P, N, device, dtype, eos, pad, min_new, padded=False, beam: Optional[dict] = None):
+    def _state(self, B, P, N, device, dtype, eos, pad, min_new, padded=False, beam: Optional[dict] = None, penalty: float = 1.0):
         # On libvtgb.so the encoder length is DEVICE data (`plen`, read by the cross-attention kernel) and the cross-attention K | V live in
         # persistent buffers of a bucketed length (multiples of 64): an eval loop over real questions of varying length reuses a handful of
         # captured graphs (round-3 VERDICT: the state keyed on the exact P).  The torch path (CPU, fused=False) keeps exact-P caches.
@@ -1583,7 +1645,7 @@ class T5GreedyDecoder(_GraphDecoder):
         key = (B, Pb, N, eos, pad, min_new, hip, padded)
         if beam is not None:      # (keyed by K and the penalties as well: they are constants of the captured step)
             key = ("beams", items, beam["K"], beam["repetition_penalty"], beam["length_penalty"]) + key[1:]
-        return self._cached_state(key, B, N, N if beam is None else N + 1, device, eos, pad, min_new, None, None, buffers)
+        return self._cached_state(key, B, N, N if beam is None else N + 1, device, eos, pad, min_new, None, None, buffers, penalty)
 
     def _decode_step(self, st):
         """One token for every sequence, entirely on the device (captured): `tok` at decoder position `pos` -> next token."""
@@ -1679,15 +1741,15 @@ class T5GreedyDecoder(_GraphDecoder):
         ``attention_mask`` [B, P] of 0 / 1 (None: all ones): the encoder input's padding.
         ``num_beams`` > 1: HF's deterministic beam search (``_beam_search``, early_stopping False) with ``length_penalty`` and
         ``repetition_penalty`` -- the start token, then per batch item the best finished beam, cropped to the longest, finished rows filled
-        with ``pad_token_id or eos_token_id``.  Sampling and stopping criteria are not served (NotImplementedError), nor is a repetition
-        penalty on one beam.  A list of several distinct eos ids: a decoder built with ``eos_sets=True`` (``GreedyDecoder.generate``)."""
+        with ``pad_token_id or eos_token_id``.  Sampling and stopping criteria are not served (NotImplementedError).  ``repetition_penalty`` != 1
+        on one beam: a decoder built with ``penalty=True`` (HF's processor inside the step, over the start token and the generated ids);
+        NotImplementedError otherwise.  A list of several distinct eos ids: a decoder built with ``eos_sets=True`` (``GreedyDecoder.generate``)."""
         num_beams = int(num_beams)
         if num_beams < 1 or not float(repetition_penalty) > 0.0:
             raise ValueError(f"num_beams={num_beams} / repetition_penalty={repetition_penalty}: at least one beam, a positive penalty")
         if do_sample or stop_ids or text_stop is not None:
             raise NotImplementedError("T5GreedyDecoder: sampling and stopping criteria are not implemented: use HF generate")
-        if num_beams == 1 and float(repetition_penalty) != 1.0:
-            raise NotImplementedError("repetition_penalty with one beam: use HF generate")
+        penalty = self._one_beam_penalty(repetition_penalty) if num_beams == 1 else 1.0      # (beams: the penalty is the beam state's)
         B, P, _ = inputs_embeds.shape
         pmask = _padding(attention_mask, B, P)
         N = max_new_tokens
@@ -1701,7 +1763,7 @@ class T5GreedyDecoder(_GraphDecoder):
             # HF fills with ``pad_token_id or eos_token_id``: pad 0 fills with eos
             beam = dict(K=K, fill=-1 if eos_token_id is None else int(pad_token_id if pad_token_id else _first_eos(eos_token_id)),
                         repetition_penalty=float(repetition_penalty), length_penalty=1.0 if length_penalty is None else float(length_penalty))
-        st = self._state(B, P, N, dev, dt, eos_token_id, beam["fill"] if beam else pad_token_id, min_new_tokens, pmask is not None, beam)
+        st = self._state(B, P, N, dev, dt, eos_token_id, beam["fill"] if beam else pad_token_id, min_new_tokens, pmask is not None, beam, penalty)
         valid = None if pmask is None else (pmask.to(dev) != 0)
         if st["hip"]:      # (a beam state too: the encoder and the ckv projections run once per batch item)
             if valid is not None:
@@ -1757,11 +1819,13 @@ def keyword_stop_plan(criteria) -> dict:
     return dict(stop_ids=[[int(v) for v in t.tolist()] for c in crit for t in c.keyword_ids], text_stop=text_stop)
 
 
-def make_decoder(lm, weights: str = "bf16", kv_cache: str = "bf16", fp8_beams: bool = False, eos_sets: bool = False):
+def make_decoder(lm, weights: str = "bf16", kv_cache: str = "bf16", fp8_beams: bool = False, eos_sets: bool = False, penalty: bool = False):
     """The graph decoder for a language model: Llama-architecture causal LMs and T5 seq2seq LMs; NotImplementedError otherwise.
     ``weights``: "bf16", or "fp8" / "mxfp4" (Llama only: GreedyDecoder); ``kv_cache``: "bf16", or "fp8" (likewise); ``fp8_beams``: GreedyDecoder's
-    (a T5 decoder has no fp8 cache and does not take it); ``eos_sets``: both decoders' (requests with several distinct eos ids)."""
+    (a T5 decoder has no fp8 cache and does not take it); ``eos_sets``: both decoders' (requests with several distinct eos ids); ``penalty``:
+    both decoders' (one beam with a repetition penalty)."""
     sets = dict(eos_sets=True) if eos_sets else {}
+    sets.update(dict(penalty=True) if penalty else {})
     if getattr(lm.config, "model_type", "") == "t5":
         return T5GreedyDecoder(lm, weights=weights, kv_cache=kv_cache, **sets)
     return GreedyDecoder(lm, weights=weights, kv_cache=kv_cache, **(dict(fp8_beams=True) if fp8_beams else {}), **sets)
@@ -1780,20 +1844,22 @@ def prompt_padding(attention_mask: Tensor) -> Tuple[Optional[bool], Tensor]:
 def decoder_for(owner, lm):
     """The graph decoder for ``lm``, cached on ``owner`` (attribute ``_decoder``): the cached one when it was built for this ``lm`` and the
     weights it re-packed are still the model's (``weights_key``) and in the owner's modes (attributes ``decode_weights`` and ``kv_cache``,
-    "bf16" when it has none; ``fp8_beams`` = "kv8" in its ``beam_search``; ``eos_sets`` = its ``eos_sets`` is "graph"), else a new one
-    (``make_decoder``)."""
+    "bf16" when it has none; ``fp8_beams`` = "kv8" in its ``beam_search``; ``eos_sets`` = its ``eos_sets`` is "graph"; ``penalty`` = its
+    ``penalty_decode`` is "graph"), else a new one (``make_decoder``)."""
     mode = check_decode_weights(getattr(owner, "decode_weights", "bf16"))
     kv = check_kv_cache(getattr(owner, "kv_cache", "bf16"))
     kv8 = "kv8" in check_beam_search(getattr(owner, "beam_search", "hf"))
     sets = check_eos_sets(getattr(owner, "eos_sets", "hf")) == "graph"
+    pen = check_penalty_decode(getattr(owner, "penalty_decode", "hf")) == "graph"
     dec = getattr(owner, "_decoder", None)
     if (dec is None or dec.lm is not lm or dec.key != weights_key(lm) or getattr(dec, "weights", "bf16") != mode
             or getattr(dec, "kv_cache", "bf16") != kv or getattr(dec, "fp8_beams", kv8) != kv8      # (a T5 decoder has no such flag)
-            or getattr(dec, "eos_sets", False) != sets):
+            or getattr(dec, "eos_sets", False) != sets or getattr(dec, "penalty", False) != pen):
         kw = ({} if mode == "bf16" else dict(weights=mode))
         kw.update({} if kv == "bf16" else dict(kv_cache=kv))
         kw.update(dict(fp8_beams=True) if kv8 else {})
         kw.update(dict(eos_sets=True) if sets else {})
+        kw.update(dict(penalty=True) if pen else {})
         dec = owner._decoder = make_decoder(lm, **kw)      # (the default modes: the positional lm alone)
     return dec
 
@@ -1810,6 +1876,9 @@ class Envelope(NamedTuple):
     # opt-in (eos_sets="graph"): several distinct eos ids (up to ops.EOS_MAX, each in [0, vocab_size)) stay on the decoders.  Always given by
     # name (``_replace(eos_sets=True)``); it stands before the beam switches because tests/test_t5_beam_decode.py pins those as the last two fields
     eos_sets: bool = False
+    # opt-in (penalty_decode="graph"): a one-beam request may carry any real ``repetition_penalty`` > 0 (Llama and T5; greedy, and sampling where
+    # ``sampling`` serves it).  Always given by name, and placed before the beam switches for the same reason
+    penalty: bool = False
     beams: bool = False      # opt-in (beam_search="graph"): Llama, num_beams > 1 with any positive repetition_penalty and any length_penalty
     t5_beams: bool = False   # opt-in (beam_search="graph+t5"): the same requests on a T5 as well
 
@@ -1837,7 +1906,7 @@ def envelope_for(owner, module: bool) -> Envelope:
     """The envelope a caller plans with: today's, or its beam twin when the owner opted in (attribute ``beam_search``, "hf" when it has none;
     "graph+t5": the twin with ``t5_beams``; "+kv8" changes the decoder, not the envelope); an owner whose ``eos_sets`` is "graph" gets that
     envelope's ``_replace(eos_sets=True)`` twin, one whose ``sampled_decode`` is "graph" the module envelope's twin with ``sampling`` and the
-    keys ``max_length`` / ``min_length``."""
+    keys ``max_length`` / ``min_length``, one whose ``penalty_decode`` is "graph" the ``_replace(penalty=True)`` twin."""
     mode = check_beam_search(getattr(owner, "beam_search", "hf")).replace("+kv8", "")
     if mode == "graph+t5":
         env = MODULE_ENVELOPE_T5_BEAMS if module else GENERATE_ENVELOPE_T5_BEAMS
@@ -1850,6 +1919,8 @@ def envelope_for(owner, module: bool) -> Envelope:
     if module and check_sampled_decode(getattr(owner, "sampled_decode", "hf")) == "graph":
         # the modules' configurations may sample and give the length as ``max_length`` / ``min_length`` (LSTP.generate's envelope samples already)
         env = env._replace(sampling=True, keys=env.keys | {"max_length", "min_length"})
+    if check_penalty_decode(getattr(owner, "penalty_decode", "hf")) == "graph":
+        env = env._replace(penalty=True)
     return env
 
 
@@ -1872,7 +1943,8 @@ def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: E
     as ``generate(inputs_embeds=..., attention_mask=..., **request)``, or None when it is outside what the graph decoders reproduce (then HF
     ``generate`` runs it).  Inside: a Llama the decoder states (``llama_state``) or a T5 language model on the device, at most one distinct eos
     id (under ``env.eos_sets``: up to ops.EOS_MAX, each in [0, vocab_size)), only keys ``env`` knows, one beam, neutral penalties (or, where
-    ``env.beams`` -- for a T5 ``env.t5_beams`` -- says so, deterministic beam search with a positive repetition penalty), a 0 / 1
+    ``env.beams`` -- for a T5 ``env.t5_beams`` -- says so, deterministic beam search with a positive repetition penalty; under ``env.penalty``
+    one beam with any finite positive repetition penalty, which enters the plan when it is not 1), a 0 / 1
     attention mask with a token in every row (a padded mask goes into the plan as its host copy); greedy, or -- Llama, where ``env`` serves it --
     sampling with temperature / top_k / top_p; ``stopping_criteria`` None or (Llama) KeywordsStoppingCriteria objects (eval/utils/builder_utils.py:
     320-346: recognised by their ``keyword_ids`` / ``keywords`` / ``tokenizer`` attributes)."""
@@ -1894,8 +1966,14 @@ def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: E
         rp, lp = (1.0 if rp is None else rp), (1.0 if lp is None else lp)
         if not ("llama" in mt or (mt == "t5" and env.t5_beams)) or do_sample or crit or not all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in (rp, lp)) or not rp > 0:
             return None
-    elif any(k in request and request[k] not in ok for k, ok in env.neutral.items()):
+    elif any(k in request and request[k] not in ok for k, ok in env.neutral.items() if not (env.penalty and k == "repetition_penalty")):
         return None
+    one_pen = 1.0      # one beam under ``env.penalty``: any real repetition penalty > 0 (None counts as 1); anything else is HF generate's to judge
+    if env.penalty and not beams:
+        one_pen = request.get("repetition_penalty")
+        one_pen = 1.0 if one_pen is None else one_pen
+        if not isinstance(one_pen, (int, float)) or isinstance(one_pen, bool) or not 0 < one_pen < float("inf"):
+            return None
     if (do_sample and not env.sampling) or any(not all(hasattr(c, a) for a in ("keyword_ids", "keywords", "tokenizer")) for c in crit):
         return None
     if mt == "t5" and (do_sample or crit):
@@ -1926,6 +2004,8 @@ def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: E
         plan.update(keyword_stop_plan(crit))
     if beams:
         plan.update(num_beams=K, repetition_penalty=float(rp), length_penalty=float(lp))
+    elif one_pen != 1:      # (a neutral penalty plans exactly as without the opt-in)
+        plan["repetition_penalty"] = float(one_pen)
     return plan
 
 

@@ -449,7 +449,7 @@ class _LSTPBase(nn.Module):
 
     def __init__(self, base_model_path, device="cuda", lora: bool = False, language_model: Optional[nn.Module] = None,
                  compute_dtype="bf16", raft_dtype=None, lm_dtype=None, tgb_cfg: Optional[synth.TgbCfg] = None, decode_weights: str = "bf16",
-                 kv_cache: str = "bf16", beam_search: str = "hf", eos_sets: str = "hf"):
+                 kv_cache: str = "bf16", beam_search: str = "hf", eos_sets: str = "hf", penalty_decode: str = "hf"):
         """Reference signature (eval/utils/model.py:21-45, :240-264): ``LSTP(base_model_path, device, lora=False)`` -- the
         HF config in ``base_model_path`` sizes the vision tower, Q-Former and language model (random init, the checkpoint
         fills them), the TGB is BERT-base with fusion_layer 6, RAFT is RAFT-large.  ``base_model_path`` may also be a
@@ -469,9 +469,13 @@ class _LSTPBase(nn.Module):
         and the T5 graph decoder of the BLIP-2 flavours does the same; "graph+kv8" / "graph+t5+kv8" = opt-in: those, and with ``kv_cache="fp8"``
         the Llama's beams run over the fp8 cache instead of being refused; see decode.GreedyDecoder.generate, decode.T5GreedyDecoder.generate), ``eos_sets``
         ("hf": a request with several distinct eos ids -- Llama-3.1-Instruct's generation config lists three -- runs on HF generate, as before;
-        "graph" = opt-in: the graph decoders serve up to ops.EOS_MAX ids, greedy, sampled and with beams, whatever the other modes)."""
+        "graph" = opt-in: the graph decoders serve up to ops.EOS_MAX ids, greedy, sampled and with beams, whatever the other modes),
+        ``penalty_decode`` ("hf": a ONE-beam request with ``repetition_penalty`` != 1 -- the reference's demo sends 1.5 with every call -- runs on
+        HF generate, as before; "graph" = opt-in: the graph decoders apply HF's RepetitionPenaltyLogitsProcessor inside the captured step, greedy
+        on Llama and T5, sampled on Llama, whatever the other modes; see decode.check_penalty_decode)."""
         super().__init__()
-        from .decode import check_beam_search, check_decode_weights, check_eos_sets, check_kv_cache
+        from .decode import check_beam_search, check_decode_weights, check_eos_sets, check_kv_cache, check_penalty_decode
+        self.penalty_decode = check_penalty_decode(penalty_decode)      # (decode.envelope_for and decode.decoder_for read it from their owner)
         self.decode_weights = check_decode_weights(decode_weights)      # (decode.decoder_for reads it from its owner)
         self.kv_cache = check_kv_cache(kv_cache)                        # (likewise)
         self.beam_search = check_beam_search(beam_search)               # (decode.envelope_for reads it from its owner)
@@ -518,9 +522,9 @@ class _LSTPBase(nn.Module):
 
     @classmethod
     def from_cfg(cls, cfg: synth.PathCfg, device="cuda", language_model: Optional[nn.Module] = None, compute_dtype="bf16", raft_dtype=None,
-                 decode_weights: str = "bf16", kv_cache: str = "bf16", beam_search: str = "hf", eos_sets: str = "hf"):
+                 decode_weights: str = "bf16", kv_cache: str = "bf16", beam_search: str = "hf", eos_sets: str = "hf", penalty_decode: str = "hf"):
         return cls(cfg, device, False, language_model, compute_dtype, raft_dtype, decode_weights=decode_weights, kv_cache=kv_cache, beam_search=beam_search,
-                   eos_sets=eos_sets)
+                   eos_sets=eos_sets, penalty_decode=penalty_decode)
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         """Accepts a reference (Lightning) checkpoint's ``state_dict`` as is: peft's ``language_model.base_model.model.``

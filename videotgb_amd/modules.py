@@ -176,10 +176,11 @@ class _LSTPLightningBase(_Base):
     def __init__(self, model_name_or_path: str, sampler_name_or_path: str, of_extractor_name_or_path: str, temperature: float = 1.0,
                  optimizer=None, scheduler: Optional[str] = None, scheduler_params: Optional[dict] = None,
                  generate_configs: Optional[dict] = None, compute_dtype="bf16", processor=None, tgb_cfg: Optional[synth.TgbCfg] = None,
-                 decode_weights: str = "bf16", kv_cache: str = "bf16", beam_search: str = "hf", eos_sets: str = "hf", sampled_decode: str = "hf"):
+                 decode_weights: str = "bf16", kv_cache: str = "bf16", beam_search: str = "hf", eos_sets: str = "hf", sampled_decode: str = "hf",
+                 penalty_decode: str = "hf"):
         super().__init__()
         self.save_hyperparameters(logger=False)
-        from .decode import check_beam_search, check_decode_weights, check_eos_sets, check_kv_cache, check_sampled_decode
+        from .decode import check_beam_search, check_decode_weights, check_eos_sets, check_kv_cache, check_penalty_decode, check_sampled_decode
         self.decode_weights = check_decode_weights(decode_weights)      # "fp8": models.LSTP's opt-in decode mode (decode.decoder_for reads it)
         self.kv_cache = check_kv_cache(kv_cache)                        # "fp8": models.LSTP's opt-in K/V cache mode (likewise)
         self.beam_search = check_beam_search(beam_search)               # "graph" / "graph+t5" (/ "+kv8"): models.LSTP's opt-in beam search (decode.graph_generate reads it)
@@ -187,6 +188,8 @@ class _LSTPLightningBase(_Base):
         # "graph": the shipped sampled generate_configs -- do_sample, top_p, temperature, max_length / min_length -- stay on the Llama graph
         # decoder (decode.envelope_for reads it; a T5's sampled requests stay on HF generate)
         self.sampled_decode = check_sampled_decode(sampled_decode)
+        # "graph": generate_configs with one beam and a repetition penalty stay on the graph decoders (decode.graph_generate reads it)
+        self.penalty_decode = check_penalty_decode(penalty_decode)
         if not hasattr(self.hparams, "optimizer"):      # the stand-in base: keep what configure_optimizers reads
             self.hparams.optimizer, self.hparams.scheduler, self.hparams.scheduler_params = optimizer, scheduler, scheduler_params or {}
         self.temperature = temperature

@@ -744,6 +744,27 @@ def beam_candidates_eos(logits: Tensor, seq: Tensor, step: Tensor, running: Tens
     return out
 
 
+# ---- repetition penalty on one beam (opt-in: penalty_decode="graph").
+def repetition_penalty(logits: Tensor, seq: Tensor, step: Tensor, penalty: float, start_id: Optional[int] = None, out: Optional[Tensor] = None) -> Tensor:
+    """HF's RepetitionPenaltyLogitsProcessor on one step's logits (vtgb_llm_repetition_penalty): logits [R, V] bf16 / fp32, ``seq`` [R, N]
+    int64, ``step`` device int64 -> fp32 scores [R, V]: x < 0 ? x * penalty : x / penalty at every index among seq[r, :clamp(step, 0, N)] or
+    equal to ``start_id`` (an id that is always seen -- T5's decoder start token; None / -1: none), once whatever the repeats, and
+    float(logit) elsewhere.  Ids outside [0, V) match no index.  With ``out`` ([R, V] fp32, the caller's) nothing is allocated, so the call
+    can be captured.  Returns ``out``."""
+    _need_cuda(logits, seq, step, out)
+    R, V = logits.shape
+    N = seq.shape[1]
+    assert seq.shape == (R, N) and seq.dtype == torch.int64 and step.dtype == torch.int64 and step.numel() == 1
+    assert logits.is_contiguous() and seq.is_contiguous()
+    if out is None:
+        out = torch.empty(R, V, dtype=torch.float32, device=logits.device)
+    assert out.shape == (R, V) and out.dtype == torch.float32 and out.is_contiguous() and out.data_ptr() != logits.data_ptr()
+    a = L.LlmRepetitionPenaltyArgs(dtype_code(logits.dtype), R, V, N, -1 if start_id is None else int(start_id), float(penalty), _ptr(logits),
+                                   _ptr(seq), _ptr(step), _ptr(out))
+    L.check(L.lib().vtgb_llm_repetition_penalty(C.byref(a), _stream()))
+    return out
+
+
 # ---- beam search on the T5 decode step (opt-in: beam_search="graph+t5").  vtgb_llm_attention_rows_beam keeps its scores and the table rows of a
 # (row, head) in LDS: the largest t_pad (= decoder positions of a state) it is launched with, VTGB_LLM_ATTN_ROWS_BEAM_MAX_T of include/vtgb.h.
 ATTENTION_ROWS_BEAM_MAX_KEYS = 1920
