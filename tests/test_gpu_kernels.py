@@ -97,6 +97,8 @@ GEMM_SHAPES = [(257, 384, 128), (2056, 4224, 1408), (300, 1408, 6144), (32, 768,
 @pytest.mark.parametrize("M,N,K", GEMM_SHAPES)
 @pytest.mark.parametrize("dtype", ["bf16", "f32"])
 def test_gemm_epilogues(dev, M, N, K, dtype):
+    """Every shape here has fewer than 200 tiles of 256 x 256, so bf16 runs gemm_bf16_kernel (128 x 128 tile) only; the persistent and the large
+    kernel, padded strides and the element-wise float64 bound are in tests/test_gpu_gemm_large.py."""
     from videotgb_amd import _lib as L, ops
     g = torch.Generator().manual_seed(M * 7 + N)
     td = torch.bfloat16 if dtype == "bf16" else torch.float32
