@@ -270,8 +270,8 @@ def test_vit_folded_layernorm_gemms_on_the_persistent_kernel(dev):
         names = R.kernels_run(lambda: box.append(ops.vit_forward(w, pix)[0]))
         pp = [pp_args(k) for k in names if PP in k]
         lnf = {int(a[0]) for a in pp if is_true(a[6])}
-        assert any(re.search(LARGE + rf"<{EPI_RESID_F32}, 0, false,", k) for k in names), \
-            f"the patch embedding (200 m-tiles, row maps) is meant to reach {LARGE}<EPI_RESID_F32, 0, false>: {names}"
+        assert any(re.search(LARGE + rf"<{EPI_RESID_F32}, false,", k) for k in names), \
+            f"the patch embedding (200 m-tiles, row maps) is meant to reach {LARGE}<EPI_RESID_F32, false>: {names}"
         assert SMALL not in gemm_kernels(names), names
         if fold:      # consumers: qkv (EPI_STORE) and fc1 (EPI_GELU); producers: projection and fc2 (EPI_RESID_F32)
             assert lnf == {EPI_STORE, EPI_GELU, EPI_RESID_F32}, f"the LNF instantiations did not all run: {names}"

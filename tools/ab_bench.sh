@@ -1,10 +1,11 @@
 #!/bin/bash
-# Same-box A/B of the headline (boxes differ by 5-12 %).  The product library is never overwritten:
-#   tools/ab_bench.sh                 -> persistent kernel (default) vs the one-tile-per-workgroup kernel (VTGB_GEMM_OLD=1)
-#   tools/ab_bench.sh path/to/old.so  -> the current build vs another build of libvtgb.so (selected through VTGB_LIB)
-# Run through gpurun from the repo root; prints the headline and the roofline families for A / B / A / B.
+# Same-box A/B of the headline (boxes differ by 5-12 %): the current build vs another build of libvtgb.so, which is selected
+# through VTGB_LIB -- the product library is never overwritten.
+#   tools/ab_bench.sh path/to/other.so
+# Run from the repo root; prints the headline and the roofline families for A / B / A / B.
 cd "${GRAFT_REPO_ROOT:-.}"
 OTHER="$1"
+if [ -z "$OTHER" ] || [ ! -f "$OTHER" ]; then echo "usage: $0 path/to/other/libvtgb.so" >&2; exit 2; fi
 run() {
   python bench.py --full --no-secondary --no-cpu-baseline --steps 4 --warmup 1 2>/dev/null | python -c "
 import json,sys
@@ -13,5 +14,5 @@ print('$1', 'clips/s', d['value'], 'ms/step', d['ms_per_step'], '| conv', r['ach
 }
 for i in 1 2; do
   run new
-  if [ -n "$OTHER" ]; then VTGB_LIB="$(realpath "$OTHER")" run other; else VTGB_GEMM_OLD=1 run old-kernel; fi
+  VTGB_LIB="$(realpath "$OTHER")" run other
 done

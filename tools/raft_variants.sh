@@ -1,8 +1,9 @@
 #!/bin/bash
-# GPU box: per-kernel-variant average times of the RAFT stage (B clips; NWN = forced conv tile: 0 default, 3 = 256x128 instead of 512x128; needs a VTGB_DEBUG_HOOKS build)
-B=${1:-31}; NWN=${2:-0}
+# GPU box: per-kernel-variant average times of the RAFT stage (B clips)
+B=${1:-31}
+ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/rt; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rt -- python3 $GRAFT_REPO_ROOT/tools/raft_bench.py $B $NWN > /tmp/rt.log 2>&1
+rm -rf /tmp/rt; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rt -- python3 "$ROOT/tools/raft_bench.py" $B > /tmp/rt.log 2>&1
 tail -1 /tmp/rt.log
 python3 - <<'PY'
 import csv, glob

@@ -43,7 +43,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         if verbose:
             cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
         cmd[1:1] = os.environ.get("VTGB_CFLAGS", "").split()      # experiments: e.g. VTGB_CFLAGS=-DVTGB_SPREAD=0
-        if os.environ.get("VTGB_DEBUG_HOOKS") == "1":      # experiment knobs + timing-only ablation kernels (tools/gemm_ablate.py)
+        if os.environ.get("VTGB_DEBUG_HOOKS") == "1":      # the A/B switches of raft.hip and raft_enc.hip
             cmd.insert(1, "-DVTGB_DEBUG_HOOKS")
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
     failed = False

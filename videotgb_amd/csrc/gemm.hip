@@ -245,7 +245,6 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const GemmDesc p) {
 // m-tiles, and the ~32 workgroups resident on one XCD form a 4 (m) x 8 (n) super-tile so
 // that every A k-slice fetched into that L2 is used by 8 workgroups and every W k-slice by 4.
 // Requires K % 64 == 0 (every GEMM of the full-size path); anything else uses the kernel above.
-// ABL != 0: timing-only ablation builds for tools/gemm_ablate.py (results are wrong).
 // ---------------------------------------------------------------------------------------
 constexpr int L_BM = 256, L_BN = 256, L_BK = 64;
 __device__ __forceinline__ bool gru_staged(const GemmDesc& p) {
@@ -258,48 +257,10 @@ constexpr int L_LDS = (L_A_SLOTS + L_W_SLOTS) * L_OP_BYTES;   // 160 KiB
 // NWN (waves along N): 4 = the 256 x 256 tile above; 2 / 1 = 256 x 128 / 256 x 64 tiles for narrow outputs
 // (RAFT's 64..128-channel convolutions): waves 4(M) x 2(N) of 64 x 64 or 8(M) x 1(N) of 32 x 64, so that all
 // eight waves have work and only the output channels that exist are staged (weight slots of 16 / 8 KiB).
-// debug: shader-clock cycles and 100 MHz reference ticks spent inside the large kernel (summed over
-// workgroups), so that tools/gemm_ablate.py can report the clock the chip actually holds under each variant
-__device__ unsigned long long g_clk[2];
-#ifdef VTGB_DEBUG_HOOKS
-__device__ unsigned long long g_stamp[8];   // exp 10 / 11: prologue phase sums (10 ns ticks) + tile count; per-wave landing times
-extern "C" void vtgb_debug_read_stamps(unsigned long long* out, int reset) {
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamp), sizeof(g_stamp));
-    if (reset) {
-        const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_stamp), z, sizeof(z));
-    }
-}
-__device__ int g_exp_dev = 0;   // experiment selector read by the large kernel (debug-hook builds only)
-extern "C" void vtgb_debug_set_exp(int v) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_exp_dev), &v, sizeof(v)); }
-#endif
-#ifdef VTGB_DEBUG_HOOKS
-extern "C" void vtgb_debug_read_clk(unsigned long long* out, int reset) {
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_clk), sizeof(g_clk));
-    if (reset) {
-        const unsigned long long z[2] = {0, 0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_clk), z, sizeof(z));
-    }
-}
-#endif
-struct ClkScope {
-    unsigned long long c0, r0;
-    bool on;
-    __device__ ClkScope(bool enable) : on(enable) {
-        if (on) { c0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); }
-    }
-    __device__ void stop() {
-        if (on && threadIdx.x == 0) {
-            atomicAdd(&g_clk[0], __builtin_amdgcn_s_memtime() - c0);
-            atomicAdd(&g_clk[1], __builtin_amdgcn_s_memrealtime() - r0);
-        }
-    }
-};
-
-// NXF (activation fragments per wave, default 2 NWN): NWN = 2 with NXF = 8 is a 512 x 128 tile -- waves 4(M) x 2(N) of
-// 128 x 64, the SAME wave tile (and LDS-read : MFMA ratio, 12 fragment reads per 32 MFMAs) as the 256 x 256 tile, for
-// 128-channel outputs with many rows (RAFT's GRU q convolution, the 126-channel motion-encoder output, the stage 2 / 3
-// encoder convolutions); its activation slot is 64 KiB, so the ring is 2 activation + 2 weight slots = 160 KiB.
+// Every tile is 256 rows high.  (A 512 x 128 tile -- the 256 x 256 tile's 128 x 64 wave tile on 128-channel outputs -- measured
+// NO faster than 256 x 128 on RAFT's 128-channel convolutions in round 2 (GRU q: 1.69 vs 1.71 ms before the epilogue change,
+// 1.76 vs 1.61 ms after it) and is gone: every tile shape sits at the same ~30 GB/s per CU of operand fill, which is what
+// bounds them, not the fragment-read ratio.)
 
 // Column-statistics fold (EPI_STORE_F32 + col_stats): 64 NWN threads add up the MW waves' partial sums of a column (parked in the
 // waves' staging regions) and store them to the tile's slot of the partial-moment buffer (r5: was one atomic per (image, column, moment)).  Run by waves 0 .. NWN-1 WHETHER OR NOT their own
@@ -323,14 +284,10 @@ struct ClkScope {
         }                                                                                                           \
     }
 
-template <int EPI, int ABL = 0, bool CONV = false, int NWN = 4, int NXF = 2 * NWN>
+template <int EPI, bool CONV = false, int NWN = 4>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_large_kernel(const GemmDesc p, const int m_tiles, const int n_tiles, const int G) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the host pass needs only the launch stub (and cannot type the buffer-descriptor builtins)
-    ClkScope clk(ABL != 0);
-#ifdef VTGB_DEBUG_HOOKS
-    const unsigned long long t_entry = __builtin_amdgcn_s_memrealtime();
-#endif
-    constexpr int NX = NXF;              // activation fragments per wave: wave tile = (16 NX) x 64
+    constexpr int NX = 2 * NWN;          // activation fragments per wave: wave tile = (16 NX) x 64
     constexpr int WROWS = 16 * NX;       // rows of the wave tile
     constexpr int MW = 8 / NWN;          // waves along M
     constexpr int T_BN = 64 * NWN;       // tile width
@@ -340,10 +297,10 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_large_kernel(const GemmDesc 
     // activation ring: 3 slots; 2 for the 64-wide tile, whose 80 KiB then let TWO workgroups share a CU (these tiles
     // have few k-tiles -- K = 576 for RAFT's 64-channel 3x3 convolutions -- so prologue and epilogue are a third of
     // a tile's life and overlap with the other workgroup's k-loop instead of idling the CU)
-    constexpr int T_BM = MW * WROWS;     // tile height: 256, or 512 (NWN = 2, NXF = 8)
+    constexpr int T_BM = MW * WROWS;     // tile height: 256 for every NWN
     constexpr int A_OP = T_BM * 128;     // bytes per activation slot
     constexpr int AI = T_BM / 64;        // activation DMA instructions per wave and k-tile (8 rows each)
-    constexpr int A_SLOTS = (NWN == 1 || T_BM > 256) ? 2 : 3;
+    constexpr int A_SLOTS = NWN == 1 ? 2 : 3;
     char* const smem_w = smem + A_SLOTS * A_OP;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -441,21 +398,12 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_large_kernel(const GemmDesc 
         __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (lptr_t)(smem_w + (slot) * W_OP + (wave * (8 * WI) + i * 8) * 128), 16, w_voff[i], (k0) * 2, 0, 0);
     const int nk = p.K / L_BK;
     const int fr = lane & 15, fg = lane >> 4;
-#ifdef VTGB_DEBUG_HOOKS
-    const unsigned long long t_setup = __builtin_amdgcn_s_memrealtime();
-#endif
     // The first k-tile's DMAs go out FIRST; the accumulator start values (bias: one 16-byte load per weight-fragment column group,
     // not one per accumulator block; + fp32 residual / bf16 start map) are requested behind them, so the two latencies overlap.
-    // (In-kernel stamps, tools/exp/prologue_probe.py: with the start values loaded first -- and the adds that consume them
-    // waiting for every one -- that phase alone was 4.2 us of a 46 us qkv tile and 20 us of a 60 us projection tile.)
-#ifdef VTGB_DEBUG_HOOKS
-    const unsigned long long t_init = __builtin_amdgcn_s_memrealtime();
-#endif
+    // (In-kernel time stamps of the prologue phases, since removed: with the start values loaded first -- and the adds that consume
+    // them waiting for every one -- that phase alone was 4.2 us of a 46 us qkv tile and 20 us of a 60 us projection tile.)
     L_ISSUE_A(0, 0)
     L_ISSUE_W(0, 0)
-#ifdef VTGB_DEBUG_HOOKS
-    const unsigned long long t_issued = __builtin_amdgcn_s_memrealtime();
-#endif
     // EPI_RESID_F32 through the staged fp32 store: the residual tile (256 KB) is NOT preloaded into the accumulators (16 rows x
     // 64 B per load instruction, all of it waited for before the first MFMA: 20 us of a 60 us projection tile) but added in the
     // epilogue from whole 256-byte row segments requested one pass ahead
@@ -500,19 +448,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_large_kernel(const GemmDesc 
     if (A_SLOTS == 3 && nk > 2) __builtin_amdgcn_s_waitcnt(0x0F70 | (2 * AI + WI));   // vmcnt(2 AI + WI): A(0), W(0) landed
     else if (nk >= 2) __builtin_amdgcn_s_waitcnt(0x0F70 | (AI + WI));                 // vmcnt(AI + WI)
     else __builtin_amdgcn_s_waitcnt(0x0F70);               // vmcnt(0)
-#ifdef VTGB_DEBUG_HOOKS
-    const unsigned long long t_landed = __builtin_amdgcn_s_memrealtime();
-#endif
     __builtin_amdgcn_s_barrier();
-#ifdef VTGB_DEBUG_HOOKS
-    if ((g_exp_dev & 0xff) == 10 && tid == 0) {   // prologue phases of wave 0 (10 ns ticks): setup | acc init issue | DMA issue | wait | barrier; tile count
-        const unsigned long long t_bar = __builtin_amdgcn_s_memrealtime();
-        atomicAdd(&g_stamp[0], t_setup - t_entry); atomicAdd(&g_stamp[1], t_init - t_setup); atomicAdd(&g_stamp[2], t_issued - t_init);
-        atomicAdd(&g_stamp[3], t_landed - t_issued); atomicAdd(&g_stamp[4], t_bar - t_landed); atomicAdd(&g_stamp[5], 1ull);
-        atomicAdd(&g_clk[0], t_bar - t_entry); atomicAdd(&g_clk[1], 1ull);
-    }
-    if ((g_exp_dev & 0xff) == 11 && lane == 0) atomicAdd(&g_stamp[wave], t_landed - t_entry);   // per wave: entry -> its own first operands landed
-#endif
 
     // fragment byte offsets inside an operand tile for the two 32-deep halves of a k-tile
     int w_off[2][4], x_off[2][NX];
@@ -535,15 +471,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_large_kernel(const GemmDesc 
     //   read half 1 of tile t | MFMAs of half 0 | counted wait + barrier (tile t fully read by everyone;
     //   A(t+1), W(t+1) visible) | re-arm the freed slots with W(t+2), A(t+3) | read half 0 of tile t+1 |
     //   MFMAs of half 1
-#ifdef VTGB_DEBUG_HOOKS
-    if (g_exp_dev == 1 && wave >= 4) __builtin_amdgcn_s_setprio(1);
-    if (g_exp_dev == 2 && wave < 4) __builtin_amdgcn_s_setprio(1);
-    if (g_exp_dev == 3 && (wave & 1)) __builtin_amdgcn_s_setprio(1);
-    if ((g_exp_dev & 0xff) == 4 && bid < 256) {   // phase-stagger the first wave of workgroups: CU slot c of 32 waits c/32 of (g_exp_dev >> 8) us
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime(), ticks = (unsigned long long)((bid >> 3) & 31) * (g_exp_dev >> 8) * 100 / 32;
-        while (__builtin_amdgcn_s_memrealtime() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
-    }
-#endif
     int a_slot = 0;   // A(t) lives in slot t % 3, W(t) in slot t % 2
     if (!wave_active) {
         // same DMA issues, waits and barriers as the active waves, nothing else
@@ -558,7 +485,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_large_kernel(const GemmDesc 
         if constexpr (EPI == EPI_STORE || EPI == EPI_GELU) {
             if (EPI == EPI_STORE && p.frag_out) return;        // fragment-order stores use no LDS: no barrier to join
             if (staged_store) __builtin_amdgcn_s_barrier();   // the barrier in front of the LDS-staged stores
-            if constexpr (EPI == EPI_STORE && NWN == 4 && NXF == 8) {
+            if constexpr (EPI == EPI_STORE && NWN == 4) {
                 if (staged_store && p.tail_w) __builtin_amdgcn_s_barrier();   // ... and the one in front of the fused 1x1 tail
             }
         } else if constexpr (EPI == EPI_RESID_F32 || EPI == EPI_STORE_F32) {
@@ -598,22 +525,18 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_large_kernel(const GemmDesc 
         const char* ws = smem_w + (kt & 1) * W_OP;                                                     \
         const int a_nxt = a_slot == A_SLOTS - 1 ? 0 : a_slot + 1;                                      \
         const int a_prv = a_slot == 0 ? A_SLOTS - 1 : a_slot - 1;                                      \
-        if constexpr (!(ABL & 1)) { if (DEFER) { L_ISSUE_A(a_prv, (kt - 1 + A_SLOTS) * L_BK) } }       \
+        if (DEFER) { L_ISSUE_A(a_prv, (kt - 1 + A_SLOTS) * L_BK) }                                     \
         L_READ(wf1, xf1, as, ws, 1)                                                                    \
         L_MFMA(wf0, xf0)                                                                               \
-        if constexpr (!(ABL & 1) && A_SLOTS == 3) { L_SCHED_IL(AI) }                                   \
-        if constexpr (!(ABL & 8)) {                                                                    \
-            if (WAIT4) __builtin_amdgcn_s_waitcnt(0x0074);   /* vmcnt(4) lgkmcnt(0): all but A(t+2) landed */ \
-            else __builtin_amdgcn_s_waitcnt(0x0070);         /* vmcnt(0) lgkmcnt(0) */                 \
-            __builtin_amdgcn_s_barrier();                                                              \
-        }                                                                                              \
-        if constexpr (!(ABL & 1)) {                                                                    \
-            if (WCOND) { L_ISSUE_W(kt & 1, (kt + 2) * L_BK) }                                          \
-            if (ACOND) { L_ISSUE_A(a_slot, (kt + A_SLOTS) * L_BK) }                                    \
-        }                                                                                              \
+        if constexpr (A_SLOTS == 3) { L_SCHED_IL(AI) }                                                 \
+        if (WAIT4) __builtin_amdgcn_s_waitcnt(0x0074);   /* vmcnt(4) lgkmcnt(0): all but A(t+2) landed */ \
+        else __builtin_amdgcn_s_waitcnt(0x0070);         /* vmcnt(0) lgkmcnt(0) */                     \
+        __builtin_amdgcn_s_barrier();                                                                  \
+        if (WCOND) { L_ISSUE_W(kt & 1, (kt + 2) * L_BK) }                                              \
+        if (ACOND) { L_ISSUE_A(a_slot, (kt + A_SLOTS) * L_BK) }                                        \
         L_READ(wf0, xf0, smem + a_nxt * A_OP, smem_w + ((kt + 1) & 1) * W_OP, 0)                       \
         L_MFMA(wf1, xf1)                                                                               \
-        if constexpr (!(ABL & 1)) { L_SCHED_IL(A_SLOTS == 3 ? WI : WI + AI) }                          \
+        L_SCHED_IL(A_SLOTS == 3 ? WI : WI + AI)                                                        \
         /* the half-0 fragments of the next tile were requested 32 MFMAs ago: this wait is free, and it lets hipcc's      \
            waitcnt pass see (at the loop-header join) that set 0 is complete */                        \
         __builtin_amdgcn_s_waitcnt(0xC07F);                                                            \
@@ -635,21 +558,11 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_large_kernel(const GemmDesc 
         L_MFMA(wf0, xf0)
         L_MFMA(wf1, xf1)
     }
-    clk.stop();
 #undef L_READ
 #undef L_MFMA
 #undef L_ISSUE_A
 #undef L_ISSUE_W
     // D layout: column (lane & 15) <- X row (m), rows (lane >> 4) * 4 + reg <- W row (n)
-    if constexpr ((ABL & 16) != 0) {   // timing-only: no epilogue (keep the accumulators live)
-        float t = 0.f;
-#pragma unroll
-        for (int j = 0; j < NX; j++)
-#pragma unroll
-            for (int i = 0; i < 4; i++) t += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-        if (t == 123.456f) reinterpret_cast<float*>(p.out)[0] = t;
-        return;
-    }
     if constexpr (EPI == EPI_STORE) {
         if (p.frag_out) {   // fragment order: straight from the accumulators, 512 contiguous bytes per wave instruction, no LDS
             bf16x4* fdst = reinterpret_cast<bf16x4*>(p.out) + ((int64_t)(mt * n_tiles + nt) * 8 + wave) * (NX * 4 * 64) + lane;
@@ -685,7 +598,7 @@ gelu_erf_fast4(v);
                     const int row = j * 16 + fr, c16 = (i * 2 + (fg >> 1)) ^ (row & 7);
                     *reinterpret_cast<bf16x4*>(cst + row * 128 + c16 * 16 + (fg & 1) * 8) = pk;
                 }
-            if constexpr (EPI == EPI_STORE && NWN == 4 && NXF == 8) {
+            if constexpr (EPI == EPI_STORE && NWN == 4) {
                 if (p.tail_w) {
                     // Fused 1x1 tail: T[256 px][32] = tile[256 px][256 ch] . tail_w[32][256]^T.  The activated bf16 tile is in LDS
                     // (wave (wm, wn) owns rows wm * 128 .., columns wn * 64 .. as 128-byte rows, 16-byte chunks XOR row & 7); the
@@ -721,11 +634,6 @@ gelu_erf_fast4(v);
                 }
             }
             bf16_t* const outp = reinterpret_cast<bf16_t*>(p.out);
-#ifdef VTGB_DEBUG_HOOKS
-            const bool skip_store = (g_exp_dev & 0xff) == 5;   // timing only: the whole epilogue but the global stores
-#else
-            constexpr bool skip_store = false;
-#endif
             // operands of the fused elementwise tails (r * h gate, ResidualBlock skip): all rows' loads in flight before the
             // first store, not one HBM round trip per row
             const bool gated = EPI == EPI_STORE && p.gate_from > 0, resd = EPI == EPI_STORE && !gated && p.resid_bf16 != nullptr;
@@ -746,10 +654,6 @@ gelu_erf_fast4(v);
                     }
                 }
             }
-#ifdef VTGB_DEBUG_HOOKS
-            unsigned long long ts0 = 0;
-            if ((g_exp_dev & 0xff) == 6) ts0 = __builtin_amdgcn_s_memrealtime();
-#endif
             // Every LDS read of the wave's tile is issued before its first global store, and the common case (identity row
             // map, no fused tail) runs a branch-free store loop: stores then leave back to back.  (Interleaved
             // read -> address -> store through the general path cost 8.2 us per wave for 16 stores -- 15 GB/s per CU against
@@ -786,7 +690,7 @@ gelu_erf_fast4(v);
                 }
             }
             const int mrow = m0 + wm * WROWS + (lane >> 3);
-            const bool nok = nn < p.N && !skip_store;
+            const bool nok = nn < p.N;
             if (to_out2 || p.o_map.seg_rows == 0) {
                 bf16_t* const o = to_out2 ? reinterpret_cast<bf16_t*>(p.out2) + (int64_t)mrow * p.ldo2 + (nn - p.gate_from) : outp + (int64_t)mrow * p.ldo + nn;
                 const int64_t step = (int64_t)8 * (to_out2 ? p.ldo2 : p.ldo);
@@ -798,14 +702,6 @@ gelu_erf_fast4(v);
                 for (int rr = 0; rr < WROWS / 8; rr++)
                     if (nok && mrow + rr * 8 < p.M) *reinterpret_cast<uint4*>(outp + map_row(p.o_map, mrow + rr * 8) * p.ldo + nn) = vv[rr];
             }
-#ifdef VTGB_DEBUG_HOOKS
-            if ((g_exp_dev & 0xff) == 6) {   // per wave: 10 ns ticks from the first store's issue to the last one's, and to their completion
-                const unsigned long long ts1 = __builtin_amdgcn_s_memrealtime();
-                __builtin_amdgcn_s_waitcnt(0x0F70);
-                const unsigned long long ts2 = __builtin_amdgcn_s_memrealtime();
-                if (lane == 0) { atomicAdd(&g_clk[0], ts1 - ts0); atomicAdd(&g_clk[1], ts2 - ts0); }
-            }
-#endif
             return;
         }
     }
@@ -1061,56 +957,19 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmDesc p) {
     }
 }
 
-// round 3: the persistent ping-pong form of the large kernel (gemm_pp.hip); VTGB_GEMM_OLD=1 keeps the one-tile-per-workgroup kernel
+// round 3: the persistent ping-pong form of the large kernel (gemm_pp.hip) takes every launch that pp_supported accepts; the
+// one-tile-per-workgroup kernel above serves the rest
 template <int EPI, bool CONV, int NWN, int WF = 4>
 int launch_large_pp(const GemmDesc& d, hipStream_t s);
 bool pp_supported(const GemmDesc& d);
-// (A/B switches -- VTGB_GEMM_OLD=1, VTGB_PP_MASK=<bits> -- exist only in builds with -DVTGB_DEBUG_HOOKS: the production library reads no
-// environment variable)
-static bool use_old_large() {
-#ifdef VTGB_DEBUG_HOOKS
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("VTGB_GEMM_OLD"); v = (e && e[0] == '1') ? 1 : 0; }
-    return v == 1;
-#else
-    return false;
-#endif
-}
-// bisecting aid: VTGB_PP_MASK = bit set of launch classes that may use the persistent kernel (default: all)
-//   1 plain GEMM   2 conv 256-wide bf16 store   4 conv + fused 1x1 tail   8 conv 128-wide bf16 store   16 GRU   32 conv fp32 store
-static bool pp_class_enabled(int epi, bool conv, int nwn, bool tail) {
-#ifdef VTGB_DEBUG_HOOKS
-    static int mask = -1;
-    if (mask < 0) { const char* e = getenv("VTGB_PP_MASK"); mask = e ? atoi(e) : 63; }
-#else
-    const int mask = 63;
-#endif
-    int c;
-    if (!conv) c = 1;
-    else if (epi == EPI_GRU) c = 16;
-    else if (epi == EPI_STORE_F32) c = 32;
-    else if (tail) c = 4;
-    else c = nwn == 4 ? 2 : 8;
-    return (mask & c) != 0;
-}
 
-// tile-count threshold above which the 256x256 LDS-DMA kernel is used (tunable for experiments)
-// Experiment knobs.  The setters (and the timing-only ablation instantiations, whose results are WRONG by construction) exist
-// only in builds with -DVTGB_DEBUG_HOOKS (VTGB_DEBUG_HOOKS=1 python -m videotgb_amd.build; tools/gemm_ablate.py): the
-// production library exports none of them.
-static int g_large_min_tiles = 200;
-static int g_large_variant = 0;   // > 0 forces the m-tiles per XCD super-tile (G); 0 = heuristic
-static int g_ablate = 0;          // 1 no DMA, 2 one LDS stage, 4 no LDS reads, 8 no barrier (timing only)
-#ifdef VTGB_DEBUG_HOOKS
-extern "C" void vtgb_debug_set_gemm_large_min_tiles(int v) { g_large_min_tiles = v; }
-extern "C" void vtgb_debug_set_gemm_large_variant(int v) { g_large_variant = v; }
-extern "C" void vtgb_debug_set_gemm_ablate(int v) { g_ablate = v; }
-#endif
+// tile count (256 x 256 tiles) from which a plain GEMM uses the LDS-DMA kernels instead of the 128 x 128 kernel
+constexpr int L_MIN_TILES = 200;
 
 // The large kernel addresses its operands as (tile base descriptor) + 32-bit byte offset: true when every offset inside one
 // tile fits (row maps must be monotone: a 256-row tile then spans 256 rows plus the gaps of the segments it crosses).
 static bool large_kernel_addressable(const GemmDesc& d) {
-    int64_t span = 512;                                        // rows of the widest tile
+    int64_t span = 512;                                        // a row bound that covers every tile (they are 256 rows high)
     if (d.a_map.seg_rows != 0) {
         if (d.a_map.seg_stride < d.a_map.seg_rows) return false;
         span += (512 / d.a_map.seg_rows + 2) * (d.a_map.seg_stride - d.a_map.seg_rows);
@@ -1129,31 +988,17 @@ template <int EPI>
 static int launch_epi(const GemmDesc& d, hipStream_t s) {
     if (d.dtype == VTGB_BF16) {
         const int m_tiles = (d.M + L_BM - 1) / L_BM, n_tiles = (d.N + L_BN - 1) / L_BN;
-        if ((d.K % L_BK) == 0 && (int64_t)m_tiles * n_tiles >= g_large_min_tiles && large_kernel_addressable(d)) {
+        if ((d.K % L_BK) == 0 && (int64_t)m_tiles * n_tiles >= L_MIN_TILES && large_kernel_addressable(d)) {
+            if (pp_supported(d)) return launch_large_pp<EPI, false, 4>(d, s);
+            VTGB_REQUIRE(!d.ln_xb && !d.ln_stats, VTGB_EUNSUPPORTED, "gemm: the folded LayerNorm needs the persistent or the 128 x 128 kernel (row maps / alignment)");
             // m-tiles per XCD super-tile: measured best 2 for narrow outputs (<= 8 n-tiles), 8 for wide ones
-            const int G = g_large_variant > 0 ? g_large_variant : (n_tiles <= 8 ? 2 : 8);
+            const int G = n_tiles <= 8 ? 2 : 8;
             const int mx = (m_tiles + 7) / 8, groups = (mx + G - 1) / G;
             const dim3 grid(8 * groups * G * n_tiles);
-            if (!use_old_large() && !g_ablate && pp_supported(d) && pp_class_enabled(EPI, false, 4, false)) return launch_large_pp<EPI, false, 4>(d, s);
-            VTGB_REQUIRE(!d.ln_xb && !d.ln_stats, VTGB_EUNSUPPORTED, "gemm: the folded LayerNorm needs the persistent or the 128 x 128 kernel (row maps / alignment)");
             ProfScope prof(VTGB_PROF_GEMM, 2.0 * d.M * d.N * d.K, s);
-#ifdef VTGB_DEBUG_HOOKS
-            if (g_ablate && (EPI == EPI_STORE || EPI == EPI_RESID_F32)) {
-#define ABL_CASE(v)                                                                                              \
-    case v:                                                                                                       \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_large_kernel<EPI, v>),                 \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, L_LDS);                            \
-        hipLaunchKernelGGL((gemm_bf16_large_kernel<EPI, v>), grid, dim3(512), L_LDS, s, d, m_tiles, n_tiles, G);    \
-        break;
-                switch (g_ablate) { ABL_CASE(1) ABL_CASE(8) ABL_CASE(16) ABL_CASE(17) ABL_CASE(25) ABL_CASE(32) default: break; }
-#undef ABL_CASE
-            } else
-#endif
-            {
-                static DeviceOnce attr0;
-                VTGB_FUNC_LDS_ONCE(attr0, (gemm_bf16_large_kernel<EPI, 0>), L_LDS);
-                hipLaunchKernelGGL((gemm_bf16_large_kernel<EPI, 0>), grid, dim3(512), L_LDS, s, d, m_tiles, n_tiles, G);
-            }
+            static DeviceOnce attr0;
+            VTGB_FUNC_LDS_ONCE(attr0, (gemm_bf16_large_kernel<EPI>), L_LDS);
+            hipLaunchKernelGGL((gemm_bf16_large_kernel<EPI>), grid, dim3(512), L_LDS, s, d, m_tiles, n_tiles, G);
             VTGB_HIP(hipGetLastError());
             return VTGB_OK;
         }
@@ -1173,58 +1018,37 @@ static int launch_epi(const GemmDesc& d, hipStream_t s) {
 
 // Implicit-GEMM convolution (and plain GEMMs that need the activation / GRU epilogues) on the large
 // kernel.  d.conv_KH == 0: plain GEMM through the same kernel (RAFT's 1x1 convolutions).
-template <int EPI, bool CONV, int NWN, int NXF = 2 * NWN>
+template <int EPI, bool CONV, int NWN>
 static int launch_large_nwn(const GemmDesc& d, hipStream_t s) {
-    constexpr int T_BM = (8 / NWN) * 16 * NXF, T_BN = 64 * NWN;
-    constexpr int LDS = ((NWN == 1 || T_BM > 256) ? 2 : 3) * T_BM * 128 + L_W_SLOTS * T_BN * 128;
+    constexpr int T_BM = 256, T_BN = 64 * NWN;
+    constexpr int LDS = (NWN == 1 ? 2 : 3) * T_BM * 128 + L_W_SLOTS * T_BN * 128;
     const int m_tiles = (d.M + T_BM - 1) / T_BM, n_tiles = (d.N + T_BN - 1) / T_BN;
     const int G = n_tiles <= 8 ? 2 : 8;
     const int mx = (m_tiles + 7) / 8, groups = (mx + G - 1) / G;
-    if constexpr (NXF == 2 * NWN) {
-        if constexpr (!(EPI == EPI_GRU && NWN == 4) && NWN != 1) {      // (64-wide tiles: two workgroups per CU already overlap prologues)
-            if (!use_old_large() && pp_supported(d) && pp_class_enabled(EPI, CONV, NWN, d.tail_w != nullptr)) return launch_large_pp<EPI, CONV, NWN>(d, s);
-        }
+    if constexpr (!(EPI == EPI_GRU && NWN == 4) && NWN != 1) {      // (64-wide tiles: two workgroups per CU already overlap prologues)
+        if (pp_supported(d)) return launch_large_pp<EPI, CONV, NWN>(d, s);
     }
     static DeviceOnce attr;
-    VTGB_FUNC_LDS_ONCE(attr, (gemm_bf16_large_kernel<EPI, 0, CONV, NWN, NXF>), LDS);
+    VTGB_FUNC_LDS_ONCE(attr, (gemm_bf16_large_kernel<EPI, CONV, NWN>), LDS);
     const double exec_flops = 2.0 * d.M * d.N * d.K;
     ProfScope prof(CONV ? VTGB_PROF_CONV : VTGB_PROF_GEMM, d.algo_flops > 0 ? d.algo_flops : d.algo_flops < 0 ? 0.0 : exec_flops, s, exec_flops);
-    hipLaunchKernelGGL((gemm_bf16_large_kernel<EPI, 0, CONV, NWN, NXF>), dim3(8 * groups * G * n_tiles), dim3(512), LDS, s, d, m_tiles, n_tiles, G);
+    hipLaunchKernelGGL((gemm_bf16_large_kernel<EPI, CONV, NWN>), dim3(8 * groups * G * n_tiles), dim3(512), LDS, s, d, m_tiles, n_tiles, G);
     VTGB_HIP(hipGetLastError());
     return VTGB_OK;
 }
 
-static int g_conv_nwn = 0;   // > 0 forces the tile (experiments: 1, 2, 4 = waves along N; 5 = the 512 x 128 tile for 128-wide outputs); 0 = by shape
-#ifdef VTGB_DEBUG_HOOKS
-extern "C" void vtgb_debug_set_conv_nwn(int v) { g_conv_nwn = v; }
-#endif
-
+// The tile follows the output width alone: N <= 64 -> 256 x 64, N <= 128 -> 256 x 128, else 256 x 256.  (The fused 1x1 tail exists
+// only in the 256-wide tile -- launch_conv_gemm requires N == 256 for it -- and a fragment-order map's producer and consumer get
+// the same tile because both come through this rule.)
 template <int EPI, bool CONV>
-static int launch_large_forced(const GemmDesc& d, hipStream_t s) {
-    const int nwn = (g_conv_nwn > 0 && g_conv_nwn != 5) ? g_conv_nwn : (d.N <= 64 ? 1 : d.N <= 128 ? 2 : 4);
-    const int nwn_shape = d.N <= 64 ? 1 : d.N <= 128 ? 2 : 4;
-    // the fused 1x1 tail exists only in the 256-wide tile, and fragment-order maps are only meaningful between launches of ONE tile
-    // shape (the one the shape rule picks): a forced tile (debug hook) would otherwise succeed and leave the output unwritten / scrambled
-    VTGB_REQUIRE(!d.tail_w || nwn == 4, VTGB_EUNSUPPORTED, "conv gemm: the fused 1x1 tail needs the 256-wide tile (forced tile %d)", nwn);
-    VTGB_REQUIRE(!(d.frag_out || d.init_frag) || nwn == nwn_shape, VTGB_EUNSUPPORTED,
-                 "conv gemm: fragment-order start maps need the producer's and the consumer's tile shape to agree (forced tile %d, shape rule %d)", nwn, nwn_shape);
+static int launch_large_by_width(const GemmDesc& d, hipStream_t s) {
     if constexpr (EPI == EPI_STORE && CONV) {
         // 128 < N <= 192 (RAFT's convc2: 192 channels): the 256 x 192 tile whose eight waves all multiply (gemm_pp.hip, WF = 3)
-        if (g_conv_nwn == 0 && d.N > 128 && d.N <= 192 && (d.N & 7) == 0 && !use_old_large() && pp_supported(d) && !d.frag_out && !d.init_bf16 && d.gate_from == 0 &&
-            !d.resid_bf16 && !d.tail_w && pp_class_enabled(EPI, CONV, 4, false))
+        if (d.N > 128 && d.N <= 192 && (d.N & 7) == 0 && pp_supported(d) && !d.frag_out && !d.init_bf16 && d.gate_from == 0 && !d.resid_bf16 && !d.tail_w)
             return launch_large_pp<EPI, CONV, 4, 3>(d, s);
     }
-    if (nwn == 1) return launch_large_nwn<EPI, CONV, 1>(d, s);
-    if (nwn == 2) {
-        // The 512 x 128 tile (same wave tile as 256 x 256) measured NO faster than 256 x 128 on RAFT's 128-channel
-        // convolutions (GRU q: 1.69 vs 1.71 ms before the epilogue change, 1.76 vs 1.61 ms after it; round 2): every tile
-        // shape sits at the same ~30 GB/s per CU of operand fill, which is what bounds them, not the fragment-read ratio.
-        // It stays selectable for experiments only.
-#ifdef VTGB_DEBUG_HOOKS
-        if (g_conv_nwn == 5 && d.M >= 512 * 1024 && !d.col_stats) return launch_large_nwn<EPI, CONV, 2, 8>(d, s);
-#endif
-        return launch_large_nwn<EPI, CONV, 2>(d, s);
-    }
+    if (d.N <= 64) return launch_large_nwn<EPI, CONV, 1>(d, s);
+    if (d.N <= 128) return launch_large_nwn<EPI, CONV, 2>(d, s);
     return launch_large_nwn<EPI, CONV, 4>(d, s);
 }
 
@@ -1289,11 +1113,11 @@ int launch_conv_gemm(const GemmDesc& d_in, hipStream_t s) {
                      VTGB_EINVAL, "conv gemm: column statistics need fp32 whole-row stores and images of >= 256 rows");
     VTGB_REQUIRE(!d.split_f16c8 || d.epi == EPI_SPLIT, VTGB_EINVAL, "conv gemm: split_f16c8 belongs to the pair store");
     switch (d.epi) {
-        case EPI_STORE: return conv ? launch_large_forced<EPI_STORE, true>(d, s) : launch_large_forced<EPI_STORE, false>(d, s);
-        case EPI_STORE_F32: return conv ? launch_large_forced<EPI_STORE_F32, true>(d, s) : launch_large_forced<EPI_STORE_F32, false>(d, s);
+        case EPI_STORE: return conv ? launch_large_by_width<EPI_STORE, true>(d, s) : launch_large_by_width<EPI_STORE, false>(d, s);
+        case EPI_STORE_F32: return conv ? launch_large_by_width<EPI_STORE_F32, true>(d, s) : launch_large_by_width<EPI_STORE_F32, false>(d, s);
         case EPI_GRU:
             VTGB_REQUIRE(conv && d.resid && d.aux && d.out2, VTGB_EINVAL, "conv gemm: GRU epilogue needs h, z and both outputs");
-            return launch_large_forced<EPI_GRU, true>(d, s);
+            return launch_large_by_width<EPI_GRU, true>(d, s);
         case EPI_SPLIT: return launch_split(d, s);
         case EPI_X3ZR:
             VTGB_REQUIRE(conv && pp_supported(d), VTGB_EUNSUPPORTED, "conv gemm: the bf16x3 z | r gate epilogue needs a 256-channel convolution with its start map, h and both outputs");

@@ -1,7 +1,7 @@
 // gemm_pp.hip -- the round-3 form of the large bf16 MFMA kernel (plain GEMM and implicit-GEMM convolution): PERSISTENT workgroups
 // with a PING-PONG k-loop.  Same tile (256 rows x 64 NWN columns x 64 deep), same LDS image (LDS-DMA staging, XOR-swizzled 128-byte
-// rows), same accumulator layout and the same epilogue arithmetic as gemm_bf16_large_kernel in gemm.hip (which stays for A/B runs and
-// for the timing ablations: VTGB_GEMM_OLD=1); what changed is the structure around them:
+// rows), same accumulator layout and the same epilogue arithmetic as gemm_bf16_large_kernel in gemm.hip (which stays for the
+// launches pp_supported turns away, the 64-wide tiles and the 256-wide GRU tile); what changed is the structure around them:
 //
 //  * Ping-pong k-loop.  The rounds-1/2 loop ran both waves of a SIMD in lockstep (one barrier per k-tile, two fragment sets): both
 //    issued LDS-DMA pieces, both waited on LDS reads, both multiplied at the same moments.  Here waves 4-7 run ONE BARRIER BEHIND
