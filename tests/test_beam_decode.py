@@ -124,7 +124,7 @@ def test_the_winning_beam_changes_parents():
 
 
 def test_what_the_decoders_refuse():
-    from videotgb_amd.decode import GreedyDecoder, T5GreedyDecoder, check_beam_search
+    from videotgb_amd.decode import GreedyDecoder, T5GreedyDecoder, check_mode
     x, m = _inputs(1)
     dec = _decoder()
     with pytest.raises(NotImplementedError):
@@ -142,9 +142,9 @@ def test_what_the_decoders_refuse():
     assert "num_beams" in inspect.signature(T5GreedyDecoder.generate).parameters
     src = inspect.getsource(T5GreedyDecoder.generate)
     assert "NotImplementedError" in src
-    assert check_beam_search("hf") == "hf" and check_beam_search("graph") == "graph"
+    assert check_mode("beam_search", "hf") == "hf" and check_mode("beam_search", "graph") == "graph"
     with pytest.raises(ValueError):
-        check_beam_search("on")
+        check_mode("beam_search", "on")
 
 
 def test_the_option_is_accepted_everywhere_and_defaults_to_hf():

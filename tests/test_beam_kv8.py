@@ -177,12 +177,12 @@ def test_defaults_are_unchanged():
 
 def test_check_beam_search():
     from videotgb_amd import decode
-    assert decode.BEAM_SEARCH == ("hf", "graph", "graph+t5", "graph+kv8", "graph+t5+kv8")
-    for good in decode.BEAM_SEARCH:
-        assert decode.check_beam_search(good) == good
+    assert decode.MODES["beam_search"] == ("hf", "graph", "graph+t5", "graph+kv8", "graph+t5+kv8")
+    for good in decode.MODES["beam_search"]:
+        assert decode.check_mode("beam_search", good) == good
     for bad in ("on", "t5", "graph+T5", "kv8", True, None):
         with pytest.raises(ValueError):
-            decode.check_beam_search(bad)
+            decode.check_mode("beam_search", bad)
 
 
 def test_envelope_for():

@@ -108,11 +108,11 @@ def test_envelope_for_reads_the_owner():
 
 
 def test_check_eos_sets():
-    from videotgb_amd.decode import check_eos_sets
-    assert [check_eos_sets(v) for v in ("hf", "graph")] == ["hf", "graph"]
+    from videotgb_amd.decode import check_mode
+    assert [check_mode("eos_sets", v) for v in ("hf", "graph")] == ["hf", "graph"]
     for bad in ("on", "Graph", "graph+t5", True, False, None, 1):
         with pytest.raises(ValueError):
-            check_eos_sets(bad)
+            check_mode("eos_sets", bad)
 
 
 def test_decoder_for_builds_the_decoder_with_the_flag(monkeypatch):
@@ -180,4 +180,4 @@ def test_the_constructors_accept_and_store_the_parameter():
     with pytest.raises(ValueError, match="eos_sets"):
         builder_utils.load_pretrained_model("ckpt", "instructblip", "sampler", "cpu", load_processors=False, eos_sets="on")
     src = inspect.getsource(modules._LSTPLightningBase.__init__)
-    assert "self.eos_sets = check_eos_sets(eos_sets)" in src and "self.eos_sets = check_eos_sets(eos_sets)" in inspect.getsource(models._LSTPBase.__init__)
+    assert 'self.eos_sets = check_mode("eos_sets", eos_sets)' in src and 'self.eos_sets = check_mode("eos_sets", eos_sets)' in inspect.getsource(models._LSTPBase.__init__)

@@ -77,11 +77,11 @@ def _llama(seed=3, dtype=torch.float32, **kw):
 
 def test_check_kv_cache():
     from videotgb_amd import decode
-    assert decode.KV_CACHE == ("bf16", "fp8")
-    assert decode.check_kv_cache("bf16") == "bf16" and decode.check_kv_cache("fp8") == "fp8"
+    assert decode.MODES["kv_cache"] == ("bf16", "fp8")
+    assert decode.check_mode("kv_cache", "bf16") == "bf16" and decode.check_mode("kv_cache", "fp8") == "fp8"
     for bad in ("int8", "FP8", "e4m3", None, 8):
         with pytest.raises(ValueError):
-            decode.check_kv_cache(bad)
+            decode.check_mode("kv_cache", bad)
         with pytest.raises(ValueError):
             decode.GreedyDecoder(_llama(), fused=False, kv_cache=bad)
         with pytest.raises(ValueError):

@@ -236,7 +236,7 @@ def test_modes_that_are_accepted_and_modes_that_raise():
     from videotgb_amd import decode, models, synth
     from videotgb_amd.decode import GreedyDecoder, T5GreedyDecoder, make_decoder
     from transformers import T5Config, T5ForConditionalGeneration
-    assert decode.DECODE_WEIGHTS == ("bf16", "fp8", "mxfp4") and decode.check_decode_weights("mxfp4") == "mxfp4"
+    assert decode.MODES["decode_weights"] == ("bf16", "fp8", "mxfp4") and decode.check_mode("decode_weights", "mxfp4") == "mxfp4"
     lm = _llama(9, torch.bfloat16)
     for bad in ("fp4", "MXFP4", "mxfp8", "nvfp4"):
         with pytest.raises(ValueError):

@@ -120,11 +120,11 @@ def test_envelope_for_reads_the_owner():
 
 
 def test_check_penalty_decode():
-    from videotgb_amd.decode import check_penalty_decode
-    assert [check_penalty_decode(v) for v in ("hf", "graph")] == ["hf", "graph"]
+    from videotgb_amd.decode import check_mode
+    assert [check_mode("penalty_decode", v) for v in ("hf", "graph")] == ["hf", "graph"]
     for bad in ("on", "Graph", "graph+t5", "", True, False, None, 1, 1.5, ("graph",)):
         with pytest.raises(ValueError, match="penalty_decode"):
-            check_penalty_decode(bad)
+            check_mode("penalty_decode", bad)
 
 
 def test_decoder_for_builds_the_decoder_with_the_flag(monkeypatch):
@@ -203,4 +203,4 @@ def test_the_constructors_accept_and_store_the_parameter():
     with pytest.raises(ValueError, match="penalty_decode"):
         builder_utils.load_pretrained_model("ckpt", "instructblip", "sampler", "cpu", load_processors=False, penalty_decode="on")
     for cls in (models._LSTPBase, modules._LSTPLightningBase):
-        assert "self.penalty_decode = check_penalty_decode(penalty_decode)" in inspect.getsource(cls.__init__)
+        assert 'self.penalty_decode = check_mode("penalty_decode", penalty_decode)' in inspect.getsource(cls.__init__)

@@ -20,12 +20,12 @@ def _owner(**kw):
 
 
 def test_check_sampled_decode():
-    from videotgb_amd.decode import SAMPLED_DECODE, check_sampled_decode
-    assert SAMPLED_DECODE == ("hf", "graph")
-    assert check_sampled_decode("hf") == "hf" and check_sampled_decode("graph") == "graph"
+    from videotgb_amd.decode import MODES, check_mode
+    assert MODES["sampled_decode"] == ("hf", "graph")
+    assert check_mode("sampled_decode", "hf") == "hf" and check_mode("sampled_decode", "graph") == "graph"
     for bad in ("torch", "", None, True, 1, ["graph"]):
         with pytest.raises(ValueError):
-            check_sampled_decode(bad)
+            check_mode("sampled_decode", bad)
 
 
 def test_without_the_opt_in_the_envelopes_are_the_same_objects():
@@ -153,6 +153,6 @@ def test_the_module_twins_take_check_and_store_the_parameter():
             with pytest.raises(ValueError, match="sampled_decode"):      # (checked before any path is read)
                 c(model_name_or_path="nowhere", sampler_name_or_path="nowhere", of_extractor_name_or_path="nowhere", sampled_decode=bad)
     # the attribute the constructor stores is the one the planner reads from its owner
-    assert "self.sampled_decode = check_sampled_decode(sampled_decode)" in inspect.getsource(modules._LSTPLightningBase.__init__)
-    owner = types.SimpleNamespace(sampled_decode=D.check_sampled_decode("graph"))
+    assert 'self.sampled_decode = check_mode("sampled_decode", sampled_decode)' in inspect.getsource(modules._LSTPLightningBase.__init__)
+    owner = types.SimpleNamespace(sampled_decode=D.check_mode("sampled_decode", "graph"))
     assert D.envelope_for(owner, True).sampling and not D.envelope_for(types.SimpleNamespace(sampled_decode="hf"), True).sampling

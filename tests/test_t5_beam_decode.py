@@ -170,7 +170,7 @@ def test_the_winning_beam_changes_parents():
 
 def test_what_the_decoder_refuses():
     from videotgb_amd import ops
-    from videotgb_amd.decode import T5GreedyDecoder, check_beam_search
+    from videotgb_amd.decode import T5GreedyDecoder, check_mode
     x, _ = _inputs(1)
     dec = _decoder()
     for kw in (dict(do_sample=True), dict(stop_ids=[[5, 6]]), dict(text_stop=lambda ids: False)):
@@ -189,10 +189,10 @@ def test_what_the_decoder_refuses():
     with pytest.raises(NotImplementedError):      # 2 K > V
         T5GreedyDecoder(small, fused=False).generate(torch.zeros(1, 3, 16), 4, num_beams=5)
     assert "NotImplementedError" in inspect.getsource(T5GreedyDecoder.generate)
-    assert [check_beam_search(v) for v in ("hf", "graph", "graph+t5")] == ["hf", "graph", "graph+t5"]
+    assert [check_mode("beam_search", v) for v in ("hf", "graph", "graph+t5")] == ["hf", "graph", "graph+t5"]
     for bad in ("on", "t5", "graph+T5", True, None):
         with pytest.raises(ValueError):
-            check_beam_search(bad)
+            check_mode("beam_search", bad)
     assert ops.ATTENTION_ROWS_BEAM_MAX_KEYS == 1920
 
 

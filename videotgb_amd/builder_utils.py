@@ -24,12 +24,10 @@ def load_pretrained_model(ckpt_path, base_model_path, base_sampler_path, device,
     quantised model's, not the reference's; answer quality on a trained checkpoint is not measured by this project), ``kv_cache="fp8"``: its opt-in fp8 K/V cache, ``beam_search="graph"``: its opt-in
     beam search, ``"graph+t5"``: that and the T5 graph decoder's, ``eos_sets="graph"``: requests with several distinct eos ids stay on the graph
     decoders, ``penalty_decode="graph"``: one-beam requests with a repetition penalty stay on the graph decoders, models.LSTP)."""
-    from .decode import check_beam_search, check_decode_weights, check_eos_sets, check_kv_cache, check_penalty_decode
-    check_penalty_decode(penalty_decode)
-    check_eos_sets(eos_sets)
-    check_decode_weights(decode_weights)
-    check_kv_cache(kv_cache)
-    check_beam_search(beam_search)
+    from .decode import check_mode
+    for name, value in (("penalty_decode", penalty_decode), ("eos_sets", eos_sets), ("decode_weights", decode_weights), ("kv_cache", kv_cache),
+                        ("beam_search", beam_search)):
+        check_mode(name, value)
     print("start to load model...")
     processor = sampler_processor = None
     if load_processors:

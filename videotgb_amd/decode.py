@@ -20,22 +20,21 @@ the returned ids end at the step where the last row finished.  ``min_new_tokens`
 for the first steps like MinNewTokensLengthLogitsProcessor.  ``eos_token_id=None`` = fixed-length
 decode (the bench's "no EOS stopping, fixed work per clip" mode).
 Greedy ids are checked token-for-token against HF generate at fp32 (tests/test_decode.py, test_gpu_e2e.py).
-Opt-in (an owner's ``beam_search="graph"``): HF's deterministic beam search on the Llama decoder -- ``GreedyDecoder.generate(num_beams=...,
-repetition_penalty=..., length_penalty=...)``; by default such requests go to HF generate as before (tests/test_beam_decode.py,
-test_gpu_beam_decode.py).  ``beam_search="graph+kv8"`` / ``"graph+t5+kv8"``: the same, and the beams of a ``kv_cache="fp8"`` Llama run over
-the fp8 cache (``GreedyDecoder(fp8_beams=True)``; tests/test_beam_kv8.py, test_gpu_beam_kv8.py).
-Opt-in (an owner's ``penalty_decode="graph"``): ``repetition_penalty`` != 1 on ONE beam, on both decoders (``_penalise``,
-vtgb_llm_repetition_penalty; tests/test_penalty_decode.py, test_gpu_penalty_decode.py); by default such requests go to HF generate as before.
+Opt-in, by six string attributes of a decoder's owner (``MODES`` lists them, their values and what each means; ``DecodeModes`` is their parsed
+form): fp8 / MXFP4 weight streams and an fp8 K/V cache on the Llama decoder, HF's deterministic beam search on either decoder (over the fp8 cache
+as well), eos-id sets, the twins' sampled ``generate_configs``, a repetition penalty on one beam.  By default every such request goes to HF
+generate as before and the decoders are built as before (tests/test_decode_modes.py holds all 240 combinations to that).
 
 Structure: ``_GraphDecoder`` owns everything that is not the model -- the state cache (LRU, MAX_STATES), the emission state (token / position
 feedback, finished flags, lengths, sampling and stopping data), token selection, capture, the replay loop and the truncation of the returned ids;
 ``GreedyDecoder`` (Llama) and ``T5GreedyDecoder`` add weights, prefill / encoder, one decode step and their buffers.  ``plan_decode`` is the one
 place that decides "graph decoder or HF generate" (each caller's envelope is an ``Envelope`` value), ``decoder_for`` the one place a decoder is
-cached on its owner.
+cached on its owner, ``modes_of`` the one place an owner's mode attributes are read.
 """
 from __future__ import annotations
 
 import ctypes
+import functools
 from typing import Callable, Dict, NamedTuple, Optional, Tuple
 
 import torch
@@ -62,73 +61,60 @@ def _rot_half(x: Tensor) -> Tensor:
     return torch.cat((-x[..., h:], x[..., :h]), dim=-1)
 
 
-DECODE_WEIGHTS = ("bf16", "fp8", "mxfp4")
+# An owner's opt-in switches (attributes of a models.LSTP, a LightningModule twin or any object handed to ``decoder_for`` / ``envelope_for``),
+# each with the values it accepts, the default first.  ``modes_of`` reads and parses them; nothing else does.
+#   decode_weights  the weights the Llama decoder streams: "bf16" (the model's own), "fp8" (per-row e4m3 codes) or "mxfp4" (e2m1 codes under an
+#                   E8M0 scale per 32 weights)
+#   kv_cache        the Llama decoder's K/V cache: "bf16" (the model's own K/V) or "fp8" (per-row e4m3 codes)
+#   beam_search     who runs a beam-search request: "hf" (HF generate), "graph" (the Llama graph decoder; a T5's beam requests stay on HF),
+#                   "graph+t5" (that, and the T5 graph decoder) or either with "+kv8" (that, and the beams of a ``kv_cache="fp8"`` Llama run over
+#                   the fp8 cache -- ``GreedyDecoder(fp8_beams=True)`` -- instead of being refused)
+#   eos_sets        who runs a request with several distinct eos ids: "hf" or "graph" (the graph decoders, up to ``ops.EOS_MAX`` ids --
+#                   ``GreedyDecoder(eos_sets=True)`` / ``T5GreedyDecoder(eos_sets=True)``)
+#   sampled_decode  who runs a LightningModule twin's sampled ``generate_configs``: "hf" or "graph" (the module envelope serves ``do_sample`` with
+#                   temperature / top_p and takes the length as HF's ``max_length`` / ``min_length`` -- the literal dictionaries of the reference's
+#                   LSTP_blip2.yaml / LSTP_instructblip.yaml family -- so that on a Llama they stay on the graph decoder's sampling path; a T5's
+#                   sampled requests stay on HF generate)
+#   penalty_decode  who runs a ONE-beam request with ``repetition_penalty != 1``: "hf" or "graph" (the graph decoders -- ``GreedyDecoder(penalty=
+#                   True)`` / ``T5GreedyDecoder(penalty=True)`` -- apply HF's RepetitionPenaltyLogitsProcessor inside the captured step: greedy on
+#                   both, sampling on a Llama).  Beams keep their own penalty (``beam_search``)
+MODES = {"decode_weights": ("bf16", "fp8", "mxfp4"),
+         "kv_cache": ("bf16", "fp8"),
+         "beam_search": ("hf", "graph", "graph+t5", "graph+kv8", "graph+t5+kv8"),
+         "eos_sets": ("hf", "graph"),
+         "sampled_decode": ("hf", "graph"),
+         "penalty_decode": ("hf", "graph")}
 
 
-def check_decode_weights(weights) -> str:
-    """The decode-weight mode as the decoders take it: "bf16" (the model's own weights), "fp8" (Llama: per-row e4m3 weight stream) or "mxfp4" (Llama:
-    e2m1 codes under an E8M0 scale per 32 weights); ValueError otherwise."""
-    if weights not in DECODE_WEIGHTS:
-        raise ValueError(f"decode_weights must be one of {DECODE_WEIGHTS}, got {weights!r}")
-    return weights
+def check_mode(name: str, value) -> str:
+    """``value`` when it is one of ``MODES[name]``; ValueError otherwise (anything that is no string included)."""
+    if value not in MODES[name]:
+        raise ValueError(f"{name} must be one of {MODES[name]}, got {value!r}")
+    return value
 
 
-KV_CACHE = ("bf16", "fp8")
+class DecodeModes(NamedTuple):
+    """An owner's six ``MODES`` strings, parsed.  The first five fields are ``GreedyDecoder``'s constructor keywords (``DECODER_MODES``;
+    ``T5GreedyDecoder`` takes all but ``fp8_beams``), the last three with ``eos_sets`` and ``penalty`` shape the owner's ``Envelope``."""
+    weights: str = "bf16"        # decode_weights
+    kv_cache: str = "bf16"
+    fp8_beams: bool = False      # beam_search has "+kv8"
+    eos_sets: bool = False       # eos_sets is "graph"
+    penalty: bool = False        # penalty_decode is "graph"
+    beams: bool = False          # beam_search starts with "graph"
+    t5_beams: bool = False       # beam_search has "+t5"
+    sampled: bool = False        # sampled_decode is "graph"
 
 
-def check_kv_cache(kv_cache) -> str:
-    """The K/V cache mode as the decoders take it: "bf16" (the model's own K/V) or "fp8" (Llama: per-row e4m3 K/V cache); ValueError otherwise."""
-    if kv_cache not in KV_CACHE:
-        raise ValueError(f"kv_cache must be one of {KV_CACHE}, got {kv_cache!r}")
-    return kv_cache
+DECODER_MODES = DecodeModes._fields[:5]
 
 
-BEAM_SEARCH = ("hf", "graph", "graph+t5", "graph+kv8", "graph+t5+kv8")
-
-
-def check_beam_search(beam_search) -> str:
-    """Who runs a beam-search request: "hf" (HF generate, the default), "graph" (opt-in: the Llama graph decoder; a T5's beam requests stay
-    on HF), "graph+t5" (opt-in: that, and the T5 graph decoder) or either with "+kv8" (opt-in: that, and the beams of a ``kv_cache="fp8"`` Llama
-    run over the fp8 cache -- ``GreedyDecoder(fp8_beams=True)`` -- instead of being refused); ValueError otherwise."""
-    if not isinstance(beam_search, str) or beam_search not in BEAM_SEARCH:
-        raise ValueError(f"beam_search must be one of {BEAM_SEARCH}, got {beam_search!r}")
-    return beam_search
-
-
-EOS_SETS = ("hf", "graph")
-
-
-def check_eos_sets(eos_sets) -> str:
-    """Who runs a request with several distinct eos ids: "hf" (HF generate, the default) or "graph" (opt-in: the graph decoders, up to
-    ``ops.EOS_MAX`` ids -- ``GreedyDecoder(eos_sets=True)`` / ``T5GreedyDecoder(eos_sets=True)``); ValueError otherwise."""
-    if not isinstance(eos_sets, str) or eos_sets not in EOS_SETS:
-        raise ValueError(f"eos_sets must be one of {EOS_SETS}, got {eos_sets!r}")
-    return eos_sets
-
-
-SAMPLED_DECODE = ("hf", "graph")
-
-
-def check_sampled_decode(sampled_decode) -> str:
-    """Who runs a LightningModule twin's sampled ``generate_configs``: "hf" (HF generate, the default) or "graph" (opt-in: the module envelope
-    serves ``do_sample`` with temperature / top_p and takes the length as HF's ``max_length`` / ``min_length`` -- the literal dictionaries of
-    the reference's LSTP_blip2.yaml / LSTP_instructblip.yaml family -- so that on a Llama they stay on the graph decoder's sampling path;
-    a T5's sampled requests stay on HF generate); ValueError otherwise."""
-    if not isinstance(sampled_decode, str) or sampled_decode not in SAMPLED_DECODE:
-        raise ValueError(f"sampled_decode must be one of {SAMPLED_DECODE}, got {sampled_decode!r}")
-    return sampled_decode
-
-
-PENALTY_DECODE = ("hf", "graph")
-
-
-def check_penalty_decode(penalty_decode) -> str:
-    """Who runs a ONE-beam request with ``repetition_penalty != 1``: "hf" (HF generate, the default) or "graph" (opt-in: the graph decoders --
-    ``GreedyDecoder(penalty=True)`` / ``T5GreedyDecoder(penalty=True)`` -- apply HF's RepetitionPenaltyLogitsProcessor inside the captured step:
-    greedy on both, sampling on a Llama); ValueError otherwise.  Beams keep their own penalty (``beam_search``)."""
-    if not isinstance(penalty_decode, str) or penalty_decode not in PENALTY_DECODE:
-        raise ValueError(f"penalty_decode must be one of {PENALTY_DECODE}, got {penalty_decode!r}")
-    return penalty_decode
+def modes_of(owner) -> DecodeModes:
+    """The modes of ``owner``, read from its attributes on every call (callers reassign them between calls); an attribute it lacks takes the
+    default, any other value than ``MODES`` lists is a ValueError."""
+    weights, kv_cache, beam_search, eos_sets, sampled, penalty = (check_mode(name, getattr(owner, name, values[0])) for name, values in MODES.items())
+    beam = beam_search.split("+")      # "graph+t5+kv8" -> who runs beams, on a T5 as well, over the fp8 cache as well
+    return DecodeModes(weights, kv_cache, "kv8" in beam, eos_sets == "graph", penalty == "graph", beam[0] == "graph", "t5" in beam, sampled == "graph")
 
 
 def _first_eos(eos):
@@ -303,8 +289,8 @@ class _GraphDecoder:
     PENALTY_KERNEL = True
 
     def __init__(self, lm, fused: bool, weights: str = "bf16", kv_cache: str = "bf16", eos_sets: bool = False, penalty: bool = False):
-        self.lm, self.cfg, self.fused, self.weights = lm, lm.config, fused, check_decode_weights(weights)
-        self.kv_cache = check_kv_cache(kv_cache)
+        self.lm, self.cfg, self.fused, self.weights = lm, lm.config, fused, check_mode("decode_weights", weights)
+        self.kv_cache = check_mode("kv_cache", kv_cache)
         self.eos_sets = bool(eos_sets)      # opt-in (eos_sets="graph"): requests with 2 .. ops.EOS_MAX distinct eos ids instead of a refusal
         self.penalty = bool(penalty)        # opt-in (penalty_decode="graph"): one beam with repetition_penalty != 1 instead of a refusal
         self.key = weights_key(lm)
@@ -1390,9 +1376,9 @@ class T5GreedyDecoder(_GraphDecoder):
         cfg = lm.config
         if getattr(cfg, "model_type", "") != "t5":
             raise NotImplementedError("T5GreedyDecoder handles T5ForConditionalGeneration")
-        if check_decode_weights(weights) != "bf16":
+        if check_mode("decode_weights", weights) != "bf16":
             raise NotImplementedError(f"decode_weights={weights!r} is implemented for the Llama decoder only")
-        if check_kv_cache(kv_cache) != "bf16":
+        if check_mode("kv_cache", kv_cache) != "bf16":
             raise NotImplementedError("kv_cache='fp8' is implemented for the Llama decoder only")
         has_lora = _lora_servable(lm)      # (adapters outside q / k / v of the attention blocks: NotImplementedError)
         super().__init__(lm, fused, weights, kv_cache, eos_sets, penalty)
@@ -1820,15 +1806,11 @@ def keyword_stop_plan(criteria) -> dict:
 
 
 def make_decoder(lm, weights: str = "bf16", kv_cache: str = "bf16", fp8_beams: bool = False, eos_sets: bool = False, penalty: bool = False):
-    """The graph decoder for a language model: Llama-architecture causal LMs and T5 seq2seq LMs; NotImplementedError otherwise.
-    ``weights``: "bf16", or "fp8" / "mxfp4" (Llama only: GreedyDecoder); ``kv_cache``: "bf16", or "fp8" (likewise); ``fp8_beams``: GreedyDecoder's
-    (a T5 decoder has no fp8 cache and does not take it); ``eos_sets``: both decoders' (requests with several distinct eos ids); ``penalty``:
-    both decoders' (one beam with a repetition penalty)."""
-    sets = dict(eos_sets=True) if eos_sets else {}
-    sets.update(dict(penalty=True) if penalty else {})
+    """The graph decoder for a language model: Llama-architecture causal LMs and T5 seq2seq LMs; NotImplementedError otherwise.  The keywords
+    are the decoders' own (``DECODER_MODES``); a T5 decoder has no fp8 cache and does not take ``fp8_beams``."""
     if getattr(lm.config, "model_type", "") == "t5":
-        return T5GreedyDecoder(lm, weights=weights, kv_cache=kv_cache, **sets)
-    return GreedyDecoder(lm, weights=weights, kv_cache=kv_cache, **(dict(fp8_beams=True) if fp8_beams else {}), **sets)
+        return T5GreedyDecoder(lm, weights=weights, kv_cache=kv_cache, eos_sets=eos_sets, penalty=penalty)
+    return GreedyDecoder(lm, weights=weights, kv_cache=kv_cache, fp8_beams=fp8_beams, eos_sets=eos_sets, penalty=penalty)
 
 
 def prompt_padding(attention_mask: Tensor) -> Tuple[Optional[bool], Tensor]:
@@ -1843,24 +1825,14 @@ def prompt_padding(attention_mask: Tensor) -> Tuple[Optional[bool], Tensor]:
 
 def decoder_for(owner, lm):
     """The graph decoder for ``lm``, cached on ``owner`` (attribute ``_decoder``): the cached one when it was built for this ``lm`` and the
-    weights it re-packed are still the model's (``weights_key``) and in the owner's modes (attributes ``decode_weights`` and ``kv_cache``,
-    "bf16" when it has none; ``fp8_beams`` = "kv8" in its ``beam_search``; ``eos_sets`` = its ``eos_sets`` is "graph"; ``penalty`` = its
-    ``penalty_decode`` is "graph"), else a new one (``make_decoder``)."""
-    mode = check_decode_weights(getattr(owner, "decode_weights", "bf16"))
-    kv = check_kv_cache(getattr(owner, "kv_cache", "bf16"))
-    kv8 = "kv8" in check_beam_search(getattr(owner, "beam_search", "hf"))
-    sets = check_eos_sets(getattr(owner, "eos_sets", "hf")) == "graph"
-    pen = check_penalty_decode(getattr(owner, "penalty_decode", "hf")) == "graph"
+    weights it re-packed are still the model's (``weights_key``) and its ``DECODER_MODES`` attributes are those of the owner's modes (``modes_of``,
+    read on every call), else a new one: ``make_decoder`` with the modes that are not the default -- by default the positional ``lm`` alone."""
+    want, default = modes_of(owner)._asdict(), DecodeModes._field_defaults
     dec = getattr(owner, "_decoder", None)
-    if (dec is None or dec.lm is not lm or dec.key != weights_key(lm) or getattr(dec, "weights", "bf16") != mode
-            or getattr(dec, "kv_cache", "bf16") != kv or getattr(dec, "fp8_beams", kv8) != kv8      # (a T5 decoder has no such flag)
-            or getattr(dec, "eos_sets", False) != sets or getattr(dec, "penalty", False) != pen):
-        kw = ({} if mode == "bf16" else dict(weights=mode))
-        kw.update({} if kv == "bf16" else dict(kv_cache=kv))
-        kw.update(dict(fp8_beams=True) if kv8 else {})
-        kw.update(dict(eos_sets=True) if sets else {})
-        kw.update(dict(penalty=True) if pen else {})
-        dec = owner._decoder = make_decoder(lm, **kw)      # (the default modes: the positional lm alone)
+    # (an attribute a decoder lacks counts as the default; a T5 decoder has no ``fp8_beams`` and is not retired for it)
+    if dec is None or dec.lm is not lm or dec.key != weights_key(lm) or any(
+            getattr(dec, f, want[f] if f == "fp8_beams" else default[f]) != want[f] for f in DECODER_MODES):
+        dec = owner._decoder = make_decoder(lm, **{f: want[f] for f in DECODER_MODES if want[f] != default[f]})
     return dec
 
 
@@ -1884,44 +1856,44 @@ class Envelope(NamedTuple):
 
 
 _COMMON_KEYS = {"do_sample", "temperature", "top_p", "min_new_tokens", "eos_token_id", "pad_token_id", "num_beams", "repetition_penalty", "length_penalty"}
-# LSTP.generate(**gen_kwargs): sampling and KeywordsStoppingCriteria on Llama (max_new_tokens / use_cache are its own parameters, handed to the decoder
-# by the caller)
-GENERATE_ENVELOPE = Envelope(frozenset(_COMMON_KEYS | {"top_k", "sample_noise", "generator", "stopping_criteria"}),
-                             {"num_beams": (1,), "repetition_penalty": (None, 1.0), "length_penalty": (None, 1.0)}, sampling=True, need_max_new=False)
-# the LightningModule twins' ``generate_configs``: greedy only (length_penalty has no effect on one beam)
-MODULE_ENVELOPE = Envelope(frozenset(_COMMON_KEYS | {"max_new_tokens", "use_cache"}), {"num_beams": (1,), "repetition_penalty": (1.0,)},
-                           sampling=False, need_max_new=True)
+_LENGTH_KEYS = {"max_length", "min_length"}      # HF's way to give the length (``generated_length``), as the shipped generate_configs do
+_BASE_ENVELOPES = {
+    # LSTP.generate(**gen_kwargs): sampling and KeywordsStoppingCriteria on Llama (max_new_tokens / use_cache are its own parameters, handed to the
+    # decoder by the caller)
+    False: Envelope(frozenset(_COMMON_KEYS | {"top_k", "sample_noise", "generator", "stopping_criteria"}),
+                    {"num_beams": (1,), "repetition_penalty": (None, 1.0), "length_penalty": (None, 1.0)}, sampling=True, need_max_new=False),
+    # the LightningModule twins' ``generate_configs``: greedy only (length_penalty has no effect on one beam)
+    True: Envelope(frozenset(_COMMON_KEYS | {"max_new_tokens", "use_cache"}), {"num_beams": (1,), "repetition_penalty": (1.0,)},
+                   sampling=False, need_max_new=True)}
 
 
-# the owner's opt-in (beam_search="graph"): the same, and deterministic beam search on Llama; the modules' configurations may then give the
-# length as HF's ``max_length`` / ``min_length`` (``generated_length``), as the shipped generate_configs do
-GENERATE_ENVELOPE_BEAMS = GENERATE_ENVELOPE._replace(beams=True)
-MODULE_ENVELOPE_BEAMS = MODULE_ENVELOPE._replace(keys=MODULE_ENVELOPE.keys | {"max_length", "min_length"}, beams=True)
-# beam_search="graph+t5": their twins that let a T5's beam requests through as well
-GENERATE_ENVELOPE_T5_BEAMS = GENERATE_ENVELOPE_BEAMS._replace(t5_beams=True)
-MODULE_ENVELOPE_T5_BEAMS = MODULE_ENVELOPE_BEAMS._replace(t5_beams=True)
+@functools.lru_cache(maxsize=None)      # (one object per envelope: callers and tests compare them with ``is``)
+def _envelope(module: bool, beams: bool, t5_beams: bool, eos_sets: bool, sampled: bool, penalty: bool) -> Envelope:
+    """The envelope of LSTP.generate (``module`` False) or of the LightningModule twins under the envelope half of a ``DecodeModes``."""
+    env = _BASE_ENVELOPES[module]
+    if beams:      # deterministic beam search on Llama; the modules' configurations may then give the length as ``max_length`` / ``min_length``
+        env = env._replace(keys=env.keys | _LENGTH_KEYS if module else env.keys, beams=True)
+    if t5_beams:      # a T5's beam requests as well
+        env = env._replace(t5_beams=True)
+    if eos_sets:
+        env = env._replace(eos_sets=True)
+    if module and sampled:      # the modules' configurations may sample and give the length that way (LSTP.generate's envelope samples already)
+        env = env._replace(sampling=True, keys=env.keys | _LENGTH_KEYS)
+    if penalty:
+        env = env._replace(penalty=True)
+    return env
+
+
+GENERATE_ENVELOPE, MODULE_ENVELOPE = (_envelope(m, False, False, False, False, False) for m in (False, True))
+GENERATE_ENVELOPE_BEAMS, MODULE_ENVELOPE_BEAMS = (_envelope(m, True, False, False, False, False) for m in (False, True))               # beam_search="graph"
+GENERATE_ENVELOPE_T5_BEAMS, MODULE_ENVELOPE_T5_BEAMS = (_envelope(m, True, True, False, False, False) for m in (False, True))          # "graph+t5"
 
 
 def envelope_for(owner, module: bool) -> Envelope:
-    """The envelope a caller plans with: today's, or its beam twin when the owner opted in (attribute ``beam_search``, "hf" when it has none;
-    "graph+t5": the twin with ``t5_beams``; "+kv8" changes the decoder, not the envelope); an owner whose ``eos_sets`` is "graph" gets that
-    envelope's ``_replace(eos_sets=True)`` twin, one whose ``sampled_decode`` is "graph" the module envelope's twin with ``sampling`` and the
-    keys ``max_length`` / ``min_length``, one whose ``penalty_decode`` is "graph" the ``_replace(penalty=True)`` twin."""
-    mode = check_beam_search(getattr(owner, "beam_search", "hf")).replace("+kv8", "")
-    if mode == "graph+t5":
-        env = MODULE_ENVELOPE_T5_BEAMS if module else GENERATE_ENVELOPE_T5_BEAMS
-    elif module:
-        env = MODULE_ENVELOPE_BEAMS if mode == "graph" else MODULE_ENVELOPE
-    else:
-        env = GENERATE_ENVELOPE_BEAMS if mode == "graph" else GENERATE_ENVELOPE
-    if check_eos_sets(getattr(owner, "eos_sets", "hf")) == "graph":      # (else: the very objects above)
-        env = env._replace(eos_sets=True)
-    if module and check_sampled_decode(getattr(owner, "sampled_decode", "hf")) == "graph":
-        # the modules' configurations may sample and give the length as ``max_length`` / ``min_length`` (LSTP.generate's envelope samples already)
-        env = env._replace(sampling=True, keys=env.keys | {"max_length", "min_length"})
-    if check_penalty_decode(getattr(owner, "penalty_decode", "hf")) == "graph":
-        env = env._replace(penalty=True)
-    return env
+    """The envelope a caller plans with: ``_envelope`` of the owner's modes (``modes_of``, read on every call).  With no opt-in but
+    ``beam_search`` it is one of the six objects above; ``sampled_decode`` changes the module envelope alone, "+kv8" the decoder alone."""
+    m, module = modes_of(owner), bool(module)
+    return _envelope(module, m.beams, m.t5_beams, m.eos_sets, module and m.sampled, m.penalty)
 
 
 def generated_length(lm, request: dict, P: int) -> Optional[Tuple[int, Optional[int]]]:
@@ -1948,6 +1920,8 @@ def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: E
     attention mask with a token in every row (a padded mask goes into the plan as its host copy); greedy, or -- Llama, where ``env`` serves it --
     sampling with temperature / top_k / top_p; ``stopping_criteria`` None or (Llama) KeywordsStoppingCriteria objects (eval/utils/builder_utils.py:
     320-346: recognised by their ``keyword_ids`` / ``keywords`` / ``tokenizer`` attributes)."""
+    def number(v, types=(int, float)):      # (a bool is an int to Python and no number to HF generate)
+        return isinstance(v, types) and not isinstance(v, bool)
     mt = getattr(lm.config, "model_type", "")
     if not inputs_embeds.is_cuda or not ("llama" in mt or mt == "t5"):
         return None
@@ -1960,11 +1934,11 @@ def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: E
     do_sample = bool(request.get("do_sample", False))
     crit = list(request["stopping_criteria"]) if request.get("stopping_criteria") is not None else []
     K = request.get("num_beams", 1)
-    beams = env.beams and isinstance(K, int) and not isinstance(K, bool) and K > 1
+    beams = env.beams and number(K, int) and K > 1
     if beams:      # deterministic beam search on Llama (on T5: under ``env.t5_beams``); any positive repetition penalty, any length penalty
         rp, lp = request.get("repetition_penalty"), request.get("length_penalty")
         rp, lp = (1.0 if rp is None else rp), (1.0 if lp is None else lp)
-        if not ("llama" in mt or (mt == "t5" and env.t5_beams)) or do_sample or crit or not all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in (rp, lp)) or not rp > 0:
+        if not ("llama" in mt or (mt == "t5" and env.t5_beams)) or do_sample or crit or not (number(rp) and number(lp)) or not rp > 0:
             return None
     elif any(k in request and request[k] not in ok for k, ok in env.neutral.items() if not (env.penalty and k == "repetition_penalty")):
         return None
@@ -1972,7 +1946,7 @@ def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: E
     if env.penalty and not beams:
         one_pen = request.get("repetition_penalty")
         one_pen = 1.0 if one_pen is None else one_pen
-        if not isinstance(one_pen, (int, float)) or isinstance(one_pen, bool) or not 0 < one_pen < float("inf"):
+        if not number(one_pen) or not 0 < one_pen < float("inf"):
             return None
     if (do_sample and not env.sampling) or any(not all(hasattr(c, a) for a in ("keyword_ids", "keywords", "tokenizer")) for c in crit):
         return None
@@ -1986,7 +1960,7 @@ def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: E
     if isinstance(eos, (list, tuple)) and len(set(eos)) > 1:      # several distinct eos ids (Llama-3.1-Instruct ships three): HF generate,
         # or -- under ``env.eos_sets`` -- the decoders' eos sets: up to ops.EOS_MAX ids, each a token of the vocabulary
         V = getattr(lm.config, "vocab_size", 0)
-        if not env.eos_sets or len(set(eos)) > ops.EOS_MAX or any(not isinstance(e, int) or isinstance(e, bool) or not 0 <= e < V for e in eos):
+        if not env.eos_sets or len(set(eos)) > ops.EOS_MAX or any(not number(e, int) or not 0 <= e < V for e in eos):
             return None
         eos = list(eos)
     elif isinstance(eos, (list, tuple)) and len(eos) > 1:      # (one id, repeated)
@@ -2011,8 +1985,8 @@ def plan_decode(lm, inputs_embeds, attention_mask: Tensor, request: dict, env: E
 
 def graph_generate(owner, lm, inputs_embeds: Tensor, attention_mask: Tensor, generate_configs: dict):
     """``lm.generate(inputs_embeds=..., attention_mask=..., **generate_configs)`` through the graph decoder when the configuration is inside
-    the owner's module envelope (``envelope_for``: MODULE_ENVELOPE, or MODULE_ENVELOPE_BEAMS / MODULE_ENVELOPE_T5_BEAMS when its ``beam_search`` is "graph" / "graph+t5"), else None (the
-    caller then runs HF generate).  The decoder is cached on ``owner``."""
+    the owner's module envelope (``envelope_for``: MODULE_ENVELOPE, or what the owner's ``MODES`` make of it), else None (the caller then runs
+    HF generate).  The decoder is cached on ``owner`` (``decoder_for``)."""
     gc = dict(generate_configs or {})
     env = envelope_for(owner, module=True)
     plan = plan_decode(lm, inputs_embeds, attention_mask, gc, env)

@@ -472,14 +472,14 @@ class _LSTPBase(nn.Module):
         "graph" = opt-in: the graph decoders serve up to ops.EOS_MAX ids, greedy, sampled and with beams, whatever the other modes),
         ``penalty_decode`` ("hf": a ONE-beam request with ``repetition_penalty`` != 1 -- the reference's demo sends 1.5 with every call -- runs on
         HF generate, as before; "graph" = opt-in: the graph decoders apply HF's RepetitionPenaltyLogitsProcessor inside the captured step, greedy
-        on Llama and T5, sampled on Llama, whatever the other modes; see decode.check_penalty_decode)."""
+        on Llama and T5, sampled on Llama, whatever the other modes; see decode.MODES)."""
         super().__init__()
-        from .decode import check_beam_search, check_decode_weights, check_eos_sets, check_kv_cache, check_penalty_decode
-        self.penalty_decode = check_penalty_decode(penalty_decode)      # (decode.envelope_for and decode.decoder_for read it from their owner)
-        self.decode_weights = check_decode_weights(decode_weights)      # (decode.decoder_for reads it from its owner)
-        self.kv_cache = check_kv_cache(kv_cache)                        # (likewise)
-        self.beam_search = check_beam_search(beam_search)               # (decode.envelope_for reads it from its owner)
-        self.eos_sets = check_eos_sets(eos_sets)                        # (decode.envelope_for and decode.decoder_for read it from their owner)
+        from .decode import check_mode      # (decode.modes_of reads these attributes from a decoder's owner, on every call)
+        self.penalty_decode = check_mode("penalty_decode", penalty_decode)
+        self.decode_weights = check_mode("decode_weights", decode_weights)
+        self.kv_cache = check_mode("kv_cache", kv_cache)
+        self.beam_search = check_mode("beam_search", beam_search)
+        self.eos_sets = check_mode("eos_sets", eos_sets)
         hf_config = None
         if isinstance(base_model_path, synth.PathCfg):
             cfg = base_model_path

@@ -180,16 +180,16 @@ class _LSTPLightningBase(_Base):
                  penalty_decode: str = "hf"):
         super().__init__()
         self.save_hyperparameters(logger=False)
-        from .decode import check_beam_search, check_decode_weights, check_eos_sets, check_kv_cache, check_penalty_decode, check_sampled_decode
-        self.decode_weights = check_decode_weights(decode_weights)      # "fp8": models.LSTP's opt-in decode mode (decode.decoder_for reads it)
-        self.kv_cache = check_kv_cache(kv_cache)                        # "fp8": models.LSTP's opt-in K/V cache mode (likewise)
-        self.beam_search = check_beam_search(beam_search)               # "graph" / "graph+t5" (/ "+kv8"): models.LSTP's opt-in beam search (decode.graph_generate reads it)
-        self.eos_sets = check_eos_sets(eos_sets)                        # "graph": models.LSTP's opt-in eos-id sets (decode.graph_generate reads it)
-        # "graph": the shipped sampled generate_configs -- do_sample, top_p, temperature, max_length / min_length -- stay on the Llama graph
-        # decoder (decode.envelope_for reads it; a T5's sampled requests stay on HF generate)
-        self.sampled_decode = check_sampled_decode(sampled_decode)
-        # "graph": generate_configs with one beam and a repetition penalty stay on the graph decoders (decode.graph_generate reads it)
-        self.penalty_decode = check_penalty_decode(penalty_decode)
+        # models.LSTP's opt-in decode modes ("fp8" / "mxfp4" weights, an "fp8" K/V cache, beam search "graph" / "graph+t5" (/ "+kv8"), eos-id sets
+        # and a one-beam repetition penalty on the graph decoders) and, for the twins' ``generate_configs`` alone, ``sampled_decode``: decode.MODES
+        # says what each value means; decode.modes_of reads these attributes from a decoder's owner, on every call
+        from .decode import check_mode
+        self.decode_weights = check_mode("decode_weights", decode_weights)
+        self.kv_cache = check_mode("kv_cache", kv_cache)
+        self.beam_search = check_mode("beam_search", beam_search)
+        self.eos_sets = check_mode("eos_sets", eos_sets)
+        self.sampled_decode = check_mode("sampled_decode", sampled_decode)
+        self.penalty_decode = check_mode("penalty_decode", penalty_decode)
         if not hasattr(self.hparams, "optimizer"):      # the stand-in base: keep what configure_optimizers reads
             self.hparams.optimizer, self.hparams.scheduler, self.hparams.scheduler_params = optimizer, scheduler, scheduler_params or {}
         self.temperature = temperature
