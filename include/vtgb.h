@@ -1275,6 +1275,53 @@ int vtgb_layernorm_train_backward(const vtgb_layernorm_train_args* a, vtgb_strea
 int vtgb_gelu_forward(const float* x, float* y, int64_t n, vtgb_stream_t stream);
 int vtgb_gelu_backward(const float* x, const float* dy, float* dx, int64_t n, vtgb_stream_t stream);
 
+/* ---- the language model's training pass (config C5 under LoRA: videotgb_amd.train.llama_with_grad) ---------------------------
+ * Added at version 601 without a version bump (the existing entries are unchanged).  What a LlamaDecoderLayer (transformers
+ * modeling_llama.py) runs between its linear layers, forward and backward, fp32 and token-major like the rest of the training graph; every
+ * sum in a fixed order, no atomics.  All checks run on the host before any launch.
+ * vtgb_rmsnorm_train_forward: LlamaRMSNorm.forward (variance = x.pow(2).mean(-1); x * rsqrt(variance + eps); weight * x) with the residual add
+ *   in front of it (LlamaDecoderLayer.forward: hidden_states = residual + hidden_states) folded in: sum = x (+ delta, or NULL; `sum` may be
+ *   NULL without a delta), y = gamma * (sum * rstd), rstd [rows] = rsqrt(mean(sum^2) + eps) kept for the backward.
+ *   _backward: from dy, sum (= x when there was no delta), rstd, gamma -> ds = rstd * (gamma . dy) - sum * rstd^3 / D * SUM(gamma . dy . sum),
+ *   (+ dsum, or NULL: the gradient that reaches `sum` from its other consumers -- the residual stream past this norm -- added in the same
+ *   pass; ds may be dsum), the gradient of x and of delta alike.  gamma is frozen under LoRA: there is no dgamma.  VTGB_EINVAL for a NULL operand, a non-positive size
+ *   or a buffer that is not 16-byte aligned; VTGB_EUNSUPPORTED unless D % 4 == 0 and D <= 8192.
+ * vtgb_rope_train: apply_rotary_pos_emb (q * cos + rotate_half(q) * sin) on the nh query and nkv key heads of x [B, S, (nh + 2 nkv) * hd]
+ *   (q heads | k heads | v heads) -> y of the same shape, the v heads copied.  cos / sin: fp32 [S, hd], row = position.  conjugate != 0
+ *   applies the transposed rotation: the backward (dx from dy) is the same launch with the flag set.  VTGB_EINVAL for a NULL operand, a
+ *   non-positive size, an odd hd or y == x; VTGB_EUNSUPPORTED for hd > 128.
+ * vtgb_swiglu_train_forward: LlamaMLP's act_fn(gate_proj(x)) * up_proj(x) on gu [M, 2 I] = [gate | up] -> act [M, I] = silu(gate) * up.
+ *   _backward: dgu [M, 2 I] from dact and gu: dgate = dact * up * sig(g) (1 + g (1 - sig(g))), dup = dact * silu(gate).  VTGB_EINVAL for a
+ *   NULL operand or a non-positive size.
+ * vtgb_attn_train_causal_forward / _backward: eager_attention_forward under the causal mask (softmax(q k^T * scale + causal + key_mask) v
+ *   with repeat_kv), on the struct of vtgb_attn_train_forward: key j is visible to query i when j <= i; k / v (and dk / dv) hold kv_heads heads
+ *   at the strides kv_tok / kv_batch, query head h reads K/V head h / (heads / kv_heads), and dk / dv of a K/V head are the sums over its
+ *   query heads in head order.  The additive key_mask [batch, s_kv] still applies; its entries must be FINITE
+ *   (the most negative float, as finfo(float32).min, for a padded key; a literal -inf on the first visible key of a row makes the running maximum
+ *   -inf - -inf = NaN -- the non-causal entries share this).  VTGB_EINVAL for NULL args or a NULL operand, a non-positive
+ *   size, s_q != s_kv, heads % kv_heads != 0 or a non-NULL drop; VTGB_EUNSUPPORTED for head_dim > 128. */
+typedef struct {
+    int32_t rows, D;
+    float eps;
+    const float* x;
+    const float* delta; /* or NULL */
+    const float* gamma;
+    float* sum;         /* required with a delta */
+    float* y;
+    float* rstd;
+    const float* dy; /* backward only from here */
+    float* ds;
+    const float* dsum; /* or NULL */
+} vtgb_rmsnorm_train_args;
+int vtgb_rmsnorm_train_forward(const vtgb_rmsnorm_train_args* a, vtgb_stream_t stream);
+int vtgb_rmsnorm_train_backward(const vtgb_rmsnorm_train_args* a, vtgb_stream_t stream);
+int vtgb_rope_train(const float* x, float* y, const float* cos_t, const float* sin_t, int32_t B, int32_t S, int32_t nh, int32_t nkv, int32_t hd,
+                    int32_t conjugate, vtgb_stream_t stream);
+int vtgb_swiglu_train_forward(const float* gu, float* act, int32_t M, int32_t I, vtgb_stream_t stream);
+int vtgb_swiglu_train_backward(const float* gu, const float* dact, float* dgu, int32_t M, int32_t I, vtgb_stream_t stream);
+int vtgb_attn_train_causal_forward(const vtgb_attn_train_args* a, int32_t kv_heads, vtgb_stream_t stream);
+int vtgb_attn_train_causal_backward(const vtgb_attn_train_args* a, int32_t kv_heads, vtgb_stream_t stream);
+
 /* ---- gradient exchange (config C5; the one collective of the path) ------------------------------------------------
  * Thin wrapper over RCCL (SURVEY.md 8b "later: vtgb_allreduce_f32", 8e): replaces what Lightning's DDPStrategy does for the reference
  * (configs/trainer/ddp.yaml:4, find_unused_parameters: the sum / mean all-reduce of the trainable gradients once per optimizer

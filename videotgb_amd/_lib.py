@@ -51,6 +51,8 @@ EXPORTS = [
     "vtgb_raft_stem_workspace_bytes", "vtgb_raft_stem", "vtgb_llm_lora_parts", "vtgb_llm_pick_greedy", "vtgb_llm_beam_candidates_eos",
     "vtgb_llm_repetition_penalty",
     "vtgb_raft_layer1_h8_workspace_bytes", "vtgb_raft_layer1_h8",
+    "vtgb_rmsnorm_train_forward", "vtgb_rmsnorm_train_backward", "vtgb_rope_train", "vtgb_swiglu_train_forward", "vtgb_swiglu_train_backward",
+    "vtgb_attn_train_causal_forward", "vtgb_attn_train_causal_backward",
 ]
 COMM_ID_BYTES = 128
 
@@ -71,6 +73,10 @@ class GemmTrainArgs(C.Structure):
 class LayerNormTrainArgs(C.Structure):
     _fields_ = [("rows", i32), ("D", i32), ("eps", f32), ("x", vp), ("mask", vp), ("resid", vp), ("gamma", vp), ("beta", vp), ("sum", vp),
                 ("y", vp), ("mean", vp), ("rstd", vp), ("dy", vp), ("ds", vp), ("dx", vp), ("dgamma", vp), ("dbeta", vp), ("partial", vp)]
+
+
+class RmsNormTrainArgs(C.Structure):
+    _fields_ = [("rows", i32), ("D", i32), ("eps", f32), ("x", vp), ("delta", vp), ("gamma", vp), ("sum", vp), ("y", vp), ("rstd", vp), ("dy", vp), ("ds", vp), ("dsum", vp)]
 
 
 class VtgbError(RuntimeError):
@@ -459,6 +465,16 @@ def lib() -> C.CDLL:
     L.vtgb_gelu_backward.argtypes = [vp, vp, vp, i64, vp]
     for fn in (L.vtgb_gemm_train, L.vtgb_col_sum_f32, L.vtgb_layernorm_train_forward, L.vtgb_layernorm_train_backward, L.vtgb_gelu_forward,
                L.vtgb_gelu_backward):
+        fn.restype = C.c_int
+    for fn in (L.vtgb_rmsnorm_train_forward, L.vtgb_rmsnorm_train_backward):
+        fn.argtypes = [C.POINTER(RmsNormTrainArgs), vp]
+    L.vtgb_rope_train.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    L.vtgb_swiglu_train_forward.argtypes = [vp, vp, i32, i32, vp]
+    L.vtgb_swiglu_train_backward.argtypes = [vp, vp, vp, i32, i32, vp]
+    for fn in (L.vtgb_attn_train_causal_forward, L.vtgb_attn_train_causal_backward):
+        fn.argtypes = [C.POINTER(AttnTrainArgs), i32, vp]
+    for fn in (L.vtgb_rmsnorm_train_forward, L.vtgb_rmsnorm_train_backward, L.vtgb_rope_train, L.vtgb_swiglu_train_forward, L.vtgb_swiglu_train_backward,
+               L.vtgb_attn_train_causal_forward, L.vtgb_attn_train_causal_backward):
         fn.restype = C.c_int
     L.vtgb_comm_unique_id.argtypes = [vp]
     L.vtgb_comm_init.argtypes = [C.POINTER(vp), vp, i32, i32]

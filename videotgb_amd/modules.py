@@ -172,11 +172,12 @@ class _LSTPLightningBase(_Base):
     LORA = None                 # IVT: "CAUSAL_LM" / "SEQ_2_SEQ_LM"
     SAMPLER_IS_STATE_DICT = False
     SELF_REFINE = False         # SF: pseudo labels + MRC loss in forward
+    train_lm = "hf"             # (class default: a twin assembled without __init__ keeps HF's language-model path)
 
     def __init__(self, model_name_or_path: str, sampler_name_or_path: str, of_extractor_name_or_path: str, temperature: float = 1.0,
                  optimizer=None, scheduler: Optional[str] = None, scheduler_params: Optional[dict] = None,
                  generate_configs: Optional[dict] = None, compute_dtype="bf16", processor=None, tgb_cfg: Optional[synth.TgbCfg] = None,
-                 decode_weights: str = "bf16", kv_cache: str = "bf16", beam_search: str = "hf", eos_sets: str = "hf", sampled_decode: str = "hf",
+                 train_lm: str = "hf", decode_weights: str = "bf16", kv_cache: str = "bf16", beam_search: str = "hf", eos_sets: str = "hf", sampled_decode: str = "hf",
                  penalty_decode: str = "hf"):
         super().__init__()
         self.save_hyperparameters(logger=False)
@@ -190,6 +191,9 @@ class _LSTPLightningBase(_Base):
         self.eos_sets = check_mode("eos_sets", eos_sets)
         self.sampled_decode = check_mode("sampled_decode", sampled_decode)
         self.penalty_decode = check_mode("penalty_decode", penalty_decode)
+        # the training-side opt-in (not a decode mode; the decode modes keep the end of the signature): "own" = ``forward`` takes the decoder-only language model's logits from
+        # train.llama_with_grad (forward and backward on the library's kernels) instead of HF's ``lm(...)``
+        self.train_lm = train.check_train_lm(train_lm)
         if not hasattr(self.hparams, "optimizer"):      # the stand-in base: keep what configure_optimizers reads
             self.hparams.optimizer, self.hparams.scheduler, self.hparams.scheduler_params = optimizer, scheduler, scheduler_params or {}
         self.temperature = temperature
@@ -212,6 +216,12 @@ class _LSTPLightningBase(_Base):
         if self.LORA:
             train.apply_lora(self.model.language_model, r=8, lora_alpha=32, lora_dropout=0.1)
         self.freeze_weights()
+        if self.train_lm == "own":
+            if not self.model.config.use_decoder_only_language_model:
+                raise NotImplementedError("train_lm='own' is implemented for the Llama language model only (a seq2seq model's label loss stays HF's)")
+            state = train.llama_train_state(self.model.language_model)
+            if state is not None:
+                raise NotImplementedError(f"train_lm='own': a language model outside the training graph's statement -- {state}")
 
     # ---- the eval twin's ``prefix`` signature, so refine.frame_answers can drive a LightningModule twin as well
     @torch.no_grad()
@@ -367,7 +377,10 @@ class _LSTPLightningBase(_Base):
             if lm_inputs is not None:
                 emb = torch.cat([lm_inputs.to(emb.dtype), emb], dim=1)
                 attention_mask = torch.cat([torch.ones(lm_inputs.shape[:2], dtype=torch.long, device=emb.device), attention_mask], dim=1)
-            logits = lm(inputs_embeds=emb, attention_mask=attention_mask)[0]
+            if self.train_lm == "own":
+                logits = train.llama_with_grad(lm, emb, attention_mask, dropout=self._dropout())
+            else:
+                logits = lm(inputs_embeds=emb, attention_mask=attention_mask)[0]
             loss = train.shifted_cross_entropy(logits, labels)
         else:
             emb = lm.get_input_embeddings()(batch["question"])

@@ -18,10 +18,13 @@
   vtgb_tgb_forward) keep no activations and have no dropout: they serve eval.  Dropout (Q-Former / TGB hidden and
   attention-probability dropout 0.1; LoRA dropout inside ``LoraLinear``) enters as injectable masks (``Dropout``).
 
-The language model itself, autograd through it and AdamW stay PyTorch, as they are third-party in the reference.
+The language model itself, autograd through it and AdamW stay PyTorch, as they are third-party in the reference -- unless the caller opts in
+to ``train_lm="own"``: ``llama_with_grad`` then states a Llama's training forward as the same kind of graph (``_HipLinear`` for every
+projection and adapter, RMSNorm / rotary / SwiGLU / causal grouped-head attention on train_llm.hip, forward and backward).
 """
 import ctypes as C
 import math
+import weakref
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import torch
@@ -563,6 +566,293 @@ def freeze_weights(module: nn.Module) -> None:
             p.requires_grad = False
 
 
+# ----------------------------------------------------------------------------- the language model's training pass (opt-in: train_lm="own")
+RMSNORM_TRAIN_MAX_D = 8192      # vtgb_rmsnorm_train_*: D % 4 == 0, D <= 8192
+TRAIN_LM = ("hf", "own")
+LLAMA_PROJECTIONS = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
+
+
+def check_train_lm(value: str) -> str:
+    if value not in TRAIN_LM:
+        raise ValueError(f"train_lm={value!r}: one of {TRAIN_LM}")
+    return value
+
+
+class _HipRmsNorm(torch.autograd.Function):
+    """(y, sum) = (gamma * rmsnorm(x + delta), x + delta) on vtgb_rmsnorm_train_forward / _backward: LlamaRMSNorm with the decoder layer's
+    residual add in front of it.  ``sum`` is the residual stream: the gradient its later consumers return is added inside the backward
+    kernel.  ``gamma`` is a constant of this node (frozen under ``apply_lora``)."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, delta: Optional[Tensor], gamma: Tensor, eps: float):
+        _need_cuda(x)
+        if gamma.requires_grad:
+            raise NotImplementedError("rms_norm: a trainable RMSNorm weight (the kernel has no dgamma; apply_lora freezes it)")
+        D = x.shape[-1]
+        x2 = x.reshape(-1, D).float().contiguous()
+        d2 = None if delta is None else delta.reshape(-1, D).float().contiguous()
+        g = gamma.detach().float().contiguous()
+        rows = x2.shape[0]
+        y = torch.empty_like(x2)
+        s = torch.empty_like(x2)                 # (without a delta a copy of x: the node's own output, never an alias of its input)
+        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+        a = L.RmsNormTrainArgs(rows, D, float(eps), x2.data_ptr(), None if d2 is None else d2.data_ptr(), g.data_ptr(), s.data_ptr(), y.data_ptr(),
+                               rstd.data_ptr(), None, None, None)
+        L.check(L.lib().vtgb_rmsnorm_train_forward(C.byref(a), _stream()))
+        ctx.save_for_backward(s, g, rstd)
+        ctx.eps, ctx.shape, ctx.has_delta = float(eps), x.shape, delta is not None
+        ctx.set_materialize_grads(False)         # an unused residual stream (the final norm) arrives as None, not as a tensor of zeros
+        return y.view(x.shape), s.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, gy: Tensor, gsum: Optional[Tensor]):
+        s, g, rstd = ctx.saved_tensors
+        rows, D = s.shape
+        dy = (torch.zeros_like(s) if gy is None else gy).reshape(rows, D).float().contiguous()
+        dsum = None if gsum is None else gsum.reshape(rows, D).float().contiguous()
+        ds = torch.empty_like(s)
+        a = L.RmsNormTrainArgs(rows, D, ctx.eps, None, None, g.data_ptr(), s.data_ptr(), None, rstd.data_ptr(), dy.data_ptr(), ds.data_ptr(),
+                               None if dsum is None else dsum.data_ptr())
+        L.check(L.lib().vtgb_rmsnorm_train_backward(C.byref(a), _stream()))
+        ds = ds.view(ctx.shape)
+        return ds, (ds if ctx.has_delta else None), None, None
+
+
+class _HipRope(torch.autograd.Function):
+    """apply_rotary_pos_emb on the q and k heads of a [B, S, (nh + 2 nkv) hd] projection (vtgb_rope_train); the backward is the same
+    launch with ``conjugate`` set."""
+
+    @staticmethod
+    def _run(x: Tensor, cos: Tensor, sin: Tensor, nh: int, nkv: int, hd: int, conjugate: int) -> Tensor:
+        y = torch.empty_like(x)
+        L.check(L.lib().vtgb_rope_train(x.data_ptr(), y.data_ptr(), cos.data_ptr(), sin.data_ptr(), x.shape[0], x.shape[1], nh, nkv, hd, conjugate, _stream()))
+        return y
+
+    @staticmethod
+    def forward(ctx, qkv: Tensor, cos: Tensor, sin: Tensor, nh: int, nkv: int, hd: int):
+        _need_cuda(qkv, cos, sin)
+        if qkv.dim() != 3 or qkv.shape[-1] != (nh + 2 * nkv) * hd or tuple(cos.shape) != (qkv.shape[1], hd) or cos.shape != sin.shape:
+            raise ValueError(f"rope: qkv {tuple(qkv.shape)} with nh={nh} nkv={nkv} hd={hd} and tables {tuple(cos.shape)} / {tuple(sin.shape)}")
+        cos, sin = cos.float().contiguous(), sin.float().contiguous()
+        ctx.save_for_backward(cos, sin)
+        ctx.geom = (nh, nkv, hd)
+        return _HipRope._run(qkv.float().contiguous(), cos, sin, nh, nkv, hd, 0)
+
+    @staticmethod
+    def backward(ctx, gy: Tensor):
+        cos, sin = ctx.saved_tensors
+        return _HipRope._run(gy.float().contiguous(), cos, sin, *ctx.geom, 1), None, None, None, None, None
+
+
+class _HipSwiGlu(torch.autograd.Function):
+    """silu(gate) * up on gu [..., 2 I] = [gate | up] (vtgb_swiglu_train_forward / _backward)."""
+
+    @staticmethod
+    def forward(ctx, gu: Tensor):
+        _need_cuda(gu)
+        I = gu.shape[-1] // 2
+        g2 = gu.reshape(-1, 2 * I).float().contiguous()
+        act = torch.empty(g2.shape[0], I, dtype=torch.float32, device=gu.device)
+        L.check(L.lib().vtgb_swiglu_train_forward(g2.data_ptr(), act.data_ptr(), g2.shape[0], I, _stream()))
+        ctx.save_for_backward(g2)
+        ctx.shape = gu.shape
+        return act.view(*gu.shape[:-1], I)
+
+    @staticmethod
+    def backward(ctx, gact: Tensor):
+        (g2,) = ctx.saved_tensors
+        I = g2.shape[1] // 2
+        d = gact.reshape(-1, I).float().contiguous()
+        dgu = torch.empty_like(g2)
+        L.check(L.lib().vtgb_swiglu_train_backward(g2.data_ptr(), d.data_ptr(), dgu.data_ptr(), g2.shape[0], I, _stream()))
+        return dgu.view(ctx.shape)
+
+
+class _HipCausalAttention(torch.autograd.Function):
+    """softmax(q k^T * scale + causal + key_mask) v with grouped heads on vtgb_attn_train_causal_forward / _backward.  ``qkv`` [B, S, (nh + 2 nkv) hd]
+    (q heads | k heads | v heads, the rotary embedding applied) is read in place through the kernel's strides, and the backward writes one
+    gradient of the same layout; key_mask additive [B, S] or None.  -> [B, S, nh hd]."""
+
+    @staticmethod
+    def _args(qkv, nh, nkv, hd, scale, key_mask, out, lse):
+        B, S, W = qkv.shape
+        base, e = qkv.data_ptr(), qkv.element_size()
+        return L.AttnTrainArgs(B, nh, hd, S, S, base, base + nh * hd * e, base + (nh + nkv) * hd * e, W, W, S * W, S * W,
+                               None if key_mask is None else key_mask.data_ptr(), None, float(scale), out.data_ptr(), out.stride(1), out.stride(0),
+                               lse.data_ptr(), None, None, None, None, None)
+
+    @staticmethod
+    def forward(ctx, qkv: Tensor, nh: int, nkv: int, hd: int, scale: float, key_mask: Optional[Tensor]):
+        _need_cuda(qkv)
+        if qkv.dim() != 3 or qkv.shape[-1] != (nh + 2 * nkv) * hd:
+            raise ValueError(f"causal attention: qkv {tuple(qkv.shape)} with nh={nh} nkv={nkv} hd={hd}")
+        qkv = qkv.float().contiguous()
+        key_mask = None if key_mask is None else key_mask.float().contiguous()
+        B, S, _ = qkv.shape
+        out = torch.empty(B, S, nh * hd, dtype=torch.float32, device=qkv.device)
+        lse = torch.empty(B, nh, S, dtype=torch.float32, device=qkv.device)
+        a = _HipCausalAttention._args(qkv, nh, nkv, hd, scale, key_mask, out, lse)
+        L.check(L.lib().vtgb_attn_train_causal_forward(C.byref(a), nkv, _stream()))
+        ctx.save_for_backward(qkv, out, lse, key_mask)
+        ctx.geom = (nh, nkv, hd, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, go: Tensor):
+        qkv, out, lse, key_mask = ctx.saved_tensors
+        nh, nkv, hd, scale = ctx.geom
+        go = go.float().contiguous()
+        dqkv = torch.empty_like(qkv)
+        delta = torch.empty_like(lse)
+        a = _HipCausalAttention._args(qkv, nh, nkv, hd, scale, key_mask, out, lse)
+        base, e = dqkv.data_ptr(), dqkv.element_size()
+        a.dout, a.dq, a.dk, a.dv, a.delta = go.data_ptr(), base, base + nh * hd * e, base + (nh + nkv) * hd * e, delta.data_ptr()
+        L.check(L.lib().vtgb_attn_train_causal_backward(C.byref(a), nkv, _stream()))
+        return dqkv, None, None, None, None, None
+
+
+def rms_norm(x: Tensor, gamma: Tensor, eps: float, delta: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """(gamma * rmsnorm(x + delta), x + delta)."""
+    return _HipRmsNorm.apply(x, delta, gamma, eps)
+
+
+def _llama_geometry(lm) -> Tuple[int, int, int]:
+    cfg = lm.config
+    nh = cfg.num_attention_heads
+    nkv = getattr(cfg, "num_key_value_heads", None) or nh
+    hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // nh
+    return nh, nkv, hd
+
+
+def llama_config_state(lm) -> Optional[str]:
+    """The part of ``llama_train_state`` that reads the architecture and the configuration alone (no walk over modules and parameters, nothing
+    about adapters or what is trainable): what a constructor checks BEFORE it wraps projections with adapters."""
+    from .decode import llama_state
+    state = llama_state(lm)
+    if state is not None:
+        return state
+    cfg = lm.config
+    if float(getattr(cfg, "attention_dropout", 0.0) or 0.0) > 0.0:
+        return f"attention_dropout {cfg.attention_dropout}: the causal attention kernel has no dropout on the probabilities"
+    if int(getattr(cfg, "pretraining_tp", 1) or 1) > 1:
+        return f"pretraining_tp {cfg.pretraining_tp}: sliced projections"
+    nh, nkv, hd = _llama_geometry(lm)
+    if hd % 2 or hd > 128:
+        return f"head_dim {hd}: the rotary and attention kernels serve even head dimensions up to 128"
+    if nh % nkv:
+        return f"{nh} attention heads over {nkv} key / value heads"
+    H = cfg.hidden_size
+    if H % 4 or H > RMSNORM_TRAIN_MAX_D:
+        return f"hidden_size {H}: the RMSNorm kernel serves multiples of 4 up to {RMSNORM_TRAIN_MAX_D}"
+    return None
+
+
+def llama_train_state(lm) -> Optional[str]:
+    """None: ``llama_with_grad`` states this language model's training forward -- a LlamaForCausalLM (``decode.llama_state``: position-only
+    rotary types, SwiGLU, the norm -> attention -> norm -> MLP layer), frozen but for ``LoraLinear`` adapters on its layer projections.  Any
+    string: what the graph does not compute; it raises NotImplementedError with it and never trains such a model as a plain Llama.  The walk
+    over the modules and parameters costs ~5 ms of host time at 32 layers: ``llama_with_grad`` runs it on a model's first call and afterwards
+    only guards, per call, what it actually reads (``_STATED``)."""
+    state = llama_config_state(lm)
+    if state is not None:
+        return state
+    sites = {id(getattr(getattr(l, part), p)) for l in lm.model.layers for part, ps in (("self_attn", LLAMA_PROJECTIONS[:4]), ("mlp", LLAMA_PROJECTIONS[4:]))
+             for p in ps}
+    for name, mod in lm.named_modules():
+        adapter = hasattr(mod, "lora_A") or hasattr(mod, "lora_B")
+        if id(mod) in sites:
+            if adapter and not isinstance(mod, LoraLinear):
+                return f"{name}: an adapter that is not a train.LoraLinear ({type(mod).__name__})"
+            if not isinstance(mod, nn.Linear):
+                return f"{name}: a {type(mod).__name__} where the graph states nn.Linear"
+            if isinstance(mod, LoraLinear) and set(mod.lora_A.keys()) != {"default"}:
+                return f"{name}: adapters {sorted(mod.lora_A.keys())} (one adapter named 'default' is stated)"
+        elif adapter:
+            return f"{name}: an adapter outside the layers' seven projections"
+    for name, p in lm.named_parameters():
+        if p.requires_grad and "lora_" not in name:
+            return f"{name}: a trainable parameter that is no adapter (the graph computes input and adapter gradients only)"
+    return None
+
+
+_STATED = weakref.WeakSet()      # language models llama_train_state has passed once (llama_with_grad)
+
+
+def _llama_rope_tables(lm, S: int, device) -> Tuple[Tensor, Tensor]:
+    """cos / sin [S, hd] fp32 of positions 0 .. S-1 from the model's own rotary module (``inv_freq`` and ``attention_scaling``), as
+    LlamaRotaryEmbedding.forward computes them and ``GreedyDecoder._rope`` builds them."""
+    rot = getattr(lm.model, "rotary_emb", None)
+    inv = getattr(rot, "inv_freq", None)
+    if isinstance(inv, Tensor):
+        inv, factor = inv.detach().float().to(device), float(getattr(rot, "attention_scaling", 1.0))
+    else:
+        _, _, hd = _llama_geometry(lm)
+        theta = float(getattr(lm.config, "rope_theta", 10000.0))
+        inv, factor = 1.0 / (theta ** (torch.arange(0, hd, 2, device=device, dtype=torch.float32) / hd)), 1.0
+    fr = torch.arange(S, device=device, dtype=torch.float32)[:, None] * inv[None]
+    emb = torch.cat((fr, fr), dim=-1)
+    return emb.cos() * factor, emb.sin() * factor
+
+
+def llama_with_grad(lm, inputs_embeds: Tensor, attention_mask: Optional[Tensor], compute_dtype=None, dropout: Optional[Dropout] = None) -> Tensor:
+    """``lm(inputs_embeds=..., attention_mask=...).logits`` of an HF LlamaForCausalLM [B, S, V] fp32 WITH gradients to ``inputs_embeds`` and to
+    the ``LoraLinear`` adapters, as an autograd graph over the model's LIVE parameters (built like ``_qformer_graph``): per layer
+    RMSNorm (residual add folded in) -> q | k | v -> rotary -> causal grouped-head attention -> o_proj -> RMSNorm -> gate | up -> SwiGLU -> down,
+    then the final norm and ``lm_head`` (modeling_llama.py LlamaDecoderLayer / LlamaModel / LlamaForCausalLM.forward).  Every linear layer is
+    ``_HipLinear`` (a frozen weight costs forward + dgrad; its bias where the model has one); a ``LoraLinear`` on any of the seven projections
+    adds ``lora_B(lora_A(dropout(x))) * scaling`` from two more.  Positions are arange(S) whatever the mask (HF without ``position_ids``);
+    ``attention_mask`` [B, S] of 0 / 1 becomes the additive key mask.  ``compute_dtype``: "f32" or "bf16" GEMM operands (default: the model's
+    dtype).  ``dropout``: the LoRA dropout sites, named ``<module name>.lora_dropout`` (``Dropout(p)`` draws with ITS p; recorded in ``drawn``)."""
+    if lm not in _STATED:            # the full statement check once per model; later calls guard each weight and adapter where they read it
+        state = llama_train_state(lm)
+        if state is not None:
+            raise NotImplementedError(f"a language model outside the training graph's statement -- {state}; use train_lm='hf'")
+    _need_cuda(inputs_embeds)
+    drop = dropout or _NO_DROPOUT
+    cfg = lm.config
+    code = dtype_code(compute_dtype) if compute_dtype is not None else dtype_code(lm.lm_head.weight.dtype)
+    nh, nkv, hd = _llama_geometry(lm)
+    B, S, _ = inputs_embeds.shape
+    dev = inputs_embeds.device
+    cos, sin = _llama_rope_tables(lm, S, dev)
+    key_mask = None
+    if attention_mask is not None:
+        if tuple(attention_mask.shape) != (B, S):
+            raise ValueError(f"attention_mask of shape {tuple(attention_mask.shape)} for inputs_embeds of {B} x {S} positions")
+        key_mask = torch.zeros(B, S, dtype=torch.float32, device=dev).masked_fill_(attention_mask.to(dev) == 0, torch.finfo(torch.float32).min)
+    eps = cfg.rms_norm_eps
+    scale = 1.0 / math.sqrt(hd)
+
+    def lin(name: str, mod: nn.Linear, x: Tensor) -> Tensor:
+        if mod.weight.requires_grad or (mod.bias is not None and mod.bias.requires_grad):
+            raise NotImplementedError(f"a language model outside the training graph's statement -- {name}.weight: a trainable parameter that is no "
+                                      "adapter (the graph computes input and adapter gradients only); use train_lm='hf'")
+        if not isinstance(mod, LoraLinear) and (hasattr(mod, "lora_A") or not isinstance(mod, nn.Linear)):
+            raise NotImplementedError(f"a language model outside the training graph's statement -- {name}: an adapter that is not a train.LoraLinear "
+                                      f"({type(mod).__name__}); use train_lm='hf'")
+        y = _HipLinear.apply(x, mod.weight, mod.bias, code)
+        if isinstance(mod, LoraLinear):
+            a, b = mod.lora_A["default"], mod.lora_B["default"]
+            z = _HipLinear.apply(drop(name + ".lora_dropout", x), a.weight, a.bias, code)
+            y = y + _HipLinear.apply(z * mod.scaling, b.weight, b.bias, code)      # (the scaling on the rank-r side: r columns, not N)
+        return y
+
+    x, delta = inputs_embeds.float(), None
+    for li, layer in enumerate(lm.model.layers[: cfg.num_hidden_layers]):
+        at, mlp, p = layer.self_attn, layer.mlp, f"model.layers.{li}."
+        h, x = rms_norm(x, layer.input_layernorm.weight, getattr(layer.input_layernorm, "variance_epsilon", eps), delta)
+        qkv = torch.cat([lin(p + "self_attn." + n, getattr(at, n), h) for n in ("q_proj", "k_proj", "v_proj")], dim=-1)
+        ctx = _HipCausalAttention.apply(_HipRope.apply(qkv, cos, sin, nh, nkv, hd), nh, nkv, hd, scale, key_mask)
+        delta = lin(p + "self_attn.o_proj", at.o_proj, ctx)
+        h, x = rms_norm(x, layer.post_attention_layernorm.weight, getattr(layer.post_attention_layernorm, "variance_epsilon", eps), delta)
+        gu = torch.cat([lin(p + "mlp.gate_proj", mlp.gate_proj, h), lin(p + "mlp.up_proj", mlp.up_proj, h)], dim=-1)
+        delta = lin(p + "mlp.down_proj", mlp.down_proj, _HipSwiGlu.apply(gu))
+    h, _ = rms_norm(x, lm.model.norm.weight, getattr(lm.model.norm, "variance_epsilon", eps), delta)
+    logits = lin("lm_head", lm.lm_head, h)
+    _STATED.add(lm)
+    return logits
+
+
 # ----------------------------------------------------------------------------- optimizer
 def cosine_schedule_lambda(num_warmup_steps: int, num_training_steps: int, num_cycles: float = 0.5):
     """The lr lambda of transformers.get_cosine_schedule_with_warmup (4.36.0)."""
@@ -596,15 +886,42 @@ class LoraTrainStep:
     with LoRA -> shifted CE (HIP) -> backward; every ``accumulate_grad_batches`` micro-batches ALL trainable gradients (Q-Former
     185.7 M + projections + query tokens + 4.19 M adapter parameters = the reference's ~785 MB fp32) are summed over the
     ranks in one flat bucket and AdamW steps (configs/experiment/LSTP_instructblipvicuna7b_ivtinstruct.yaml:34
-    accumulate_grad_batches=4).  ``train_prefix=False`` keeps the round-1 adapters-only step (not reference-equivalent)."""
+    accumulate_grad_batches=4).  ``train_prefix=False`` keeps the round-1 adapters-only step (not reference-equivalent).
+    ``train_lm``: "hf" (default) calls the HF language model; "own" (opt-in, Llama only) takes the logits from ``llama_with_grad`` -- the
+    language model's forward and backward on the library's kernels.  Under "own" the LoRA dropout of a model in training mode is drawn from
+    ``lm_dropout`` (a ``Dropout``; None: a fresh ``Dropout(p of the adapters, generator=dropout_generator)`` per call), and the masks of
+    the last call are kept in ``drawn``; ``lm_compute_dtype`` ("f32" / "bf16"; None: the model's dtype) is the own pass's GEMM operand format.
+    ``lora_target_modules``: ``apply_lora``'s (None: peft's defaults)."""
+
+    # the own pass's switches, as class defaults: a step assembled without __init__ (attributes set by hand) runs HF's path, as it always did
+    train_lm = "hf"
+    lm_compute_dtype = None
+    lm_dropout: Optional[Dropout] = None
+    dropout_generator: Optional[torch.Generator] = None
 
     def __init__(self, lstp, pad_token_id: int, lr: float = 1e-4, weight_decay: float = 0.0, accumulate_grad_batches: int = 4,
-                 train_prefix: bool = True, use_rccl: bool = True):
+                 train_prefix: bool = True, use_rccl: bool = True, train_lm: str = "hf", lm_compute_dtype=None,
+                 lora_target_modules: Optional[Sequence[str]] = None):
         from .dist import FlatGradBucket
         self.m = lstp
         self.lm = lstp.model.language_model
         self.pad_token_id = pad_token_id
-        self.params = apply_lora(self.lm)
+        self.train_lm = check_train_lm(train_lm)
+        if self.train_lm == "own":      # refused before anything is changed: the adapters go on only once the architecture is known to be stated
+            if getattr(getattr(self.lm, "config", None), "model_type", "") == "t5":
+                raise NotImplementedError("train_lm='own' is implemented for the Llama language model only (a seq2seq model's label loss stays HF's)")
+            state = llama_config_state(self.lm)
+            if state is not None:
+                raise NotImplementedError(f"train_lm='own': a language model outside the training graph's statement -- {state}")
+        self.lm_compute_dtype = lm_compute_dtype
+        self.params = apply_lora(self.lm, target_modules=lora_target_modules)
+        if self.train_lm == "own":
+            state = llama_train_state(self.lm)
+            if state is not None:
+                raise NotImplementedError(f"train_lm='own': a language model outside the training graph's statement -- {state}")
+        self.lm_dropout: Optional[Dropout] = None
+        self.dropout_generator: Optional[torch.Generator] = None
+        self.drawn: Dict[str, Tensor] = {}
         freeze_weights(lstp)
         self.train_prefix = train_prefix
         if train_prefix:
@@ -642,8 +959,21 @@ class LoraTrainStep:
         emb = self.lm.get_input_embeddings()(llm_tokens["input_ids"])
         inputs_embeds = torch.cat([language_model_inputs.to(emb.dtype), emb], dim=1)
         attention_mask = torch.cat([torch.ones(B, P, dtype=torch.long, device=emb.device), llm_tokens["attention_mask"]], dim=1)
-        logits = self.lm(inputs_embeds=inputs_embeds, attention_mask=attention_mask)[0]
+        if self.train_lm == "own":
+            logits = llama_with_grad(self.lm, inputs_embeds, attention_mask, self.lm_compute_dtype, self._lm_dropout())
+        else:
+            logits = self.lm(inputs_embeds=inputs_embeds, attention_mask=attention_mask)[0]
         return shifted_cross_entropy(logits, labels)
+
+    def _lm_dropout(self) -> Optional[Dropout]:
+        """The LoRA dropout of the own pass: ``lm_dropout`` when set (recorded masks, a seeded generator), else -- in training mode only --
+        fresh masks at the adapters' own p.  ``drawn`` is the mask dictionary of this call."""
+        drop = self.lm_dropout
+        if drop is None and self.lm.training:
+            p = max((float(getattr(m.lora_dropout["default"], "p", 0.0)) for m in self.lm.modules() if isinstance(m, LoraLinear)), default=0.0)
+            drop = Dropout(p, generator=self.dropout_generator)
+        self.drawn = {} if drop is None else drop.drawn
+        return drop
 
     def step(self, language_model_inputs: Tensor, question: Tensor, question_mask: Tensor, answer: Tensor, answer_mask: Tensor) -> Tuple[Tensor, bool]:
         """One micro-batch from a prefix (``self.prefix(...)`` output: gradients flow into the Q-Former / projection when
